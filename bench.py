@@ -49,15 +49,25 @@ rank hashes every clustering's state (all ranks must agree) and rank 0 re-labels
 
 The JSON line also carries
   roofline      k_assign_f16_rw, the HBM-bound kernel of the path: algorithmic bytes N*d*4 + N*8 per launch over the
-                kernel's duration measured with HIP events on the library's stream around that launch alone.  `frac` / `achieved`
-                are the SUSTAINED figures (160 launches back to back, the median of the last third: the socket's power cap has
-                throttled the shader clock by then); `*_timed_region` = the launches inside the timed pass (device at rest)
+                kernel's duration measured with HIP events on the library's stream around that launch alone, inside the
+                timed pass (device at rest).  With --full, `frac` / `achieved` are the SUSTAINED figures (160 launches back to
+                back, the median of the last third: the socket's power cap has throttled the shader clock by then) and
+                `*_timed_region` keep the timed pass's figures
                 (`sweep_*` keys: the whole calc_best sweep incl. centre preparation and the exact re-check pass)
   roofline_mi   the candidate-permutation stream of the greedy loop (16 L bytes per iteration) vs HBM
+With --full (off by default: a plain run sets up, warms up, times the steps and prints the line) it also measures, after
+the timed region:
   variants      the same pipeline with the selection chunked (chunk_size = 100 shards = 100k clips, 10 chunks in
                 lockstep, computation.concurrent_chunks) -- a different, equally legal reference configuration
   cpu_baseline  the oracle (oracle/libacav_oracle.so, a C port of the reference algorithm incl. its dense
                 [B,P,C,C] scoring and per-iteration randperm) timed on this box's host cores on a bounded sample.
+(--no-variants / --no-cpu-baseline leave a leg out of a --full run.)
+
+--dump-outputs DIR (rank 0) writes what the last timed step computed, after the timed region, as DIR/<name>.npy in
+float32 / float64: every view's final k-means state (centers_v<i>, counts_v<i>), the labels of the assign sweep
+(labels [N, views]) and the selection (selected: clip ids in pick order, gains).  An array of more than 2^21 values
+keeps a fixed, seeded sample of its rows (<name>_rows.npy holds their indices): at most 64 MB in all.  The inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import contextlib
@@ -251,7 +261,11 @@ def main():
     ap.add_argument("--verify", action="store_true")  # cross-rank state hashes + an oracle sample on rank 0, outside the timed region
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-variants", action="store_true")
+    ap.add_argument("--full", action="store_true")  # the measurements beyond the headline (variants, sustained roofline, cpu_baseline)
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR")  # the last timed step's outputs as .npy
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     # the contract is ONE JSON line on stdout: whatever the libraries print there (RCCL's version banner at communicator
     # creation, for one) goes to stderr instead -- fd 1 is parked and handed back for the result line only
     sys.stdout.flush()
@@ -367,8 +381,9 @@ def main():
             res = select_chunked(a, types, chunk, wl["width"])
             t4 = time.perf_counter()
             S = [c0 * chunk + i for c0, (Sc, _) in enumerate(res) for i in Sc]
+            GAIN = [g for _, Gc in res for g in Gc]
             assert len(S) == subset and len(set(S)) == subset
-        last["S"], last["a"] = S, a
+        last["S"], last["GAIN"], last["a"] = S, GAIN, a
         if args.verify:
             last["states"] = [km.state_arrays() for km in kms]
         if timed:
@@ -390,6 +405,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, labels)
 
     verify = None
     if args.verify:
@@ -488,7 +506,7 @@ def main():
                              "us_per_step": st["train"] * 1e6 / train_steps,
                              "persistent_launches_and_fallbacks": last.get("train_stats")},
         }
-        if not args.no_variants and world == 1 and chunk is None and n >= 200_000:
+        if args.full and not args.no_variants and world == 1 and chunk is None and n >= 200_000:
             out["variants"] = {"chunked_lockstep": chunked_variant(last["a"], types, n, st)}
             if not mfma_bound:  # (an HBM figure: the K = 256 shapes)
                 bb = back_to_back_sweeps(lib, last["kms"][vq], xs[vq], labels[vq], n, bytes_per_launch)
@@ -506,11 +524,11 @@ def main():
                     rf["what_caps_it"] = ("socket power: back to back the filter pulls ~1.35 kW of the 1.4 kW cap (PVIOL 95-100 %), the shader "
                                           "clock falls 2.4 -> 1.55-1.65 GHz within ~50 ms; without the MFMAs (timing-only ablation) 0.93 kW, no "
                                           "throttling, 0.685-0.69: profiles/r06_filter_sustained.txt")
-        if not args.no_variants and world == 1 and k <= 256:
+        if args.full and not args.no_variants and world == 1 and k <= 256:
             del xs
             torch.cuda.empty_cache()
             out["variants"] = dict(out.get("variants", {}), assign_hard_data=assign_hard_variant(torch, lib, n, d, k, b, dev))
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(n, dims, k, b, 1234, chunk)
         if verify is not None:
             out["verify"] = verify
@@ -574,6 +592,40 @@ def run_verify(torch, dist, world, rank, last, xs, labels, dims, k, sample=16384
     if not ok:
         raise SystemExit("bench.py --verify FAILED on rank {}: {}".format(rank, verdict))
     return verdict
+
+
+DUMP_MAX_VALUES = 1 << 21  # per array: the whole dump stays under 64 MB on every workload (cfg5: ~60 MB)
+
+
+def _exact_float(ints):
+    """integers as float32 where every value is exact there (below 2^24), else float64"""
+    ints = np.asarray(ints)
+    return ints.astype(np.float32 if ints.size == 0 or np.abs(ints).max() < (1 << 24) else np.float64)
+
+
+def dump_outputs(out_dir, last, labels, seed=0):
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy -- every view's k-means state, the
+    assign sweep's labels [N, views] and the selection (clip ids in pick order and their gains).  Labels, ids and counters
+    are written as float32 where that is exact (else float64), centres and counts as float32, gains as float64.  An array
+    of more than DUMP_MAX_VALUES values keeps a sorted, seeded sample of its rows (the same rows from run to run), their
+    indices in DIR/<name>_rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for v, km in enumerate(last["kms"]):
+        centers, counts, count, fallback = km.state_arrays()
+        arrays[f"centers_v{v}"] = np.asarray(centers, np.float32)
+        arrays[f"counts_v{v}"] = np.asarray(counts, np.float32)
+        arrays[f"count_v{v}"] = np.array([count, fallback], np.float64)
+    arrays["labels"] = _exact_float(np.stack([lab.cpu().numpy() for lab in labels], 1))
+    arrays["selected"] = _exact_float(last["S"])
+    arrays["gains"] = np.asarray(last["GAIN"], np.float64)
+    for name, arr in arrays.items():
+        rows = arr.shape[0]
+        if arr.size > DUMP_MAX_VALUES:
+            keep = np.sort(np.random.default_rng(seed).choice(rows, DUMP_MAX_VALUES // (arr.size // rows), replace=False))
+            arr = arr[keep]
+            np.save(os.path.join(out_dir, f"{name}_rows.npy"), _exact_float(keep))
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
 
 
 def back_to_back_sweeps(lib, km, x, lab, n, bytes_per_launch, reps=160):

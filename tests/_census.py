@@ -16,7 +16,10 @@ U = 2.0 ** -24  # fp32 unit roundoff
 
 
 def load_case(name):
-    g = np.load(os.path.join(GOLDEN, f"kmeans_big_{name}.npz"))
+    g = dict(np.load(os.path.join(GOLDEN, f"kmeans_big_{name}.npz")))
+    centers = os.path.join(GOLDEN, f"kmeans_big_{name}_centers.npz")  # full centres: a file of their own (1 MiB per file)
+    if os.path.exists(centers):
+        g.update(np.load(centers))
     n, d, k = int(g["N"]), int(g["d"]), int(g["K"])
     x = synth.overlapping_rows(int(g["data_seed"]), n, d, int(g["comps"]), float(g["spread"]))
     assert hashlib.sha256(x.tobytes()).hexdigest() == str(g["x_sha256"]), "the rows are not the generator's rows"

@@ -319,3 +319,32 @@ def test_bench_verify_one_gpu():
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert out["config"]["multi_gpu_mode"] is None and out["config"]["global_batch"] == 32
     assert out["verify"]["ranks_agree"] and out["verify"]["oracle_labels_equal"] == [True, True]
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """a plain bench.py run (no --full) times exactly --steps steps, carries none of the --full legs, and --dump-outputs writes
+    the last timed step's labels and selection -- identical for another run with the same arguments"""
+    import json
+    import subprocess
+    import sys
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    rows, outs = 65536, []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "0", "--rows", str(rows),
+               "--dump-outputs", str(tmp_path / run)]
+        r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        outs.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0]))
+    for out in outs:
+        assert out["steps"] == 2 and out["ms_per_step"] > 0 and "cpu_baseline" not in out and "variants" not in out
+        assert abs(out["value"] - rows * 2 / (out["ms_per_step"] * 2e-3)) < 1e-6 * out["value"]
+    lab = np.load(tmp_path / "a" / "labels.npy")
+    sel = np.load(tmp_path / "a" / "selected.npy")
+    assert lab.dtype == np.float32 and lab.shape == (rows, 2) and lab.min() >= 0 and lab.max() < 256
+    assert len(sel) == round(0.2 * rows) and len(np.unique(sel)) == len(sel)
+    # one gain per pick of every iteration (k = 4): S is cut to the subset size, the gains are not (batch.py:258)
+    assert len(np.load(tmp_path / "a" / "gains.npy")) == -(-len(sel) // 4) * 4
+    for name in sorted(os.listdir(tmp_path / "a")):
+        assert np.array_equal(np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)), name

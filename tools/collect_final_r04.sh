@@ -8,10 +8,10 @@ stats() { local tag=$1; shift
     timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt_$tag" -o kt -- "$@" > "$OUT/${P}_${tag}.txt" 2> /dev/null
     cp "$OUT"/kt_$tag/*kernel_stats.csv "$OUT/${P}_${tag}_kernel_stats.csv" 2> /dev/null
     rm -rf "$OUT/kt_$tag"; }
-timeout 900 python bench.py --steps 2 --warmup 1 > "$OUT/${P}_bench_1gpu_s3.json" 2> /dev/null
+timeout 900 python bench.py --full --steps 2 --warmup 1 > "$OUT/${P}_bench_1gpu_s3.json" 2> /dev/null
 stats bench_under_rocprof python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-variants
-timeout 900 python bench.py --workload cfg4 --steps 2 --warmup 1 > "$OUT/${P}_cfg4_slice.json" 2> /dev/null
-timeout 1800 python bench.py --workload cfg5 --steps 1 --warmup 1 > "$OUT/${P}_cfg5_slice.json" 2> /dev/null
+timeout 900 python bench.py --full --workload cfg4 --steps 2 --warmup 1 > "$OUT/${P}_cfg4_slice.json" 2> /dev/null
+timeout 1800 python bench.py --full --workload cfg5 --steps 1 --warmup 1 > "$OUT/${P}_cfg5_slice.json" 2> /dev/null
 stats mi_1m python tools/bench_mi.py 1000000 256 2 0 3000
 ACAV_MI_TIMING=1 timeout 300 python tools/bench_mi.py 1000000 256 2 0 20000 > "$OUT/${P}_mi_1m_steady.txt" 2>&1
 if [ -x tools/exp/fy_bench ]; then (tools/exp/fy_bench 1000000; tools/exp/fy_bench 100000) > "$OUT/${P}_mi_kernels_alone.txt" 2>&1; fi

@@ -15,17 +15,17 @@ pmc() { local tag=$1 re=$2 ctr=$3; shift 3
     timeout 900 rocprofv3 --pmc $ctr --kernel-include-regex "$re" --output-format csv -d "$OUT/pmc_$tag" -o pmc -- "$@" > /dev/null 2>&1
     cp "$OUT"/pmc_$tag/*counter_collection.csv "$OUT/${P}_pmc_${tag}_counter_collection.csv" 2> /dev/null
     rm -rf "$OUT/pmc_$tag"; }
-timeout 900 python bench.py --steps 2 --warmup 1 > "$OUT/${P}_bench_1gpu.json" 2> /dev/null
+timeout 900 python bench.py --full --steps 2 --warmup 1 > "$OUT/${P}_bench_1gpu.json" 2> /dev/null
 stats bench_under_rocprof python bench.py --steps 1 --warmup 0 --no-cpu-baseline
 stats assign_filter python tools/run_assign_only.py 1000000 200 filter
 pmc fetch "k_assign" FETCH_SIZE python tools/run_assign_only.py 1000000 5 filter
 pmc write "k_assign" WRITE_SIZE python tools/run_assign_only.py 1000000 5 filter
 python tools/summarize_pmc.py "$OUT" "$P"
 stats assign_k1024 python tools/run_assign_only.py 1000000 3 filter 1024 1024
-timeout 900 python bench.py --workload cfg4 --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/${P}_cfg4_slice.json" 2> /dev/null
-timeout 1800 python bench.py --workload cfg5 --steps 1 --warmup 1 --no-cpu-baseline > "$OUT/${P}_cfg5_slice.json" 2> /dev/null
-timeout 900 python bench.py --workload real10 --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/${P}_real10_k32.json" 2> /dev/null
-timeout 900 python bench.py --workload real10 --k 256 --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/${P}_real10_k256.json" 2> /dev/null
+timeout 900 python bench.py --full --workload cfg4 --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/${P}_cfg4_slice.json" 2> /dev/null
+timeout 1800 python bench.py --full --workload cfg5 --steps 1 --warmup 1 --no-cpu-baseline > "$OUT/${P}_cfg5_slice.json" 2> /dev/null
+timeout 900 python bench.py --full --workload real10 --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/${P}_real10_k32.json" 2> /dev/null
+timeout 900 python bench.py --full --workload real10 --k 256 --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/${P}_real10_k256.json" 2> /dev/null
 stats mi_1m python tools/bench_mi.py 1000000 256 2 0 3000
 ACAV_MI_TIMING=1 timeout 300 python tools/bench_mi.py 1000000 256 2 0 20000 > "$OUT/${P}_mi_1m_steady.txt" 2>&1
 : > "$OUT/${P}_train_shapes.txt"

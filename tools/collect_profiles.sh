@@ -22,7 +22,7 @@ pmc() {  # pmc <tag> <kernel regex> <counters> <cmd...>
     rm -rf "$OUT/pmc_$tag"
 }
 # 1. the driver's command (one step: 150k greedy launches make the trace large), alone and under the tracer
-timeout 900 python bench.py --steps 2 --warmup 1 > "$OUT/${P}_bench_1gpu.json" 2> /dev/null
+timeout 900 python bench.py --full --steps 2 --warmup 1 > "$OUT/${P}_bench_1gpu.json" 2> /dev/null
 stats bench_under_rocprof python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-variants
 # 2. the assign sweep alone (the kernel of bench.py's `roofline`): stats, HBM traffic, pipe counters; round-1 layout for the A/B
 stats assign_filter python tools/run_assign_only.py 1000000 20 filter
@@ -73,8 +73,8 @@ timeout 600 python tools/recheck_table.py > "$OUT/${P}_recheck_table.txt" 2>&1
 timeout 900 python tools/bench_streamed.py 1000000 1024 256 2.0 > "$OUT/${P}_streamed_now.txt" 2>&1
 # 6. round 4: the 8-GPU configurations' per-GPU slices (bench lines with the K = 1024 roofline against the MFMA roof), the
 #    candidate-restricted re-check (kernel statistics + counters at 62 % undecided rows)
-timeout 900 python bench.py --workload cfg4 --steps 2 --warmup 1 > "$OUT/${P}_cfg4_slice.json" 2> /dev/null
-timeout 1800 python bench.py --workload cfg5 --steps 1 --warmup 1 > "$OUT/${P}_cfg5_slice.json" 2> /dev/null
+timeout 900 python bench.py --full --workload cfg4 --steps 2 --warmup 1 > "$OUT/${P}_cfg4_slice.json" 2> /dev/null
+timeout 1800 python bench.py --full --workload cfg5 --steps 1 --warmup 1 > "$OUT/${P}_cfg5_slice.json" 2> /dev/null
 stats recheck_hard python tools/recheck_table.py 1000000 1024 0.06,0.05
 : > "$OUT/${P}_cand_pmc.txt"
 for C in "TCC_REQ_sum TCC_HIT_sum" "TCC_MISS_sum TCC_EA0_RDREQ_sum" "TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum" "SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_INSTS_VALU SQ_WAVES" "TA_BUSY_avr TCP_PENDING_STALL_CYCLES_sum" "SQ_WAIT_INST_ANY SQ_WAVE_CYCLES"; do
@@ -94,8 +94,8 @@ PY
 done
 # 7. round 5: the real pipeline's shape (ten clusterings, P = 45) as bench lines, ten clusterings alone vs in one call, the driver's
 #    command with --verify, the cfg4 pair and the K = d = 1024 pair side by side
-timeout 900 python bench.py --workload real10 --steps 2 --warmup 1 > "$OUT/${P}_real10_k32.json" 2> /dev/null
-timeout 900 python bench.py --workload real10 --k 256 --steps 2 --warmup 1 > "$OUT/${P}_real10_k256.json" 2> /dev/null
+timeout 900 python bench.py --full --workload real10 --steps 2 --warmup 1 > "$OUT/${P}_real10_k32.json" 2> /dev/null
+timeout 900 python bench.py --full --workload real10 --k 256 --steps 2 --warmup 1 > "$OUT/${P}_real10_k256.json" 2> /dev/null
 (BENCH_K=32 python tools/bench_train_real10.py; BENCH_K=256 python tools/bench_train_real10.py) > "$OUT/${P}_train_real10.txt" 2>&1
 timeout 600 python bench.py --steps 2 --warmup 1 --verify --no-cpu-baseline --no-variants > "$OUT/${P}_bench_verify.json" 2> /dev/null
 (python tools/bench_train_multi.py; BENCH_D=2048 BENCH_D2=128 python tools/bench_train_multi.py; BENCH_K=256 python tools/bench_train_multi.py) > "$OUT/${P}_train_multi.txt" 2>&1
