@@ -119,6 +119,14 @@ __device__ __forceinline__ double canon_exp(double x)
     return ldexp(p, (int)k);
 }
 
+// generalized_mean (mi.py:201-209) of the two entropies: avg 0 = arithmetic (the reference's default), 1 = max, 2 = min
+__device__ __forceinline__ double generalized_mean(double ha, double hb, int avg)
+{
+    if (avg == 1) return ha > hb ? ha : hb;
+    if (avg == 2) return ha < hb ? ha : hb;
+    return (ha + hb) / 2.0;
+}
+
 // EfficientAMI._calc_score (mi.py:212-259) of cache + candidate `id` for pair p: (MI - EMI) / max(mean entropy - EMI, eps)
 // with the reference's one-term-per-cell EMI, over integer counts; every log / log-factorial is a look-up in the host-built
 // tables lnk / lf (the oracle's doubles), the cells are walked row-major: the canonical form of oracle ami_score_canon.
@@ -126,7 +134,7 @@ __device__ double ami_pair_score(const int *__restrict__ asg, int D, int C, int 
                                  const int *__restrict__ Nc, const int *__restrict__ ac, const int *__restrict__ bc,
                                  const double *__restrict__ SN, const double *__restrict__ Sa, const double *__restrict__ Sb,
                                  const double *__restrict__ phi, const double *__restrict__ lnk, const double *__restrict__ lf,
-                                 long long nc)
+                                 long long nc, int avg)
 {
     const int *row = asg + (size_t)id * D;
     const int i = row[pairs[2 * p]], j = row[pairs[2 * p + 1]];
@@ -159,7 +167,7 @@ __device__ double ami_pair_score(const int *__restrict__ asg, int D, int C, int 
         }
     }
     const double ha = ln_n - sa / n1, hb = ln_n - sb / n1;
-    double den = (ha + hb) / 2.0 - emi;
+    double den = generalized_mean(ha, hb, avg) - emi;
     if (den < 2.220446049250313e-16) den = 2.220446049250313e-16;
     return (mi - emi) / den;
 }
@@ -169,7 +177,8 @@ __device__ double ami_pair_score(const int *__restrict__ asg, int D, int C, int 
 __device__ __forceinline__ double nmi_pair_score(const int *__restrict__ asg, int D, int C, int p, const int *__restrict__ pairs, int id,
                                                  const int *__restrict__ Nc, const int *__restrict__ ac, const int *__restrict__ bc,
                                                  const double *__restrict__ SN, const double *__restrict__ Sa, const double *__restrict__ Sb,
-                                                 const double *__restrict__ phi, const double *__restrict__ lnk, long long nc)
+                                                 const double *__restrict__ phi, const double *__restrict__ lnk, long long nc,
+                                                 int avg)
 {
     const int *row = asg + (size_t)id * D;
     const int i = row[pairs[2 * p]], j = row[pairs[2 * p + 1]];
@@ -181,7 +190,8 @@ __device__ __forceinline__ double nmi_pair_score(const int *__restrict__ asg, in
     const double sb = Sb[p] - phi[cb] + phi[cb + 1];
     if ((long long)cN + 1 == n1i) {
         // DEGENERATE (every sample in ONE cell: MI = entropies = 0 over integer counts): the reference returns the ratio of its eps
-        // artefacts, a closed form of C and n -- derivation in oracle/acav_oracle.c nmi_score_canon; the same operations here
+        // artefacts, a closed form of C and n -- derivation in oracle/acav_oracle.c nmi_score_canon; the same operations here.
+        // Both entropy artefacts are equal there, so every average_method gives this value
         const double ln_eps = -36.043653389117154, ln_c = lnk[C];
         const double num = (double)(C - 1) * ((ln_n - ln_eps) - 2.0 * ln_c) - 2.0 * ln_c;
         const double dd = (double)C * ((ln_n - ln_c) - ln_eps);
@@ -189,10 +199,92 @@ __device__ __forceinline__ double nmi_pair_score(const int *__restrict__ asg, in
     }
     const double mi = (((sN - sa) - sb) + phi[n1i]) / n1;
     const double ha = ln_n - sa / n1, hb = ln_n - sb / n1;
-    double den = (ha + hb) / 2.0;
+    double den = generalized_mean(ha, hb, avg);
     if (den < 2.220446049250313e-16) den = 2.220446049250313e-16;  // ensure_nonzero (mi.py:194-199)
     return (2.0 * mi) / den;
 }
+
+// ------------------------------------------------------------------ pair-counting scores (fm / rand / arand)
+// correspondence_retrieval/code/measures/efficient_pair.py: FowlkesMallowsScore, RandScore, AdjustedRandScore.  Per pair p the
+// handle keeps T_ab = sum C(N,2), T_a = sum C(a,2), T_b = sum C(b,2) of the current tables, from which TP = T_ab,
+// FP = T_a - T_ab, FN = T_b - T_ab, TN = C(n,2) - T_a - T_b + T_ab.  The reference's fp32 tables start at float64 eps: a zero
+// cell of N holds eps, a zero marginal C eps, and those residues survive in its running TP / FP / FN while their integer
+// part is 0.  Each such quantity is carried as (integer I, residue count R), valued I if I > 0 and R eps otherwise; a sum or
+// difference drops R as soon as either integer part is at least 1 (what fp32 does to 1 + R eps).  rtp / rfp / rfn are
+// the residue counts of the running TP / FP / FN (0 once the integer part is >= 1); TN never carries one while n >= 1.
+struct PairStat {
+    long long tab, ta, tb;
+    long long rtp, rfp, rfn;
+};
+
+// one workgroup per pair: T_ab / T_a / T_b from the tables, residues 0 (init_pair_stats, efficient_pair.py:33-46: scipy's
+// comb(..., exact=False).round() of the eps-valued cells is 0)
+__global__ __launch_bounds__(256) void k_pair_stats_init(int C, const int *__restrict__ Nc, const int *__restrict__ ac,
+                                                         const int *__restrict__ bc, PairStat *__restrict__ ps)
+{
+    __shared__ long long red[3][256];
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const int *Np = Nc + (size_t)p * C * C, *ap = ac + (size_t)p * C, *bp = bc + (size_t)p * C;
+    long long tab = 0, ta = 0, tb = 0;
+    for (int q = tid; q < C * C; q += 256) {
+        const long long v = Np[q];
+        tab += v * (v - 1) / 2;
+    }
+    for (int q = tid; q < C; q += 256) {
+        const long long va = ap[q], vb = bp[q];
+        ta += va * (va - 1) / 2;
+        tb += vb * (vb - 1) / 2;
+    }
+    red[0][tid] = tab, red[1][tid] = ta, red[2][tid] = tb;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (tid < h) red[0][tid] += red[0][tid + h], red[1][tid] += red[1][tid + h], red[2][tid] += red[2][tid + h];
+        __syncthreads();
+    }
+    if (tid == 0) ps[p] = PairStat{red[0][0], red[1][0], red[2][0], 0, 0, 0};
+}
+
+constexpr double PAIR_EPS = 2.220446049250313e-16;  // float64 eps = 2^-52, the reference's table initialisation
+
+__device__ __forceinline__ double pair_value(long long I, long long R)
+{
+    return I > 0 ? (double)I : (double)R * PAIR_EPS;
+}
+
+// score of cache + candidate `id` for pair p.  measure 4 = FM, 5 = Rand (on cache TP/FP/FN/TN + the candidate's deltas
+// dTP = N_ij, dFP = a_j - N_ij, dFN = b_i - N_ij, dTN = n - a_j - b_i + N_ij, efficient_pair.py:53-72), 6 = ARI (on
+// last = cache + candidate, efficient_pair.py:121-135; a function of the integer counts only, 0/0 = NaN while the
+// selection is degenerate).  Every operation is +, -, *, / or sqrt of IEEE doubles (the test restatement repeats them).
+__device__ __forceinline__ double pair_count_score(const int *__restrict__ asg, int D, int C, int p, const int *__restrict__ pairs,
+                                                   int id, const int *__restrict__ Nc, const int *__restrict__ ac,
+                                                   const int *__restrict__ bc, const PairStat *__restrict__ ps, long long n,
+                                                   int measure)
+{
+    const int *row = asg + (size_t)id * D;
+    const int i = row[pairs[2 * p]], j = row[pairs[2 * p + 1]];
+    const long long cN = Nc[((size_t)p * C + i) * C + j], ca = ac[(size_t)p * C + j], cb = bc[(size_t)p * C + i];
+    const PairStat st = ps[p];
+    if (measure == 6) {
+        const double Nc2 = (double)(st.tab + cN), ac2 = (double)(st.ta + ca), bc2 = (double)(st.tb + cb);
+        const double nc2 = (double)(n * (n + 1) / 2);
+        const double chance = (ac2 * bc2) / nc2;
+        return (Nc2 - chance) / (0.5 * (ac2 + bc2) - chance);
+    }
+    const long long tpI = st.tab + cN, fpI = (st.ta - st.tab) + (ca - cN), fnI = (st.tb - st.tab) + (cb - cN);
+    const long long tnI = ((n * (n - 1) / 2 - st.ta) - st.tb + st.tab) + (((n - ca) - cb) + cN);
+    const long long tpR = tpI ? 0 : st.rtp + 1;
+    const long long fpR = fpI ? 0 : st.rfp + (ca == 0 ? C - 1 : 0);
+    const long long fnR = fnI ? 0 : st.rfn + (cb == 0 ? C - 1 : 0);
+    const double tp = pair_value(tpI, tpR);
+    if (measure == 4) {
+        const double tpfp = pair_value(tpI + fpI, tpR + fpR), tpfn = pair_value(tpI + fnI, tpR + fnR);
+        return sqrt((tp / tpfp) * (tp / tpfn));
+    }
+    // Rand: TP + TN only -- every pair shares the denominator C(n+1, 2), so k_mi_exact_iter divides the sum over the pairs
+    // by P C(n+1, 2) once (its pair_mean): candidates whose Rand indices are equal tie exactly, as they do in the reference's fp32
+    return pair_value(tpI + tnI, tpR);
+}
+
 
 constexpr int SEL_MAXB = 64;
 constexpr int SEL_MAXBP = 8192;
@@ -498,11 +590,22 @@ struct ExactBest {
     int pos;
     int pad;
 };
+// candidate (so, po) beats (s, p): score descending, position ascending.  PAIR (the pair-counting scores): NaN ranks above
+// every number and the lowest position wins among NaNs -- torch's max(dim=0) returns the first NaN (the arand score is 0/0
+// while the selection is degenerate); the other measures never produce NaN and keep the plain order
+template <bool PAIR>
 __device__ __forceinline__ bool exact_better(double s, int p, double so, int po)
 {
-    return so > s || (so == s && po < p);  // candidate (so, po) beats (s, p)
+    if constexpr (PAIR) {
+        const bool sn = s != s, on = so != so;
+        if (on || sn) return on && (!sn || po < p);
+    }
+    return so > s || (so == s && po < p);
 }
 
+// PAIR: the pair-counting scores (measures 4-6) in an instantiation of their own, so that the code of measures 0-3 is what
+// it was before they existed
+template <bool PAIR>
 __global__ __launch_bounds__(256) void k_mi_exact_iter(
     const int *__restrict__ asg, int D, int C, int P, const int *__restrict__ pairs, const int *__restrict__ A, int L,
     unsigned char *__restrict__ removed, int *__restrict__ Nc, int *__restrict__ ac, int *__restrict__ bc,
@@ -510,15 +613,25 @@ __global__ __launch_bounds__(256) void k_mi_exact_iter(
     MiScalars *__restrict__ sc, ExactBest *__restrict__ blockbest, unsigned *__restrict__ ticket,
     long long *__restrict__ S_out, double *__restrict__ G_out, const int *__restrict__ forced,
     double *__restrict__ trace_scores, int *__restrict__ trace_argmax, int measure, const double *__restrict__ lnk,
-    const double *__restrict__ lf)
+    const double *__restrict__ lf, int avg, PairStat *__restrict__ ps)
 {
     // measure 0: calc_MI ('mi' / 'mem_mi'); 1: calc_AMI ('ami'); 2: calc_NMI (mi.py:262-271); 3: ConstantMeasure (mi.py:274-281:
-    // every candidate scores 1, the first remaining one is taken)
+    // every candidate scores 1, the first remaining one is taken); 4 / 5 / 6: Fowlkes-Mallows / Rand / adjusted Rand
+    // (efficient_pair.py; ps holds their per-pair sums).  avg: average_method of 1 and 2
     auto pair_score = [&](int p, int id, long long n) -> double {
-        if (measure == 1) return ami_pair_score(asg, D, C, p, pairs, id, Nc, ac, bc, SN, Sa, Sb, phi, lnk, lf, n);
-        if (measure == 2) return nmi_pair_score(asg, D, C, p, pairs, id, Nc, ac, bc, SN, Sa, Sb, phi, lnk, n);
-        if (measure == 3) return 1.0;
-        return mi_pair_score(asg, D, C, p, pairs, id, Nc, ac, bc, SN, Sa, Sb, phi, n);
+        if constexpr (PAIR) {
+            return pair_count_score(asg, D, C, p, pairs, id, Nc, ac, bc, ps, n, measure);
+        } else {
+            if (measure == 1) return ami_pair_score(asg, D, C, p, pairs, id, Nc, ac, bc, SN, Sa, Sb, phi, lnk, lf, n, avg);
+            if (measure == 2) return nmi_pair_score(asg, D, C, p, pairs, id, Nc, ac, bc, SN, Sa, Sb, phi, lnk, n, avg);
+            if (measure == 3) return 1.0;
+            return mi_pair_score(asg, D, C, p, pairs, id, Nc, ac, bc, SN, Sa, Sb, phi, n);
+        }
+    };
+    auto pair_mean = [&](double tot, long long n) -> double {  // scores.mean(-1); Rand's shared denominator joins the division
+        if constexpr (PAIR)
+            if (measure == 5) return tot / ((double)P * (double)(n * (n + 1) / 2));
+        return tot / (double)P;
     };
     __shared__ double sS[4];
     __shared__ int sP[4];
@@ -532,7 +645,7 @@ __global__ __launch_bounds__(256) void k_mi_exact_iter(
         const int id = A[w];
         double tot = 0.0;
         for (int p = 0; p < P; ++p) tot = tot + pair_score(p, id, nc);
-        s = tot / (double)P;
+        s = pair_mean(tot, nc);
         pos = w;
     }
     if (trace_scores && w < L) trace_scores[w] = pos == w ? s : (double)NAN;
@@ -540,13 +653,13 @@ __global__ __launch_bounds__(256) void k_mi_exact_iter(
     for (int dlt = 1; dlt < 64; dlt <<= 1) {
         const double so = __shfl_xor(s, dlt);
         const int po = __shfl_xor(pos, dlt);
-        if (exact_better(s, pos, so, po)) s = so, pos = po;
+        if (exact_better<PAIR>(s, pos, so, po)) s = so, pos = po;
     }
     if (lane == 0) sS[wave] = s, sP[wave] = pos;
     __syncthreads();
     if (tid == 0) {
         for (int q = 1; q < 4; ++q)
-            if (exact_better(s, pos, sS[q], sP[q])) s = sS[q], pos = sP[q];
+            if (exact_better<PAIR>(s, pos, sS[q], sP[q])) s = sS[q], pos = sP[q];
         blockbest[blockIdx.x].s = s;
         blockbest[blockIdx.x].pos = pos;
         __threadfence();  // the result is visible device-wide before the ticket is taken
@@ -560,25 +673,25 @@ __global__ __launch_bounds__(256) void k_mi_exact_iter(
     for (int q = tid; q < (int)gridDim.x; q += 256) {
         const double so = __hip_atomic_load(&blockbest[q].s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const int po = __hip_atomic_load(&blockbest[q].pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (exact_better(s, pos, so, po)) s = so, pos = po;
+        if (exact_better<PAIR>(s, pos, so, po)) s = so, pos = po;
     }
 #pragma unroll
     for (int dlt = 1; dlt < 64; dlt <<= 1) {
         const double so = __shfl_xor(s, dlt);
         const int po = __shfl_xor(pos, dlt);
-        if (exact_better(s, pos, so, po)) s = so, pos = po;
+        if (exact_better<PAIR>(s, pos, so, po)) s = so, pos = po;
     }
     if (lane == 0) sS[wave] = s, sP[wave] = pos;
     __syncthreads();
     if (tid == 0) {
         for (int q = 1; q < 4; ++q)
-            if (exact_better(s, pos, sS[q], sP[q])) s = sS[q], pos = sP[q];
+            if (exact_better<PAIR>(s, pos, sS[q], sP[q])) s = sS[q], pos = sP[q];
         if (trace_argmax) *trace_argmax = pos;
         if (forced) {
             pos = *forced;
             double tot = 0.0;
             for (int p = 0; p < P; ++p) tot = tot + pair_score(p, A[pos], nc);
-            s = tot / (double)P;
+            s = pair_mean(tot, nc);
         }
         sP[0] = pos;
         *S_out = (long long)A[pos];
@@ -594,12 +707,21 @@ __global__ __launch_bounds__(256) void k_mi_exact_iter(
         const int i = row[pairs[2 * p]], j = row[pairs[2 * p + 1]];
         const size_t cell = ((size_t)p * C + i) * C + j;
         const int cN = Nc[cell], ca = ac[(size_t)p * C + j], cb = bc[(size_t)p * C + i];
+        PairStat st{};
+        if constexpr (PAIR) st = ps[p];  // loaded beside the counts: the commit is on the critical path of every pick
         Nc[cell] = cN + 1;
         ac[(size_t)p * C + j] = ca + 1;
         bc[(size_t)p * C + i] = cb + 1;
         SN[p] = SN[p] - phi[cN] + phi[cN + 1];
         Sa[p] = Sa[p] - phi[ca] + phi[ca + 1];
         Sb[p] = Sb[p] - phi[cb] + phi[cb + 1];
+        if constexpr (PAIR) {  // the running pair sums (update_cache, efficient_pair.py:74-81: cache += the pick's deltas)
+            st.tab += cN, st.ta += ca, st.tb += cb;
+            st.rtp = st.tab ? 0 : st.rtp + 1;
+            st.rfp = st.ta - st.tab ? 0 : st.rfp + (ca == 0 ? C - 1 : 0);
+            st.rfn = st.tb - st.tab ? 0 : st.rfn + (cb == 0 ? C - 1 : 0);
+            ps[p] = st;
+        }
     }
 }
 
@@ -1387,7 +1509,11 @@ struct acav_mi {
     DevBuf chunk_desc;                         // descriptor array of a multi-chunk run (lead handle)
     DevBuf lane_states, ring, polys;           // MT19937 lanes of the single-chunk greedy (MtStream)
     DevBuf lnk, lf;   // ln k and ln k! tables of the `ami` score (acav_mi_set_measure)
-    int measure = 0;  // exact greedy: 0 = calc_MI, 1 = calc_AMI, 2 = calc_NMI, 3 = constant
+    int measure = 0;  // exact greedy: 0 = calc_MI, 1 = calc_AMI, 2 = calc_NMI, 3 = constant, 4 = FM, 5 = Rand, 6 = ARI
+    int avg = 0;      // average_method of 1 and 2: 0 = arithmetic, 1 = max, 2 = min (acav_mi_set_average_method)
+    DevBuf pst;       // PairStat [P] of the pair-counting scores (derived from the tables by k_pair_stats_init)
+    bool pst_valid = false;  // pst matches the tables: only the exact greedy with a pair-counting score keeps it up to date;
+                             // anything else that changes the tables (add_samples = init_pair_stats) re-derives it, residues 0
     int queue_probe_replaced = 0;  // streams replaced by mi_separate_queues (diagnostics: ACAV_MI_TIMING prints it)
     bool lockstep_member = false;  // ran as one of several chunks of acav_mi_run_greedy_multi: its streams / events are RETIRED at destroy
     bool queue_probe_pending = false;  // the three streams have not been checked for a shared hardware queue yet
@@ -2136,6 +2262,8 @@ ACAV_EXPORT int acav_mi_run_greedy_multi(acav_mi **mis, int nchunks, const int64
                  k);
     acav_mi *lead = mis[0];
     ACAV_REQUIRE(lead, ACAV_EINVAL, "handle is NULL");
+    for (int c = 0; c < nchunks; ++c)
+        if (mis[c]) mis[c]->pst_valid = false;  // the batch greedy changes the tables without the pair sums
     ACAV_HIP_TRY(hipSetDevice(lead->ctx.device));
     {   // validation common to both evaluations, then the tiled one unless a list is too long for it (or ACAV_FY_LEGACY=1)
         const char *legacy = getenv("ACAV_FY_LEGACY");
@@ -2282,12 +2410,13 @@ ACAV_EXPORT int acav_mi_run_greedy_multi(acav_mi **mis, int nchunks, const int64
 }
 
 // which score the exact greedy (acav_mi_run_exact) maximises: 0 = calc_MI ('mi', 'mem_mi'; mi.py:85-91), 1 = calc_AMI ('ami',
-// mi.py:212-259), 2 = calc_NMI (EfficientNMI, mi.py:262-271), 3 = ConstantMeasure (mi.py:274-281).  The adjusted and normalised
-// scores read two more host-built tables, ln k and ln k! for k <= V + 1.
+// mi.py:212-259), 2 = calc_NMI (EfficientNMI, mi.py:262-271), 3 = ConstantMeasure (mi.py:274-281), 4 / 5 / 6 = Fowlkes-Mallows /
+// Rand / adjusted Rand (correspondence_retrieval efficient_pair.py).  The adjusted and normalised scores read two more host-built
+// tables, ln k and ln k! for k <= V + 1.
 ACAV_EXPORT int acav_mi_set_measure(acav_mi *mi, int measure)
 {
     ACAV_REQUIRE(mi, ACAV_EINVAL, "handle is NULL");
-    ACAV_REQUIRE(measure >= 0 && measure <= 3, ACAV_EINVAL, "unknown measure %d", measure);
+    ACAV_REQUIRE(measure >= 0 && measure <= 6, ACAV_EINVAL, "unknown measure %d", measure);
     ACAV_REQUIRE(measure != 2 || (int64_t)mi->C <= mi->V + 1, ACAV_EINVAL, "nmi: ncentroids %d exceeds the ln k table (V + 1 = %lld)",
                  mi->C, (long long)(mi->V + 1));
     if ((measure == 1 || measure == 2) && !mi->lnk.p) {
@@ -2302,6 +2431,52 @@ ACAV_EXPORT int acav_mi_set_measure(acav_mi *mi, int measure)
         ACAV_HIP_TRY(hipStreamSynchronize(mi->ctx.stream));  // the vectors are locals
     }
     mi->measure = measure;
+    return ACAV_OK;
+}
+
+// generalized_mean (mi.py:201-209) of the ami / nmi scores: 0 = arithmetic (default), 1 = max, 2 = min
+ACAV_EXPORT int acav_mi_set_average_method(acav_mi *mi, int method)
+{
+    ACAV_REQUIRE(mi, ACAV_EINVAL, "handle is NULL");
+    ACAV_REQUIRE(method >= 0 && method <= 2, ACAV_EINVAL, "unknown average_method %d (0 arithmetic, 1 max, 2 min)", method);
+    mi->avg = method;
+    return ACAV_OK;
+}
+
+// T_ab / T_a / T_b of the current tables into mi->pst, residues 0 (on the handle's stream), unless pst is still current: the
+// reference resets its residues only in add_samples, so consecutive exact-greedy calls carry them on
+static int pair_stats_init(acav_mi *mi)
+{
+    if (mi->pst_valid) return ACAV_OK;
+    ACAV_TRY(mi->pst.ensure(sizeof(PairStat) * (size_t)mi->P));
+    hipLaunchKernelGGL(k_pair_stats_init, dim3(mi->P), dim3(256), 0, mi->ctx.stream, mi->C, mi->Nc.as<int>(), mi->ac.as<int>(),
+                       mi->bc.as<int>(), mi->pst.as<PairStat>());
+    ACAV_HIP_TRY(hipGetLastError());
+    mi->pst_valid = true;
+    return ACAV_OK;
+}
+
+// pair counts of the current tables (sklearn's pair_confusion_matrix / 2, per pair): TP = T_ab, FP = T_a - T_ab,
+// FN = T_b - T_ab, TN = C(n,2) - T_a - T_b + T_ab; TP + FP + FN + TN = n (n - 1) / 2 exactly
+ACAV_EXPORT int acav_mi_get_pair_stats(acav_mi *mi, int64_t *TP, int64_t *FP, int64_t *FN, int64_t *TN)
+{
+    ACAV_REQUIRE(mi, ACAV_EINVAL, "handle is NULL");
+    ACAV_HIP_TRY(hipSetDevice(mi->ctx.device));
+    hipStream_t st = mi->ctx.stream;
+    ACAV_TRY(pair_stats_init(mi));
+    std::vector<PairStat> ps((size_t)mi->P);
+    ACAV_HIP_TRY(hipMemcpyAsync(ps.data(), mi->pst.p, sizeof(PairStat) * ps.size(), hipMemcpyDeviceToHost, st));
+    MiScalars s{};
+    ACAV_HIP_TRY(hipMemcpyAsync(&s, mi->scalars.p, sizeof(s), hipMemcpyDeviceToHost, st));
+    ACAV_HIP_TRY(hipStreamSynchronize(st));
+    const long long n2 = s.nc * (s.nc - 1) / 2;
+    for (int p = 0; p < mi->P; ++p) {
+        const PairStat &q = ps[(size_t)p];
+        if (TP) TP[p] = q.tab;
+        if (FP) FP[p] = q.ta - q.tab;
+        if (FN) FN[p] = q.tb - q.tab;
+        if (TN) TN[p] = ((n2 - q.ta) - q.tb) + q.tab;
+    }
     return ACAV_OK;
 }
 
@@ -2343,15 +2518,28 @@ ACAV_EXPORT int acav_mi_run_exact(acav_mi *mi, const int64_t *candidates, int64_
     }
     if (trace_scores) ACAV_TRY(mi->tr_sc.ensure(sizeof(double) * (size_t)iters * (size_t)L));
     if (trace_argmax) ACAV_TRY(mi->tr_am.ensure(sizeof(int) * (size_t)iters));
+    if (mi->measure < 4) mi->pst_valid = false;  // the commits below do not maintain pst
+    if (mi->measure >= 4) {  // the pair-counting scores: their sums start from the tables as they are (init_pair_stats)
+        if (mi->measure != 6) {
+            MiScalars s{};
+            ACAV_HIP_TRY(hipMemcpyAsync(&s, mi->scalars.p, sizeof(s), hipMemcpyDeviceToHost, st));
+            ACAV_HIP_TRY(hipStreamSynchronize(st));
+            ACAV_REQUIRE(s.nc >= 1, ACAV_EINVAL, "fm / rand: the tables hold no sample -- add the start clips first "
+                         "(the reference's pair-count check fails on an empty start)");
+        }
+        ACAV_TRY(pair_stats_init(mi));
+    }
+    const bool pair = mi->measure >= 4;
     for (int64_t it = 0; it < iters; ++it) {
-        hipLaunchKernelGGL(k_mi_exact_iter, dim3(grid), dim3(256), 0, st, mi->asg.as<int>(), mi->D, mi->C, mi->P,
+        hipLaunchKernelGGL(pair ? k_mi_exact_iter<true> : k_mi_exact_iter<false>, dim3(grid), dim3(256), 0, st, mi->asg.as<int>(), mi->D, mi->C, mi->P,
                            mi->pairs.as<int>(), mi->A0.as<int>(), (int)L, mi->removed.as<unsigned char>(), mi->Nc.as<int>(),
                            mi->ac.as<int>(), mi->bc.as<int>(), mi->SN.as<double>(), mi->Sa.as<double>(), mi->Sb.as<double>(),
                            mi->phi.as<double>(), mi->scalars.as<MiScalars>(), mi->blockbest.as<ExactBest>(),
                            mi->ticket.as<unsigned>(), mi->S.as<long long>() + it, mi->G.as<double>() + it,
                            forced_pos ? mi->forced.as<int>() + it : nullptr,
                            trace_scores ? mi->tr_sc.as<double>() + (size_t)it * (size_t)L : nullptr,
-                           trace_argmax ? mi->tr_am.as<int>() + it : nullptr, mi->measure, mi->lnk.as<double>(), mi->lf.as<double>());
+                           trace_argmax ? mi->tr_am.as<int>() + it : nullptr, mi->measure, mi->lnk.as<double>(), mi->lf.as<double>(),
+                           mi->avg, mi->pst.as<PairStat>());
     }
     ACAV_HIP_TRY(hipGetLastError());
     ACAV_HIP_TRY(hipMemcpyAsync(S_out, mi->S.p, sizeof(long long) * (size_t)iters, hipMemcpyDeviceToHost, st));
@@ -2390,6 +2578,7 @@ ACAV_EXPORT int acav_mi_timer_end(acav_mi *mi, float *ms)
 ACAV_EXPORT int acav_mi_add_samples(acav_mi *mi, const int64_t *ids, int64_t n)
 {
     ACAV_REQUIRE(mi && (ids || n == 0) && n >= 0 && n < 0x7fffffff, ACAV_EINVAL, "bad argument");
+    mi->pst_valid = false;  // init_pair_stats after add_samples (efficient_pair.py:29-31)
     if (n == 0) return ACAV_OK;
     ACAV_HIP_TRY(hipSetDevice(mi->ctx.device));
     ACAV_TRY(ids_to_device32(mi, ids, n, mi->stage, mi->ids32));
@@ -2458,6 +2647,7 @@ ACAV_EXPORT int acav_mi_run_greedy(acav_mi *mi, const int64_t *candidates, int64
                                    const int32_t *forced_pos, int64_t max_iters)
 {
     ACAV_REQUIRE(mi && candidates && rng && S_out && GAIN_out, ACAV_EINVAL, "NULL argument");
+    mi->pst_valid = false;  // the batch greedy changes the tables without the pair sums
     ACAV_REQUIRE(L > 0 && L <= mi->V && ns >= 0 && (start || ns == 0) && subset >= 0, ACAV_EINVAL, "bad sizes");
     ACAV_REQUIRE(B > 0 && B <= SEL_MAXB && k > 0 && k <= B && (int64_t)B * mi->P <= SEL_MAXBP, ACAV_EINVAL,
                  "batch_size %d / selection_size %d / pairs %d outside the supported range (B<=%d, B*P<=%d)", B, k,

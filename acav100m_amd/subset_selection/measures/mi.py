@@ -79,27 +79,38 @@ class EfficientMemMI(EfficientMI):
     """mi.py:284-412: the memory-lean formulation of the same greedy; identical here."""
 
 
+# generalized_mean (mi.py:201-209): the normaliser of the two entropies -> acav_mi_set_average_method
+AVERAGE_METHODS = {'arithmetic': 0, 'max': 1, 'min': 2}
+
+
 class EfficientAMI(EfficientMI):
     """adjusted MI (mi.py:212-259; 'ami' in measures/__init__.py:5-14): the exact greedy on
-    (MI - EMI) / max(mean entropy - EMI, eps), EMI being the reference's own one-term-per-cell expression (calc_EMI).
+    (MI - EMI) / max(normaliser - EMI, eps), EMI being the reference's own one-term-per-cell expression (calc_EMI).
     Same kernel as `mi` with the adjusted score (acav_mi_set_measure); float64 over integer counts, within 4e-7 relative of
-    the reference's fp32 scores (tests/golden/mi_ami_*.npz).  average_method: 'arithmetic' (the reference default) only."""
+    the reference's fp32 scores (tests/golden/mi_ami_*.npz).  average_method (generalized_mean, mi.py:201-209): the
+    normaliser is the 'arithmetic' mean (the reference default), the 'max' or the 'min' of the two entropies."""
+    _measure_id = 1
+
+    def __init__(self, assignments, measure_type='mutual_info', average_method='arithmetic', ncentroids=20,
+                 device='cuda', **kwargs):
+        method = str(average_method).lower()
+        if method not in AVERAGE_METHODS:
+            raise ValueError("average_method must be one of {}, got {!r}".format(sorted(AVERAGE_METHODS), average_method))
+        super().__init__(assignments, measure_type=measure_type, average_method=method, ncentroids=ncentroids,
+                         device=device, **kwargs)
 
     def init(self, clustering_combinations, candidates):
-        assert self.average_method == 'arithmetic', "ami: only the reference's default average_method is built"
-        super().init(clustering_combinations, candidates)
-        _lib.check(_lib._lib.acav_mi_set_measure(self._h, 1))
+        EfficientMI.init(self, clustering_combinations, candidates)
+        _lib.check(_lib._lib.acav_mi_set_measure(self._h, self._measure_id))
+        _lib.check(_lib._lib.acav_mi_set_average_method(self._h, AVERAGE_METHODS[self.average_method]))
 
 
 class EfficientNMI(EfficientAMI):
-    """normalised MI (mi.py:262-271): the exact greedy on 2 MI / max(mean entropy, eps).  The reference defines the class but
+    """normalised MI (mi.py:262-271): the exact greedy on 2 MI / max(normaliser, eps).  The reference defines the class but
     its registry (measures/__init__.py:5-14) does not name it; here it is reachable as 'nmi'.  Same kernel, score 2
-    (acav_mi_set_measure); float64 over integer counts, pinned on the reference class's own run (tests/golden/mi_nmi_*.npz)."""
-
-    def init(self, clustering_combinations, candidates):
-        assert self.average_method == 'arithmetic', "nmi: only the reference's default average_method is built"
-        EfficientMI.init(self, clustering_combinations, candidates)
-        _lib.check(_lib._lib.acav_mi_set_measure(self._h, 2))
+    (acav_mi_set_measure); float64 over integer counts, pinned on the reference class's own run (tests/golden/mi_nmi_*.npz).
+    average_method as for EfficientAMI."""
+    _measure_id = 2
 
 
 class ConstantMeasure(EfficientMI):
