@@ -1033,6 +1033,15 @@ constexpr int FY_NBUF = FY_DEPTH * FY_GROUP;  // of the gathers (a cross-stream 
 constexpr int GS_EPT = 4;          // outputs per thread of the gather
 constexpr int FY_SHARDS = 8;       // sub-buckets per tile (capg entries each), filled by workgroups b with b % 8 == shard
 constexpr int FYT_THREADS = ACAV_FYT_THREADS;  // k_fy_tile: the list walks are chains of dependent LDS reads -- many waves hide them
+// Bucket entries in 4 bytes instead of an int2 (step, target) -- half of the bucket stream that k_fy_part writes and k_fy_tile reads
+// back (8 of the 16 MB per iteration at L = 10^6).  A part workgroup bx appends to shard bx & 7 only, so the entry only needs
+//   [31:26] bx >> 3   [25:13] step - bx * FYA_CH   [12:0] target - q_lo (the tile-local position: tiles are at most 8192 wide)
+// which holds for lists of at most 512 part workgroups; longer lists (and ACAV_FY_PACK=0) keep the int2 form.
+constexpr int64_t FY_PACK_MAX = FYA_CH <= 8192 ? (int64_t)512 * FYA_CH : 0;
+__device__ __forceinline__ unsigned fy_pack(int bx, int off, int p)
+{
+    return ((unsigned)(bx >> 3) << 26) | ((unsigned)off << 13) | (unsigned)p;
+}
 
 // exclusive prefix sums of cnt[0 .. n) into pre[0 .. n) (both in LDS, distinct), by all threads of the workgroup (a multiple of
 // 64, at most 1024); wsum: 16 ints of LDS; returns the total.  Ends with a barrier.
@@ -1073,18 +1082,21 @@ __device__ __forceinline__ int block_excl_scan(const int *cnt, int *pre, int n, 
 
 // STAGED: the workgroup's appends are first sorted by tile in LDS and leave as runs of consecutive slots per tile (adjacent
 // lanes -> adjacent addresses: a few L2 requests per wave store instead of one per lane)
-template <bool STAGED>
+// PACK: 4-byte entries (fy_pack) into `bucket` seen as unsigned[NT][FY_SHARDS][capg]; needs shard == bx & 7 and the tile bounds
+template <bool STAGED, bool PACK>
 __device__ __forceinline__ void fy_part_body(const unsigned *__restrict__ draws, int L, const unsigned short *__restrict__ table,
                                              int ntab, int gsh, int NT, int capg, int2 *__restrict__ bucket,
                                              int *__restrict__ gcount, unsigned *__restrict__ src, unsigned *__restrict__ err,
-                                             int bx, int shard)
+                                             int bx, int shard, const int *__restrict__ ebound)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char fy_smem[];
     int *lhist = reinterpret_cast<int *>(fy_smem), *lbase = lhist + NT;
     int2 *stage = reinterpret_cast<int2 *>(lbase + NT);                    // [FYA_CH] (STAGED)
     int *lpre = reinterpret_cast<int *>(stage + (STAGED ? FYA_CH : 0));    // [NT] (STAGED)
     int *wsum = lpre + (STAGED ? NT : 0);                                  // [16] (STAGED)
-    unsigned short *ltab = reinterpret_cast<unsigned short *>(wsum + (STAGED ? 16 : 0));  // the tile table, a few KB: LDS lookups
+    int *lehi = wsum + (STAGED ? 16 : 0);                                  // [NT] (PACK) upper e bound of the tile
+    unsigned short *ltab = reinterpret_cast<unsigned short *>(lehi + (PACK ? NT : 0));  // the tile table, a few KB: LDS lookups
+    unsigned *bucket4 = reinterpret_cast<unsigned *>(bucket);
     const int tid = threadIdx.x;
     constexpr int PER = FYA_CH / FYA_THREADS;
     const int base = bx * FYA_CH;
@@ -1096,6 +1108,8 @@ __device__ __forceinline__ void fy_part_body(const unsigned *__restrict__ draws,
     }
     for (int t = tid; t < NT; t += FYA_THREADS) lhist[t] = 0;
     for (int t = tid; t < ntab; t += FYA_THREADS) ltab[t] = table[t];
+    if constexpr (PACK)
+        for (int t = tid; t < NT; t += FYA_THREADS) lehi[t] = ebound[t + 1];
     __syncthreads();
     int hh[PER], tr[PER];
 #pragma unroll
@@ -1133,9 +1147,12 @@ __device__ __forceinline__ void fy_part_body(const unsigned *__restrict__ draws,
         for (int x = tid; x < total; x += FYA_THREADS) {
             const int2 e = stage[x];
             const int tile = ltab[(L - 1 - e.y) >> gsh], pos = lbase[tile] + (x - lpre[tile]);
-            if (pos < capg)
-                FY_ST_BUCKET(&bucket[((size_t)tile * FY_SHARDS + shard) * capg + pos], e);
-            else
+            if (pos < capg) {
+                if constexpr (PACK)  // the target relative to q_lo = L - e_hi of its tile
+                    bucket4[((size_t)tile * FY_SHARDS + shard) * capg + pos] = fy_pack(bx, e.x - base, e.y - (L - lehi[tile]));
+                else
+                    FY_ST_BUCKET(&bucket[((size_t)tile * FY_SHARDS + shard) * capg + pos], e);
+            } else
                 atomicOr(err, 1u);
         }
         return;
@@ -1149,14 +1166,19 @@ __device__ __forceinline__ void fy_part_body(const unsigned *__restrict__ draws,
             if (pos < capg)
                 FY_ST_BUCKET(&bucket[(size_t)base + u * FYA_THREADS + tid], make_int2(base + u * FYA_THREADS + tid, hh[u]));
 #else
-            if (pos < capg)
-                FY_ST_BUCKET(&bucket[((size_t)tile * FY_SHARDS + shard) * capg + pos], make_int2(base + u * FYA_THREADS + tid, hh[u]));
+            if (pos < capg) {
+                if constexpr (PACK)
+                    bucket4[((size_t)tile * FY_SHARDS + shard) * capg + pos] = fy_pack(bx, u * FYA_THREADS + tid, hh[u] - (L - lehi[tile]));
+                else
+                    FY_ST_BUCKET(&bucket[((size_t)tile * FY_SHARDS + shard) * capg + pos], make_int2(base + u * FYA_THREADS + tid, hh[u]));
+            }
 #endif
             else
                 atomicOr(err, 1u);
         }
 }
 
+template <bool PACK>
 __device__ __forceinline__ void fy_tile_body(int L, const int *__restrict__ ebound, int capg, int ecap, int wcap,
                                              const int2 *__restrict__ bucket, int *__restrict__ gcount, unsigned *__restrict__ src,
                                              int *__restrict__ g, unsigned *__restrict__ err, int tile)
@@ -1189,6 +1211,7 @@ __device__ __forceinline__ void fy_tile_body(int L, const int *__restrict__ ebou
     FY_CLK(0);
     const int count = soff[FY_SHARDS];
     const int2 *bk = bucket + (size_t)tile * FY_SHARDS * capg;
+    const unsigned *bk4 = reinterpret_cast<const unsigned *>(bucket) + (size_t)tile * FY_SHARDS * capg;  // (PACK)
     const int nsub = count <= ecap ? 1 : (count + (ecap >> 2) - 1) / (ecap >> 2);
     for (int r = 0; r < nsub; ++r) {
         const int p0 = (int)((long long)w * r / nsub), p1 = (int)((long long)w * (r + 1) / nsub);
@@ -1204,13 +1227,26 @@ __device__ __forceinline__ void fy_tile_body(int L, const int *__restrict__ ebou
         constexpr int TPF = 8;
         for (int x0 = tid; x0 < count; x0 += TPF * FYT_THREADS) {
             int2 jh[TPF];
+            unsigned pk[TPF];
+            int shv[TPF];
 #pragma unroll
             for (int u = 0; u < TPF; ++u) {
                 const int x = x0 + u * FYT_THREADS;
                 int sh = 0;
 #pragma unroll
                 for (int q = 1; q < FY_SHARDS; ++q) sh += x >= soff[q] ? 1 : 0;
-                jh[u] = x < count ? bk[(size_t)sh * capg + (x - soff[sh])] : make_int2(0, 0);
+                if constexpr (PACK) {
+                    pk[u] = x < count ? bk4[(size_t)sh * capg + (x - soff[sh])] : 0u;
+                    shv[u] = sh;
+                } else {
+                    jh[u] = x < count ? bk[(size_t)sh * capg + (x - soff[sh])] : make_int2(0, 0);
+                }
+            }
+            if constexpr (PACK) {  // (step, target) back from the entry and its shard: the part workgroup was (pk >> 26) * 8 + shard
+#pragma unroll
+                for (int u = 0; u < TPF; ++u)
+                    jh[u] = make_int2((int)(((pk[u] >> 26) << 3) | (unsigned)shv[u]) * FYA_CH + (int)((pk[u] >> 13) & 8191u),
+                                      q_lo + (int)(pk[u] & 8191u));
             }
 #pragma unroll
             for (int u = 0; u < TPF; ++u) {
@@ -1291,7 +1327,7 @@ __device__ __forceinline__ const unsigned *chunk_draw_ptr(const TileChunk &c, in
     return r0 < c.head ? c.ring - (c.head - r0) : c.ring + (r0 - c.head) % c.ring_words;
 }
 
-template <bool STAGED>
+template <bool STAGED, bool PACK>
 __global__ __launch_bounds__(FYA_THREADS) void k_fy_part_multi(const TileChunk *__restrict__ cd, int it0, int dl)
 {
     ACAV_MI_EMPTY_RETURN
@@ -1300,17 +1336,25 @@ __global__ __launch_bounds__(FYA_THREADS) void k_fy_part_multi(const TileChunk *
     const int L = c.L0 - it * dl;
     if (it >= c.iters || (int)blockIdx.x * FYA_CH >= L) return;
     const unsigned lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    fy_part_body<STAGED>(chunk_draw_ptr(c, it, dl), L, c.table, c.ntab, c.gsh, c.NT, c.capg, c.bucket + (size_t)z * c.NT * FY_SHARDS * c.capg,
-                 c.gcount + (size_t)z * c.NT * FY_SHARDS, c.src[z], c.err, (int)blockIdx.x, (int)(lin & (FY_SHARDS - 1)));
+    // (PACK: shard = bx & 7 -- for one iteration of one chunk that is the same rotation of the shards as lin & 7, and a shard is
+    // still written through one XCD's L2)
+    const size_t bofs = (size_t)z * c.NT * FY_SHARDS * c.capg;
+    fy_part_body<STAGED, PACK>(chunk_draw_ptr(c, it, dl), L, c.table, c.ntab, c.gsh, c.NT, c.capg,
+                               PACK ? reinterpret_cast<int2 *>(reinterpret_cast<unsigned *>(c.bucket) + bofs) : c.bucket + bofs,
+                               c.gcount + (size_t)z * c.NT * FY_SHARDS, c.src[z], c.err, (int)blockIdx.x,
+                               (int)((PACK ? blockIdx.x : lin) & (FY_SHARDS - 1)), c.ebound);
 }
 
+template <bool PACK>
 __global__ __launch_bounds__(FYT_THREADS) void k_fy_tile_multi(const TileChunk *__restrict__ cd, int it0, int dl)
 {
     ACAV_MI_EMPTY_RETURN
     const TileChunk &c = cd[blockIdx.y];
     const int z = (int)blockIdx.z, it = it0 + z;
     if (it >= c.iters || (int)blockIdx.x >= c.NT) return;
-    fy_tile_body(c.L0 - it * dl, c.ebound, c.capg, c.ecap, c.wcap, c.bucket + (size_t)z * c.NT * FY_SHARDS * c.capg,
+    const size_t bofs = (size_t)z * c.NT * FY_SHARDS * c.capg;
+    fy_tile_body<PACK>(c.L0 - it * dl, c.ebound, c.capg, c.ecap, c.wcap,
+                 PACK ? reinterpret_cast<int2 *>(reinterpret_cast<unsigned *>(c.bucket) + bofs) : c.bucket + bofs,
                  c.gcount + (size_t)z * c.NT * FY_SHARDS, c.src[z], c.g[z], c.err, (int)blockIdx.x);
 }
 
@@ -1738,9 +1782,10 @@ struct FyPlan {
     size_t tile_smem() const { return (size_t)wcap * 8 + (size_t)ecap_lds * 8; }
 };
 
-static size_t fy_part_smem(int NT, size_t ntab, bool staged)
+static size_t fy_part_smem(int NT, size_t ntab, bool staged, bool pack = false)
 {
-    return sizeof(int) * (staged ? 3 : 2) * (size_t)NT + (staged ? sizeof(int2) * FYA_CH + sizeof(int) * 16 : 0) + sizeof(unsigned short) * ntab;
+    return sizeof(int) * ((staged ? 3 : 2) + (pack ? 1 : 0)) * (size_t)NT + (staged ? sizeof(int2) * FYA_CH + sizeof(int) * 16 : 0) +
+           sizeof(unsigned short) * ntab;
 }
 
 // tiling of a list of (at most) L candidates and the handle's buffers for it: table, tile bounds, sharded buckets and their
@@ -2042,6 +2087,9 @@ static int run_greedy_tiled(acav_mi **mis, int nchunks, const int64_t *const *ca
     std::vector<FyPlan> plans((size_t)nchunks);
     std::vector<MtStream> streams((size_t)nchunks);
     int64_t iters_max = 0, lmax = 0;
+    for (int c = 0; c < nchunks; ++c) lmax = L[c] > lmax ? L[c] : lmax;
+    const char *vpack = getenv("ACAV_FY_PACK");  // =0: the 8-byte bucket entries (A/B)
+    const bool pack = lmax <= FY_PACK_MAX && !(vpack && vpack[0] == '0');
     int pmax = 1, dmax = 1, ntmax = 1;
     size_t part_smem = 0, part_smem_staged = 0, tile_smem = 0;
     for (int c = 0; c < nchunks; ++c) {
@@ -2096,7 +2144,7 @@ static int run_greedy_tiled(acav_mi **mis, int nchunks, const int64_t *const *ca
         ACAV_TRY(fy_setup(mi, L[c], fp, st));
         t_fy += ms_since(t0); }
         ntmax = fp.NT > ntmax ? fp.NT : ntmax;
-        const size_t ps = fy_part_smem(fp.NT, fp.table.size(), false), pss = fy_part_smem(fp.NT, fp.table.size(), true);
+        const size_t ps = fy_part_smem(fp.NT, fp.table.size(), false, pack), pss = fy_part_smem(fp.NT, fp.table.size(), true, pack);
         part_smem = ps > part_smem ? ps : part_smem;
         part_smem_staged = pss > part_smem_staged ? pss : part_smem_staged;
         tile_smem = fp.tile_smem() > tile_smem ? fp.tile_smem() : tile_smem;
@@ -2146,13 +2194,15 @@ static int run_greedy_tiled(acav_mi **mis, int nchunks, const int64_t *const *ca
     const double t_chunks = ms_since(t_setup0);
     ACAV_HIP_TRY(hipStreamSynchronize(st));  // tables, counters, candidate lists, forced positions and descriptors are in place
     const double t_setup = ms_since(t_setup0);
-    ACAV_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fy_tile_multi), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)tile_smem));
+    const auto tile_kernel = pack ? k_fy_tile_multi<true> : k_fy_tile_multi<false>;
+    ACAV_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(tile_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_smem));
     // the staged form of k_fy_part wants 64 KB of LDS beside the tile table (which grows with L: 64 KB at 16 Mi candidates)
     const bool part_staged = part_smem_staged <= 96 * 1024 && !getenv("ACAV_FY_PART_DIRECT");
+    const auto part_kernel = part_staged ? (pack ? k_fy_part_multi<true, true> : k_fy_part_multi<true, false>)
+                                         : (pack ? k_fy_part_multi<false, true> : k_fy_part_multi<false, false>);
     if (part_staged) {
         part_smem = part_smem_staged;
-        ACAV_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fy_part_multi<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        ACAV_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(part_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                          (int)part_smem));
     }
     const TileChunk *dcd = lead->chunk_desc.as<TileChunk>();
@@ -2180,12 +2230,11 @@ static int run_greedy_tiled(acav_mi **mis, int nchunks, const int64_t *const *ca
             ACAV_TRY(streams[(size_t)c].acquire(r0[(size_t)c], nd, &unused));
             r0[(size_t)c] += nd;
         }
-        hipLaunchKernelGGL(part_staged ? k_fy_part_multi<true> : k_fy_part_multi<false>,
-                           dim3((unsigned)((lt + FYA_CH - 1) / FYA_CH), (unsigned)nchunks, gz), dim3(FYA_THREADS), part_smem, sf, dcd,
+        hipLaunchKernelGGL(part_kernel, dim3((unsigned)((lt + FYA_CH - 1) / FYA_CH), (unsigned)nchunks, gz), dim3(FYA_THREADS), part_smem, sf, dcd,
                            (int)g0, (int)dl);
         for (int c = 0; c < nchunks; ++c)
             if (g0 < iters[(size_t)c]) ACAV_TRY(streams[(size_t)c].release(r0[(size_t)c]));  // k_fy_part is the only reader of the draws
-        hipLaunchKernelGGL(k_fy_tile_multi, dim3((unsigned)ntmax, (unsigned)nchunks, gz), dim3(FYT_THREADS), tile_smem, sf, dcd, (int)g0,
+        hipLaunchKernelGGL(tile_kernel, dim3((unsigned)ntmax, (unsigned)nchunks, gz), dim3(FYT_THREADS), tile_smem, sf, dcd, (int)g0,
                            (int)dl);
         hipLaunchKernelGGL(k_fy_resolve_multi, dim3((unsigned)((lt + 255) / 256), (unsigned)nchunks, gz), dim3(256), 0, sf, dcd, (int)g0,
                            (int)dl, keep_unselected ? B - k : 0);
@@ -2716,6 +2765,7 @@ ACAV_EXPORT int acav_mi_run_greedy(acav_mi *mi, const int64_t *candidates, int64
         total_draws += lt > 1 ? lt - 1 : 0;
     }
     MtStream ms;
+    ACAV_TRY(mi_ensure_streams(mi));  // the generator runs on the handle's own generator stream, as in the tiled loop (not the null stream)
     ACAV_TRY(ms.plan(mi, st, mtbuf, idx, total_draws, L, L));
 
     int *Acur = mi->A0.as<int>(), *Anew = mi->A1.as<int>();
@@ -2757,7 +2807,7 @@ ACAV_EXPORT int acav_mi_run_greedy(acav_mi *mi, const int64_t *candidates, int64
         if (trace_ids) ACAV_HIP_TRY(hipMemcpyAsync(trace_ids, mi->tr_ids.p, sizeof(long long) * (size_t)(iters * B), hipMemcpyDeviceToHost, st));
         if (trace_scores) ACAV_HIP_TRY(hipMemcpyAsync(trace_scores, mi->tr_sc.p, sizeof(double) * (size_t)(iters * B), hipMemcpyDeviceToHost, st));
     }
-    if (mi->st_mt) ACAV_HIP_TRY(hipStreamSynchronize(mi->st_mt));
+    ACAV_HIP_TRY(hipStreamSynchronize(mi->st_mt));
     ACAV_HIP_TRY(hipStreamSynchronize(st));
     ACAV_TRY(ms.final_state(mtbuf, &idx));
     ACAV_TRY(acav_rng_set_state(rng, mtbuf, idx));  // the stream continues on the host

@@ -7,7 +7,12 @@
 int main(int argc, char **argv)
 {
     const int L = argc > 1 ? atoi(argv[1]) : 1000000;
-    const int G = FY_GROUP, B = 20, k = 4, dl = 4, reps = 40;
+    // FYB_SLOTS=R (footprint probe, timing only): the iterations of a group share R src / g buffers (iteration z uses slot z % R)
+    // instead of one each -- same launches, grids and work, wrong permutations.  Every iteration of a launch then has the same L
+    // (dl = 0): an src entry written by another iteration stays inside the list, so perm and tailinv stay in range, and a g chain
+    // still only descends (every g[q] < q), so the walks end.  FYB_SLOTS=16 is the unaliased layout at dl = 0 (the A/B baseline).
+    const int slots = getenv("FYB_SLOTS") ? atoi(getenv("FYB_SLOTS")) : 0;
+    const int G = FY_GROUP, B = 20, k = 4, dl = slots > 0 ? 0 : 4, reps = 40;
     FyPlan fp;
     fp.build(L);
     printf("L %d  tiles %d cap %d gsh %d capg %d  tile smem %zu\n", L, fp.NT, fp.ecap, fp.gsh, fp.capg, fp.tile_smem());
@@ -24,6 +29,10 @@ int main(int argc, char **argv)
     const size_t nb = (size_t)G * fp.NT * FY_SHARDS * fp.capg, nc = (size_t)G * fp.NT * FY_SHARDS;
     CK(hipMalloc(&c.bucket, 8 * nb)); CK(hipMalloc(&c.gcount, 4 * nc)); CK(hipMemset(c.gcount, 0, 4 * nc));
     for (int q = 0; q < FY_GROUP; ++q) { CK(hipMalloc(&c.g[q], 4 * (size_t)L)); CK(hipMalloc(&c.src[q], 4 * (size_t)L)); }
+    if (slots > 0 && slots < FY_GROUP) {
+        for (int q = slots; q < FY_GROUP; ++q) { CK(hipFree(c.g[q])); CK(hipFree(c.src[q])); c.g[q] = c.g[q % slots]; c.src[q] = c.src[q % slots]; }
+        printf("src / g: %d slots shared by the %d iterations of a group (timing only)\n", slots, FY_GROUP);
+    }
     for (int q = 0; q < FY_NBUF; ++q) { CK(hipMalloc(&c.perm[q], 4 * (size_t)L)); CK(hipMemset(c.perm[q], 0, 4 * (size_t)L)); }
     CK(hipMalloc(&c.A[0], 4 * (size_t)(L + B))); CK(hipMalloc(&c.A[1], 4 * (size_t)(L + B)));
     CK(hipMemset(c.A[0], 0, 4 * (size_t)(L + B))); CK(hipMemset(c.A[1], 0, 4 * (size_t)(L + B)));
@@ -47,14 +56,19 @@ int main(int argc, char **argv)
     c.L0 = L; c.iters = iters; c.ntab = (int)fp.table.size(); c.gsh = fp.gsh; c.NT = fp.NT; c.capg = fp.capg; c.ecap = fp.ecap_lds; c.wcap = fp.wcap;
     c.D = D; c.C = C; c.P = P;
     TileChunk *dcd; CK(hipMalloc(&dcd, sizeof(c))); CK(hipMemcpy(dcd, &c, sizeof(c), hipMemcpyHostToDevice));
-    CK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fy_tile_multi), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fp.tile_smem()));
+    // FYB_PACK=0: 8-byte bucket entries (the product's ACAV_FY_PACK=0)
+    const bool pack = L <= FY_PACK_MAX && !(getenv("FYB_PACK") && getenv("FYB_PACK")[0] == '0');
+    const auto tile_k = pack ? k_fy_tile_multi<true> : k_fy_tile_multi<false>;
+    const auto part_st = pack ? k_fy_part_multi<true, true> : k_fy_part_multi<true, false>;
+    const auto part_di = pack ? k_fy_part_multi<false, true> : k_fy_part_multi<false, false>;
+    CK(hipFuncSetAttribute(reinterpret_cast<const void *>(tile_k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fp.tile_smem()));
     const bool staged = getenv("FYB_PART_DIRECT") == nullptr;
-    const size_t part_smem = fy_part_smem(fp.NT, fp.table.size(), staged);
-    CK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fy_part_multi<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fy_part_smem(fp.NT, fp.table.size(), true)));
-    printf("part: %s, %zu B of LDS\n", staged ? "staged" : "direct", part_smem);
+    const size_t part_smem = fy_part_smem(fp.NT, fp.table.size(), staged, pack);
+    CK(hipFuncSetAttribute(reinterpret_cast<const void *>(part_st), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fy_part_smem(fp.NT, fp.table.size(), true, pack)));
+    printf("part: %s, %zu B of LDS; bucket entries of %d bytes\n", staged ? "staged" : "direct", part_smem, pack ? 4 : 8);
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-    auto part = [&]() { if (staged) hipLaunchKernelGGL(k_fy_part_multi<true>, dim3((L + FYA_CH - 1) / FYA_CH, 1, G), dim3(FYA_THREADS), part_smem, 0, dcd, 0, dl); else hipLaunchKernelGGL(k_fy_part_multi<false>, dim3((L + FYA_CH - 1) / FYA_CH, 1, G), dim3(FYA_THREADS), part_smem, 0, dcd, 0, dl); };
-    auto tile = [&]() { hipLaunchKernelGGL(k_fy_tile_multi, dim3(fp.NT, 1, G), dim3(FYT_THREADS), fp.tile_smem(), 0, dcd, 0, dl); };
+    auto part = [&]() { hipLaunchKernelGGL(staged ? part_st : part_di, dim3((L + FYA_CH - 1) / FYA_CH, 1, G), dim3(FYA_THREADS), part_smem, 0, dcd, 0, dl); };
+    auto tile = [&]() { hipLaunchKernelGGL(tile_k, dim3(fp.NT, 1, G), dim3(FYT_THREADS), fp.tile_smem(), 0, dcd, 0, dl); };
     auto resolve = [&]() { hipLaunchKernelGGL(k_fy_resolve_multi, dim3((L + 255) / 256, 1, G), dim3(256), 0, 0, dcd, 0, dl, B - k); };
     auto timeit = [&](const char *name, auto fn, double base_us) {
         for (int i = 0; i < 3; ++i) fn();
@@ -119,9 +133,8 @@ int main(int argc, char **argv)
         }
         CK(hipStreamCreateWithPriority(&sb, hipStreamNonBlocking, pri ? hi : 0));
         auto side = [&](hipStream_t st) {
-            if (staged) hipLaunchKernelGGL(k_fy_part_multi<true>, dim3((L + FYA_CH - 1) / FYA_CH, 1, G), dim3(FYA_THREADS), part_smem, st, dcd, 8, dl);
-            else hipLaunchKernelGGL(k_fy_part_multi<false>, dim3((L + FYA_CH - 1) / FYA_CH, 1, G), dim3(FYA_THREADS), part_smem, st, dcd, 8, dl);
-            hipLaunchKernelGGL(k_fy_tile_multi, dim3(fp.NT, 1, G), dim3(FYT_THREADS), fp.tile_smem(), st, dcd, 8, dl);
+            hipLaunchKernelGGL(staged ? part_st : part_di, dim3((L + FYA_CH - 1) / FYA_CH, 1, G), dim3(FYA_THREADS), part_smem, st, dcd, 8, dl);
+            hipLaunchKernelGGL(tile_k, dim3(fp.NT, 1, G), dim3(FYT_THREADS), fp.tile_smem(), st, dcd, 8, dl);
             hipLaunchKernelGGL(k_fy_resolve_multi, dim3((L + 255) / 256, 1, G), dim3(256), 0, st, dcd, 8, dl, B - k);
         };
         const bool nosel = getenv("FYB_NOSEL") != nullptr;  // every gather as launch 0: no selection beside it
