@@ -84,6 +84,7 @@ SIGNATURES = {
     "acav_mi_run_exact": [vp, vp, i64, i32, i64, vp, vp, C.POINTER(i64), vp, vp, vp],
     "acav_mi_set_measure": [vp, i32],
     "acav_mi_set_average_method": [vp, i32],
+    "acav_mi_set_pair_weights": [vp, vp, i32],
     "acav_mi_get_pair_stats": [vp, vp, vp, vp, vp],
     "acav_mi_get_counts": [vp, vp, vp, vp, C.POINTER(i64)],
     "acav_mi_sync": [vp],

@@ -144,7 +144,9 @@ SUBSET_DEFAULTS = {
         'concurrent_chunks': 1,  # ours: > 1 selects from that many chunks in lockstep on one GPU (own RNG stream each)
     },
     'subset': {'ratio': 0.2, 'size': None},
-    'clustering': {'pairing': 'combination'},
+    # weight_type: None, or linear|log|exp[_<coeff>] / onehot_<layer>: per-layer weights of the clustering pairs
+    #   (correspondence_retrieval cluster_pairing.py / pair_weights.py) for the mi, mem_mi and batch_mi measures
+    'clustering': {'pairing': 'combination', 'weight_type': None},
     'batch': {'batch_size': 20, 'selection_size': 4, 'keep_unselected': True},
     'contrastive': {'num_epochs': 3, 'num_warmup_steps': 1, 'base_lr': 2e-4, 'train_batch_size': 128, 'test_batch_size': 128,
                     'cached_epoch': None, 'train_from_cached': False},

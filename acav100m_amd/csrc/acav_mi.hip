@@ -14,6 +14,7 @@
 // The whole loop is enqueued without host synchronisation: L shrinks deterministically.
 #include <chrono>
 #include <cmath>
+#include <type_traits>
 
 #include "acav_common.h"
 #include <vector>
@@ -319,6 +320,13 @@ struct SelShared {
     int id[SEL_MAXB], pos[SEL_MAXB], pick[SEL_MAXB];
     int pairs[2 * SEL_LDSP];
 };
+// the weighted selection (W: acav_mi_set_pair_weights) stages the fp32 pair weights beside the pairs; the unweighted kernels
+// keep the LDS footprint of SelShared
+struct SelSharedW : SelShared {
+    float w[SEL_LDSP];
+};
+template <bool W>
+using SelSharedOf = std::conditional_t<W, SelSharedW, SelShared>;
 
 // Dynamic LDS of a selection launch:  scores [B P] f64 | labels + counts 5 x [B P] i32 (SEL_FAST) | scoring's phi [B P][6] f64
 // (SEL_KEEPPHI) | commit's phi [k P][6] f64 (SEL_FAST) | label rows [B D] i32.  The mode is decided on the host for the
@@ -352,10 +360,13 @@ __device__ __forceinline__ void lds_barrier()
     __builtin_amdgcn_s_barrier();
 }
 
-// everything the selection needs that does not depend on the batch; a barrier must separate it from mi_select_body
-__device__ __forceinline__ void mi_select_stage(SelShared &ss, int P, const int *__restrict__ pairs,
+// everything the selection needs that does not depend on the batch; a barrier must separate it from mi_select_body.
+// W: pw holds the P fp32 pair weights, or is NULL for a chunk without weights (weight 1: s * 1.0 is s)
+template <bool W>
+__device__ __forceinline__ void mi_select_stage(SelSharedOf<W> &ss, int P, const int *__restrict__ pairs,
                                                 const double *__restrict__ SN, const double *__restrict__ Sa,
-                                                const double *__restrict__ Sb, const MiScalars *__restrict__ sc)
+                                                const double *__restrict__ Sb, const MiScalars *__restrict__ sc,
+                                                const float *__restrict__ pw = nullptr)
 {
     const int tid = threadIdx.x;
     if (tid == 0) ss.nc = sc->nc;
@@ -365,19 +376,24 @@ __device__ __forceinline__ void mi_select_stage(SelShared &ss, int P, const int 
         ss.SN[p] = SN[p];
         ss.Sa[p] = Sa[p];
         ss.Sb[p] = Sb[p];
+        if constexpr (W) ss.w[p] = pw ? pw[p] : 1.0f;
     }
 }
 
 // batch == nullptr: the id of batch position tid (< B) is in reg_id.  lab_in: the B label rows [B][D] when the caller has
 // them (else they are read from asg: one more level).  mode: sel_mode() for the launch (decided on the host).
+// W: every pair score is multiplied by its fp32 weight (pw, staged in ss.w up to SEL_LDSP pairs) where it is written to sS, so
+// the candidate's score is sum_p(s_p w_p) / P -- the reference's einsum('wp,p->wp') before .mean(-1) (correspondence_retrieval
+// measures/efficient.py:95-101)
+template <bool W>
 __device__ __forceinline__ void mi_select_body(
-    SelShared &ss, const int *__restrict__ asg, int D, int C, int P, const int *__restrict__ pairs,
+    SelSharedOf<W> &ss, const int *__restrict__ asg, int D, int C, int P, const int *__restrict__ pairs,
     const int *__restrict__ batch, int reg_id, const int *__restrict__ lab_in, int B, int k, int mode, int *__restrict__ Nc,
     int *__restrict__ ac, int *__restrict__ bc, double *__restrict__ SN, double *__restrict__ Sa, double *__restrict__ Sb,
     const double *__restrict__ phi, MiScalars *__restrict__ sc, double *__restrict__ scores_out,
     long long *__restrict__ S_out, double *__restrict__ G_out, const int *__restrict__ forced_pos,
     int *__restrict__ trace_pos, long long *__restrict__ trace_ids, double *__restrict__ trace_scores,
-    int keep_unselected, int *__restrict__ requeue_out, int requeue_stride = 1)
+    int keep_unselected, int *__restrict__ requeue_out, int requeue_stride = 1, const float *__restrict__ pw = nullptr)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const bool fast = (mode & SEL_FAST) != 0, keepphi = (mode & SEL_KEEPPHI) != 0;
@@ -417,7 +433,9 @@ __device__ __forceinline__ void mi_select_body(
         const double sN = sN0 - f0 + f1;
         const double sa = sa0 - f2 + f3;
         const double sb = sb0 - f4 + f5;
-        sS[t] = (((sN - sa) - sb) + phin) / (double)(nc + 1);
+        const double sp = (((sN - sa) - sb) + phin) / (double)(nc + 1);
+        if constexpr (W) sS[t] = sp * (double)(lp ? ss.w[p] : (pw ? pw[p] : 1.0f));
+        else sS[t] = sp;
         if (fast) sCi[t] = i, sCj[t] = j, sCN[t] = cN, sCa[t] = ca, sCb[t] = cb;
         if (keepphi) {
             double *o6 = sPhiAll + (size_t)t * 6;
@@ -563,6 +581,8 @@ __device__ __forceinline__ void mi_select_body(
     FY_CLK(12);
 }
 
+// W: the weighted instantiation (pw = the handle's pair weights); the unweighted one never reads pw
+template <bool W>
 __global__ __launch_bounds__(256) void k_mi_select(
     const int *__restrict__ asg, int D, int C, int P, const int *__restrict__ pairs,
     const int *__restrict__ batch, int B, int k, int mode, int *__restrict__ Nc, int *__restrict__ ac,
@@ -570,12 +590,12 @@ __global__ __launch_bounds__(256) void k_mi_select(
     const double *__restrict__ phi, MiScalars *__restrict__ sc, double *__restrict__ scores_out,
     long long *__restrict__ S_out, double *__restrict__ G_out, const int *__restrict__ forced_pos,
     int *__restrict__ trace_pos, long long *__restrict__ trace_ids, double *__restrict__ trace_scores,
-    int keep_unselected, int *__restrict__ requeue_out)
+    int keep_unselected, int *__restrict__ requeue_out, const float *__restrict__ pw)
 {
-    __shared__ SelShared ss;
-    mi_select_stage(ss, P, pairs, SN, Sa, Sb, sc);
-    mi_select_body(ss, asg, D, C, P, pairs, batch, 0, nullptr, B, k, mode, Nc, ac, bc, SN, Sa, Sb, phi, sc, scores_out, S_out, G_out,
-                   forced_pos, trace_pos, trace_ids, trace_scores, keep_unselected, requeue_out);
+    __shared__ SelSharedOf<W> ss;
+    mi_select_stage<W>(ss, P, pairs, SN, Sa, Sb, sc, pw);
+    mi_select_body<W>(ss, asg, D, C, P, pairs, batch, 0, nullptr, B, k, mode, Nc, ac, bc, SN, Sa, Sb, phi, sc, scores_out, S_out, G_out,
+                      forced_pos, trace_pos, trace_ids, trace_scores, keep_unselected, requeue_out, 1, pw);
 }
 
 // ------------------------------------------------------------------- exact greedy (mi / mem_mi)
@@ -604,8 +624,9 @@ __device__ __forceinline__ bool exact_better(double s, int p, double so, int po)
 }
 
 // PAIR: the pair-counting scores (measures 4-6) in an instantiation of their own, so that the code of measures 0-3 is what
-// it was before they existed
-template <bool PAIR>
+// it was before they existed.  W (measure 0 only): the weighted pair mean sum_p(s_p w_p) / P with the handle's fp32 pair
+// weights pw (acav_mi_set_pair_weights), in an instantiation of its own for the same reason
+template <bool PAIR, bool W = false>
 __global__ __launch_bounds__(256) void k_mi_exact_iter(
     const int *__restrict__ asg, int D, int C, int P, const int *__restrict__ pairs, const int *__restrict__ A, int L,
     unsigned char *__restrict__ removed, int *__restrict__ Nc, int *__restrict__ ac, int *__restrict__ bc,
@@ -613,7 +634,7 @@ __global__ __launch_bounds__(256) void k_mi_exact_iter(
     MiScalars *__restrict__ sc, ExactBest *__restrict__ blockbest, unsigned *__restrict__ ticket,
     long long *__restrict__ S_out, double *__restrict__ G_out, const int *__restrict__ forced,
     double *__restrict__ trace_scores, int *__restrict__ trace_argmax, int measure, const double *__restrict__ lnk,
-    const double *__restrict__ lf, int avg, PairStat *__restrict__ ps)
+    const double *__restrict__ lf, int avg, PairStat *__restrict__ ps, const float *__restrict__ pw)
 {
     // measure 0: calc_MI ('mi' / 'mem_mi'); 1: calc_AMI ('ami'); 2: calc_NMI (mi.py:262-271); 3: ConstantMeasure (mi.py:274-281:
     // every candidate scores 1, the first remaining one is taken); 4 / 5 / 6: Fowlkes-Mallows / Rand / adjusted Rand
@@ -621,6 +642,8 @@ __global__ __launch_bounds__(256) void k_mi_exact_iter(
     auto pair_score = [&](int p, int id, long long n) -> double {
         if constexpr (PAIR) {
             return pair_count_score(asg, D, C, p, pairs, id, Nc, ac, bc, ps, n, measure);
+        } else if constexpr (W) {
+            return mi_pair_score(asg, D, C, p, pairs, id, Nc, ac, bc, SN, Sa, Sb, phi, n) * (double)pw[p];
         } else {
             if (measure == 1) return ami_pair_score(asg, D, C, p, pairs, id, Nc, ac, bc, SN, Sa, Sb, phi, lnk, lf, n, avg);
             if (measure == 2) return nmi_pair_score(asg, D, C, p, pairs, id, Nc, ac, bc, SN, Sa, Sb, phi, lnk, n, avg);
@@ -1319,6 +1342,7 @@ struct TileChunk {
     long long *tr_ids;
     double *tr_sc;
     int L0, iters, ntab, gsh, NT, capg, ecap, wcap, D, C, P, pad;
+    const float *w;          // fp32 pair weights [P] (acav_mi_set_pair_weights), NULL: unweighted
 };
 
 __device__ __forceinline__ const unsigned *chunk_draw_ptr(const TileChunk &c, int it, int dl)
@@ -1397,6 +1421,8 @@ __global__ __launch_bounds__(256) void k_fy_resolve_multi(const TileChunk *__res
 //   workgroup 0      SELECTION of iteration it-1 (mi_select_body: scoring / top-k / commit on the batch gathered by the
 //                    previous launch), then the nreq re-queued ids go straight to the outputs of iteration `it` that read them.
 // Launches run it = 0 .. iters (the first has no selection, the last no gather).
+// W: the weighted selection (some chunk of the launch has pair weights); launched only then
+template <bool W>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_fy_gather_select_multi(
     const TileChunk *__restrict__ cd, int it, int dl, int B, int k, int mode, int keep_unselected)
 {
@@ -1437,17 +1463,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     }
     if (it < 1 || it > c.iters) return;
     const int ps = it - 1;  // the iteration whose selection this is
-    __shared__ SelShared ss;
+    __shared__ SelSharedOf<W> ss;
     __shared__ int sReq[SEL_MAXB];
     const int *bprev = c.batch + (ps & 1) * bstride;
-    mi_select_stage(ss, c.P, c.pairs, c.SN, c.Sa, c.Sb, c.sc);
+    mi_select_stage<W>(ss, c.P, c.pairs, c.SN, c.Sa, c.Sb, c.sc, W ? c.w : nullptr);
     const int id = (int)threadIdx.x < B ? bprev[threadIdx.x] : 0;
     const bool feeds = it < c.iters && (int)threadIdx.x < nreq;  // this thread delivers a re-queued id to the gather of `it`
     const int dest = feeds ? c.tailinv[(size_t)(it % FY_NBUF) * SEL_MAXB + threadIdx.x] : 0;
-    mi_select_body(ss, c.asg, c.D, c.C, c.P, c.pairs, nullptr, id, bprev + SEL_MAXB, B, k, mode, c.Nc, c.ac, c.bc, c.SN, c.Sa, c.Sb,
-                   c.phi, c.sc, nullptr, c.S + (size_t)ps * k, c.G + (size_t)ps * k, c.forced ? c.forced + (size_t)ps * k : nullptr,
-                   c.tr_pos ? c.tr_pos + (size_t)ps * k : nullptr, c.tr_ids ? c.tr_ids + (size_t)ps * B : nullptr,
-                   c.tr_sc ? c.tr_sc + (size_t)ps * B : nullptr, keep_unselected, sReq);
+    mi_select_body<W>(ss, c.asg, c.D, c.C, c.P, c.pairs, nullptr, id, bprev + SEL_MAXB, B, k, mode, c.Nc, c.ac, c.bc, c.SN, c.Sa, c.Sb,
+                      c.phi, c.sc, nullptr, c.S + (size_t)ps * k, c.G + (size_t)ps * k, c.forced ? c.forced + (size_t)ps * k : nullptr,
+                      c.tr_pos ? c.tr_pos + (size_t)ps * k : nullptr, c.tr_ids ? c.tr_ids + (size_t)ps * B : nullptr,
+                      c.tr_sc ? c.tr_sc + (size_t)ps * B : nullptr, keep_unselected, sReq, 1, W ? c.w : nullptr);
     if (it >= c.iters || nreq == 0) return;  // no gather left to feed
     lds_barrier();
     if (feeds) {
@@ -1483,8 +1509,14 @@ struct ChunkDesc {
     int *batch;
     long long *S;
     double *G;
-    int D, C, P, L0, iters, pad;
+    int D, C, P, L0, iters;
+    int wt;  // 1: the chunk has pair weights, fp32 [P] right behind its pairs (pairs + 2 P; acav_mi_set_pair_weights).  (Not a
+             // pointer: the kernels copy the descriptor to scratch, and a larger one would grow every unweighted kernel's scratch)
 };
+__device__ __forceinline__ const float *chunk_weights(const ChunkDesc &c)
+{
+    return c.wt ? reinterpret_cast<const float *>(c.pairs + 2 * (size_t)c.P) : nullptr;
+}
 
 __device__ __forceinline__ long long chunk_draws(const ChunkDesc &c, int t0, int t1, int dl)
 {  // draws of iterations [t0, t1) of the chunk: sum of (L_t - 1)
@@ -1520,16 +1552,18 @@ __global__ __launch_bounds__(256) void k_fy_apply_multi(const ChunkDesc *__restr
                   c.head[(it + 1) & 1], c.g[(it + 1) & 1], (int)(blockIdx.x * blockDim.x + threadIdx.x));
 }
 
+template <bool W>
 __global__ __launch_bounds__(256) void k_mi_select_multi(const ChunkDesc *__restrict__ cd, int it, int dl, int B, int k,
                                                          int mode, int keep_unselected)
 {
     const ChunkDesc c = cd[blockIdx.x];
     if (it >= c.iters) return;
-    __shared__ SelShared ss;
-    mi_select_stage(ss, c.P, c.pairs, c.SN, c.Sa, c.Sb, c.sc);
-    mi_select_body(ss, c.asg, c.D, c.C, c.P, c.pairs, c.batch, 0, nullptr, B, k, mode, c.Nc, c.ac, c.bc, c.SN, c.Sa, c.Sb, c.phi, c.sc, nullptr,
-                   c.S + (size_t)it * k, c.G + (size_t)it * k, nullptr, nullptr, nullptr, nullptr, keep_unselected,
-                   c.A[(it + 1) & 1] + (c.L0 - it * dl - B));
+    __shared__ SelSharedOf<W> ss;
+    const float *pw = W ? chunk_weights(c) : nullptr;
+    mi_select_stage<W>(ss, c.P, c.pairs, c.SN, c.Sa, c.Sb, c.sc, pw);
+    mi_select_body<W>(ss, c.asg, c.D, c.C, c.P, c.pairs, c.batch, 0, nullptr, B, k, mode, c.Nc, c.ac, c.bc, c.SN, c.Sa, c.Sb, c.phi, c.sc,
+                      nullptr, c.S + (size_t)it * k, c.G + (size_t)it * k, nullptr, nullptr, nullptr, nullptr, keep_unselected,
+                      c.A[(it + 1) & 1] + (c.L0 - it * dl - B), 1, pw);
 }
 
 __global__ void k_i64_to_i32(const long long *__restrict__ in, int *__restrict__ out, long long n)
@@ -1556,6 +1590,7 @@ struct acav_mi {
     int measure = 0;  // exact greedy: 0 = calc_MI, 1 = calc_AMI, 2 = calc_NMI, 3 = constant, 4 = FM, 5 = Rand, 6 = ARI
     int avg = 0;      // average_method of 1 and 2: 0 = arithmetic, 1 = max, 2 = min (acav_mi_set_average_method)
     DevBuf pst;       // PairStat [P] of the pair-counting scores (derived from the tables by k_pair_stats_init)
+    bool weighted = false;  // pairs holds the fp32 pair weights [P] behind the 2 P indices (acav_mi_set_pair_weights)
     bool pst_valid = false;  // pst matches the tables: only the exact greedy with a pair-counting score keeps it up to date;
                              // anything else that changes the tables (add_samples = init_pair_stats) re-derives it, residues 0
     int queue_probe_replaced = 0;  // streams replaced by mi_separate_queues (diagnostics: ACAV_MI_TIMING prints it)
@@ -1573,6 +1608,12 @@ struct acav_mi {
 };
 
 struct acav_rng;  // state access through the C ABI below
+
+// the handle's fp32 pair weights (the tail of its pairs block), NULL when it has none
+static const float *mi_weights(acav_mi *mi)
+{
+    return mi->weighted ? reinterpret_cast<const float *>(mi->pairs.as<int>() + 2 * (size_t)mi->P) : nullptr;
+}
 
 // Host-side plan of one chunk's draw stream: T draws in all, produced on the generator stream `smt` by W lanes in
 // superblocks of S = W * blk words into a two-slot ring, consumed by the Fisher-Yates kernels on `st` iteration by
@@ -1916,7 +1957,7 @@ ACAV_EXPORT int acav_mi_create(acav_mi **out, int device, const int64_t *assignm
     phi[0] = 0.0;
     for (int64_t k = 1; k < V + 2; ++k) phi[(size_t)k] = (double)k * log((double)k);
     auto body = [&]() -> int {
-        ACAV_TRY(mi->pairs.ensure(sizeof(int) * 2 * (size_t)P));
+        ACAV_TRY(mi->pairs.ensure(sizeof(int) * 3 * (size_t)P));  // [2 P] pair indices, then room for [P] fp32 pair weights
         ACAV_TRY(mi->Nc.ensure(sizeof(int) * cc));
         ACAV_TRY(mi->ac.ensure(sizeof(int) * pc));
         ACAV_TRY(mi->bc.ensure(sizeof(int) * pc));
@@ -2091,6 +2132,7 @@ static int run_greedy_tiled(acav_mi **mis, int nchunks, const int64_t *const *ca
     const char *vpack = getenv("ACAV_FY_PACK");  // =0: the 8-byte bucket entries (A/B)
     const bool pack = lmax <= FY_PACK_MAX && !(vpack && vpack[0] == '0');
     int pmax = 1, dmax = 1, ntmax = 1;
+    bool weighted = false;  // some chunk has pair weights: the weighted selection for the whole launch
     size_t part_smem = 0, part_smem_staged = 0, tile_smem = 0;
     for (int c = 0; c < nchunks; ++c) {
         acav_mi *mi = mis[c];
@@ -2188,6 +2230,8 @@ static int run_greedy_tiled(acav_mi **mis, int nchunks, const int64_t *const *ca
         d.tr_sc = ex.trace_scores ? mi->tr_sc.as<double>() : nullptr;
         d.L0 = (int)L[c], d.iters = (int)itc, d.ntab = (int)fp.table.size(), d.gsh = fp.gsh, d.NT = fp.NT, d.capg = fp.capg;
         d.ecap = fp.ecap_lds, d.wcap = fp.wcap, d.D = mi->D, d.C = mi->C, d.P = mi->P, d.pad = 0;
+        d.w = mi_weights(mi);
+        weighted = weighted || mi->weighted;
     }
     ACAV_TRY(lead->chunk_desc.ensure(sizeof(TileChunk) * (size_t)nchunks));
     ACAV_HIP_TRY(hipMemcpyAsync(lead->chunk_desc.p, desc.data(), sizeof(TileChunk) * (size_t)nchunks, hipMemcpyHostToDevice, st));
@@ -2208,8 +2252,9 @@ static int run_greedy_tiled(acav_mi **mis, int nchunks, const int64_t *const *ca
     const TileChunk *dcd = lead->chunk_desc.as<TileChunk>();
     const int sel_f = sel_mode(B, pmax, k);  // one mode for every chunk of the launch: sized for the largest P and D
     const size_t sel_smem = sel_layout(B, pmax, dmax, k, sel_f).total;
+    const auto gs_kernel = weighted ? k_fy_gather_select_multi<true> : k_fy_gather_select_multi<false>;
     if (sel_smem > 48 * 1024)
-        ACAV_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fy_gather_select_multi),
+        ACAV_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(gs_kernel),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)sel_smem));
     const auto t_loop0 = std::chrono::steady_clock::now();
     for (int64_t g0 = 0; g0 < iters_max; g0 += FY_GROUP) {
@@ -2243,13 +2288,13 @@ static int run_greedy_tiled(acav_mi **mis, int nchunks, const int64_t *const *ca
         ACAV_HIP_TRY(hipStreamWaitEvent(st, lead->ev_tile[ge], 0));
         for (int64_t it = g0; it < g1; ++it) {
             const dim3 grid((unsigned)((lmax - it * dl + 256 * GS_EPT - 1) / (256 * GS_EPT)) + 1u, (unsigned)nchunks);
-            hipLaunchKernelGGL(k_fy_gather_select_multi, grid, dim3(256), sel_smem, st, dcd, (int)it, (int)dl, B, k, sel_f, keep_unselected);
+            hipLaunchKernelGGL(gs_kernel, grid, dim3(256), sel_smem, st, dcd, (int)it, (int)dl, B, k, sel_f, keep_unselected);
         }
         ACAV_HIP_TRY(hipGetLastError());
         ACAV_HIP_TRY(hipEventRecord(lead->ev_gather[ge], st));
     }
     if (iters_max > 0)  // the selection of the last iteration
-        hipLaunchKernelGGL(k_fy_gather_select_multi, dim3(1u, (unsigned)nchunks), dim3(256), sel_smem, st, dcd, (int)iters_max, (int)dl, B, k,
+        hipLaunchKernelGGL(gs_kernel, dim3(1u, (unsigned)nchunks), dim3(256), sel_smem, st, dcd, (int)iters_max, (int)dl, B, k,
                            sel_f, keep_unselected);
     ACAV_HIP_TRY(hipGetLastError());
     const auto t_loop1 = std::chrono::steady_clock::now();
@@ -2339,6 +2384,7 @@ ACAV_EXPORT int acav_mi_run_greedy_multi(acav_mi **mis, int nchunks, const int64
     std::vector<int64_t> iters((size_t)nchunks, 0);
     int64_t iters_max = 0, lmax = 0;
     int pmax = 1, dmax = 1;
+    bool weighted = false;  // some chunk has pair weights: the weighted selection for the whole launch
     for (int c = 0; c < nchunks; ++c) {
         acav_mi *mi = mis[c];
         ACAV_REQUIRE(mi && candidates[c] && rngs[c] && S_out[c] && GAIN_out[c], ACAV_EINVAL, "chunk %d: NULL argument", c);
@@ -2399,7 +2445,8 @@ ACAV_EXPORT int acav_mi_run_greedy_multi(acav_mi **mis, int nchunks, const int64
         d.g[0] = mi->g.as<int>(), d.g[1] = mi->g2.as<int>();
         d.mt = mi->mt.as<unsigned>(), d.batch = mi->batch.as<int>();
         d.S = mi->S.as<long long>(), d.G = mi->G.as<double>();
-        d.D = mi->D, d.C = mi->C, d.P = mi->P, d.L0 = (int)L[c], d.iters = (int)itc, d.pad = 0;
+        d.D = mi->D, d.C = mi->C, d.P = mi->P, d.L0 = (int)L[c], d.iters = (int)itc, d.wt = mi->weighted ? 1 : 0;
+        weighted = weighted || mi->weighted;
     }
     ACAV_TRY(lead->chunk_desc.ensure(sizeof(ChunkDesc) * (size_t)nchunks));
     ACAV_HIP_TRY(hipMemcpyAsync(lead->chunk_desc.p, desc.data(), sizeof(ChunkDesc) * (size_t)nchunks, hipMemcpyHostToDevice, st));
@@ -2418,8 +2465,9 @@ ACAV_EXPORT int acav_mi_run_greedy_multi(acav_mi **mis, int nchunks, const int64
     if (iters_max > 0) ACAV_TRY(launch_mt(0));
     const int sel_f = sel_mode(B, pmax, k);
     const size_t smem = sel_layout(B, pmax, dmax, k, sel_f).total;
+    const auto sel_kernel = weighted ? k_mi_select_multi<true> : k_mi_select_multi<false>;
     if (smem > 48 * 1024)
-        ACAV_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mi_select_multi), hipFuncAttributeMaxDynamicSharedMemorySize,
+        ACAV_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(sel_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                          (int)smem));
     for (int64_t it = 0; it < iters_max; ++it) {
         const int64_t grp = it / MT_GROUP;
@@ -2433,7 +2481,7 @@ ACAV_EXPORT int acav_mi_run_greedy_multi(acav_mi **mis, int nchunks, const int64
         hipLaunchKernelGGL(k_fy_build_multi, grid, dim3(256), 0, st, dcd, (int)it, (int)dl);
         if (it % MT_GROUP == MT_GROUP - 1 || it + 1 == iters_max) ACAV_HIP_TRY(hipEventRecord(lead->ev_used[cur], st));
         hipLaunchKernelGGL(k_fy_apply_multi, grid, dim3(256), 0, st, dcd, (int)it, (int)dl, B);
-        hipLaunchKernelGGL(k_mi_select_multi, dim3((unsigned)nchunks), dim3(256), smem, st, dcd, (int)it, (int)dl, B, k, sel_f,
+        hipLaunchKernelGGL(sel_kernel, dim3((unsigned)nchunks), dim3(256), smem, st, dcd, (int)it, (int)dl, B, k, sel_f,
                            keep_unselected);
     }
     ACAV_HIP_TRY(hipGetLastError());
@@ -2489,6 +2537,28 @@ ACAV_EXPORT int acav_mi_set_average_method(acav_mi *mi, int method)
     ACAV_REQUIRE(mi, ACAV_EINVAL, "handle is NULL");
     ACAV_REQUIRE(method >= 0 && method <= 2, ACAV_EINVAL, "unknown average_method %d (0 arithmetic, 1 max, 2 min)", method);
     mi->avg = method;
+    return ACAV_OK;
+}
+
+// per-pair weights of the MI score (correspondence_retrieval cluster_pairing.py:7-21 / pair_weights.py:4-50; applied in
+// measures/efficient.py:95-101): a candidate scores sum_p(s_p w_p) / P.  NULL clears them.  The weighted kernels are separate
+// instantiations; only the MI scores take weights (the batch greedy, and measure 0 of the exact greedy)
+ACAV_EXPORT int acav_mi_set_pair_weights(acav_mi *mi, const float *weights, int P)
+{
+    ACAV_REQUIRE(mi, ACAV_EINVAL, "handle is NULL");
+    if (!weights) {
+        mi->weighted = false;
+        return ACAV_OK;
+    }
+    ACAV_REQUIRE(P == mi->P, ACAV_EINVAL, "%d pair weights for a handle of %d pairs", P, mi->P);
+    ACAV_REQUIRE(!is_device_ptr(weights), ACAV_EINVAL, "weights are a host array");
+    for (int p = 0; p < P; ++p)
+        ACAV_REQUIRE(std::isfinite(weights[p]), ACAV_EINVAL, "pair weight %d is not finite", p);
+    ACAV_HIP_TRY(hipSetDevice(mi->ctx.device));
+    ACAV_HIP_TRY(hipMemcpyAsync(mi->pairs.as<int>() + 2 * (size_t)P, weights, sizeof(float) * (size_t)P, hipMemcpyHostToDevice,
+                                mi->ctx.stream));
+    ACAV_HIP_TRY(hipStreamSynchronize(mi->ctx.stream));  // the caller's array may go away
+    mi->weighted = true;
     return ACAV_OK;
 }
 
@@ -2579,8 +2649,10 @@ ACAV_EXPORT int acav_mi_run_exact(acav_mi *mi, const int64_t *candidates, int64_
         ACAV_TRY(pair_stats_init(mi));
     }
     const bool pair = mi->measure >= 4;
+    const bool wt = mi->weighted && mi->measure == 0;  // the reference weights calc_MI only (the others override _calc_score)
+    const auto exact_kernel = pair ? k_mi_exact_iter<true> : wt ? k_mi_exact_iter<false, true> : k_mi_exact_iter<false>;
     for (int64_t it = 0; it < iters; ++it) {
-        hipLaunchKernelGGL(pair ? k_mi_exact_iter<true> : k_mi_exact_iter<false>, dim3(grid), dim3(256), 0, st, mi->asg.as<int>(), mi->D, mi->C, mi->P,
+        hipLaunchKernelGGL(exact_kernel, dim3(grid), dim3(256), 0, st, mi->asg.as<int>(), mi->D, mi->C, mi->P,
                            mi->pairs.as<int>(), mi->A0.as<int>(), (int)L, mi->removed.as<unsigned char>(), mi->Nc.as<int>(),
                            mi->ac.as<int>(), mi->bc.as<int>(), mi->SN.as<double>(), mi->Sa.as<double>(), mi->Sb.as<double>(),
                            mi->phi.as<double>(), mi->scalars.as<MiScalars>(), mi->blockbest.as<ExactBest>(),
@@ -2588,7 +2660,7 @@ ACAV_EXPORT int acav_mi_run_exact(acav_mi *mi, const int64_t *candidates, int64_
                            forced_pos ? mi->forced.as<int>() + it : nullptr,
                            trace_scores ? mi->tr_sc.as<double>() + (size_t)it * (size_t)L : nullptr,
                            trace_argmax ? mi->tr_am.as<int>() + it : nullptr, mi->measure, mi->lnk.as<double>(), mi->lf.as<double>(),
-                           mi->avg, mi->pst.as<PairStat>());
+                           mi->avg, mi->pst.as<PairStat>(), wt ? mi_weights(mi) : nullptr);
     }
     ACAV_HIP_TRY(hipGetLastError());
     ACAV_HIP_TRY(hipMemcpyAsync(S_out, mi->S.p, sizeof(long long) * (size_t)iters, hipMemcpyDeviceToHost, st));
@@ -2646,14 +2718,15 @@ static int launch_select(acav_mi *mi, const int *batch, int B, int k, double *sc
 {
     const int mode = sel_mode(B, mi->P, k);
     const size_t smem = sel_layout(B, mi->P, mi->D, k, mode).total;
+    const auto kernel = mi->weighted ? k_mi_select<true> : k_mi_select<false>;
     if (smem > 48 * 1024)
-        ACAV_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mi_select), hipFuncAttributeMaxDynamicSharedMemorySize,
+        ACAV_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                          (int)smem));
-    hipLaunchKernelGGL(k_mi_select, dim3(1), dim3(256), smem, mi->ctx.stream, mi->asg.as<int>(), mi->D, mi->C, mi->P,
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(256), smem, mi->ctx.stream, mi->asg.as<int>(), mi->D, mi->C, mi->P,
                        mi->pairs.as<int>(), batch, B, k, mode, mi->Nc.as<int>(), mi->ac.as<int>(), mi->bc.as<int>(),
                        mi->SN.as<double>(), mi->Sa.as<double>(), mi->Sb.as<double>(), mi->phi.as<double>(),
                        mi->scalars.as<MiScalars>(), scores_out, S_out, G_out, forced_pos, trace_pos, trace_ids,
-                       trace_scores, keep, requeue_out);
+                       trace_scores, keep, requeue_out, mi_weights(mi));
     ACAV_HIP_TRY(hipGetLastError());
     return ACAV_OK;
 }

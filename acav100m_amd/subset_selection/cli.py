@@ -47,6 +47,8 @@ def prepare(**kwargs):
 
 def run(args):
     """cli.py:90-100"""
+    from .run_greedy import check_weight_type
+    check_weight_type(args.measure_name, args.clustering.weight_type)  # before any shard is read
     if args.measure_name == 'contrastive':
         from .run_contrastive import run_chunks_contrastive, run_single_contrastive
         return run_single_contrastive(args) if args.chunk_size is None else run_chunks_contrastive(args)

@@ -10,6 +10,7 @@ acav100m_amd/csrc/acav_mi.hip.  No CPU path.
 import ctypes as C
 import math
 import time
+import warnings
 
 import numpy as np
 
@@ -32,6 +33,7 @@ def _device_index(device):
 
 class EfficientBatchMI:
     """ this implementation requires the users to use the same ncentroids for all clusterings """
+    _takes_weights = True  # the MI score multiplies by the pair weights; the measures that override it ignore them
 
     def __init__(self, assignments, measure_type='mutual_info', average_method='arithmetic',
                  ncentroids=20, batch_size=1, selection_size=1, device='cpu', keep_unselected=False,
@@ -55,7 +57,18 @@ class EfficientBatchMI:
 
     # ------------------------------------------------------------------ init (mi.py:27-39)
     def init(self, clustering_combinations, candidates):
-        self.combinations = clustering_combinations
+        """clustering_combinations: the pair list, or the reference's weighted form {'pairing': pairs, 'weights': one float
+        per pair} (correspondence_retrieval measures/efficient.py:29-33, pairing.get_cluster_pairing with a weight_type):
+        every pair's score is multiplied by its weight, rounded to fp32, before the mean over the pairs."""
+        self.pair_weights = None
+        if isinstance(clustering_combinations, dict):
+            self.combinations = clustering_combinations['pairing']
+            self.pair_weights = list(clustering_combinations['weights'])
+            if not self._takes_weights:
+                warnings.warn("{} does not weight its pairs (the reference's class overrides _calc_score): the pair weights "
+                              "are ignored".format(type(self).__name__), UserWarning, stacklevel=2)
+        else:
+            self.combinations = clustering_combinations
         self.init_cache()
         self.init_candidates(candidates)
 
@@ -76,6 +89,13 @@ class EfficientBatchMI:
         _lib.check(lib.acav_mi_create(C.byref(h), _device_index(self.device), _lib.ptr(self.assignments), v, d,
                                       self.ncentroids, _lib.ptr(pairs), len(pairs), None))
         self._h = h
+        weights = getattr(self, 'pair_weights', None)
+        if weights is not None and self._takes_weights:
+            # torch.tensor(self.pair_weights).float() (efficient.py:98): float64 -> fp32, round to nearest
+            w32 = np.ascontiguousarray(np.asarray(weights, np.float64).astype(np.float32))
+            if w32.shape != (len(pairs),):
+                raise ValueError("{} pair weights for {} clustering pairs".format(w32.size, len(pairs)))
+            _lib.check(lib.acav_mi_set_pair_weights(h, _lib.ptr(w32), len(pairs)))
 
     def init_candidates(self, candidates):
         self.candidate_ids = np.ascontiguousarray(candidates, dtype=np.int64)

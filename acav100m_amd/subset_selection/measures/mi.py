@@ -88,8 +88,10 @@ class EfficientAMI(EfficientMI):
     (MI - EMI) / max(normaliser - EMI, eps), EMI being the reference's own one-term-per-cell expression (calc_EMI).
     Same kernel as `mi` with the adjusted score (acav_mi_set_measure); float64 over integer counts, within 4e-7 relative of
     the reference's fp32 scores (tests/golden/mi_ami_*.npz).  average_method (generalized_mean, mi.py:201-209): the
-    normaliser is the 'arithmetic' mean (the reference default), the 'max' or the 'min' of the two entropies."""
+    normaliser is the 'arithmetic' mean (the reference default), the 'max' or the 'min' of the two entropies.
+    Pair weights are accepted and ignored, with a warning: the reference's calc_AMI replaces the weighted _calc_score."""
     _measure_id = 1
+    _takes_weights = False
 
     def __init__(self, assignments, measure_type='mutual_info', average_method='arithmetic', ncentroids=20,
                  device='cuda', **kwargs):
@@ -116,6 +118,7 @@ class EfficientNMI(EfficientAMI):
 class ConstantMeasure(EfficientMI):
     """mi.py:274-281: every candidate scores 1, so the exact greedy takes the first remaining candidate every iteration and
     every gain is 1.0 -- the reference's "no measure" control ('constant' here; not in the reference's registry either)."""
+    _takes_weights = False
 
     def init(self, clustering_combinations, candidates):
         super().init(clustering_combinations, candidates)

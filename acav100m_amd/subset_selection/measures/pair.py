@@ -25,6 +25,7 @@ from .mi import EfficientMI
 
 class _PairCountingMeasure(EfficientMI):
     _measure_id = None
+    _takes_weights = False  # the reference's pair-counting classes override _calc_score: pair weights are ignored
 
     def init(self, clustering_combinations, candidates):
         super().init(clustering_combinations, candidates)

@@ -39,7 +39,7 @@ def run_partition(args, shard_paths):
     assignments, clustering_types, shard_names, filenames = io.load_assignment_shards(shard_paths)
     return run_greedy(args, assignments, shard_names, filenames, clustering_types, args.subset.size,
                       args.subset.ratio, measure_name=args.measure_name, cluster_pairing=args.clustering.pairing,
-                      shuffle_candidates=args.shuffle_candidates, verbose=args.verbose)
+                      shuffle_candidates=args.shuffle_candidates, verbose=args.verbose, weight_type=args.clustering.weight_type)
 
 
 def _load(args, path):
@@ -56,7 +56,7 @@ def _select(args, data):
         results.append(run_greedy(args, assignments, shard_names, filenames, clustering_types, args.subset.size,
                                   args.subset.ratio, measure_name=args.measure_name,
                                   cluster_pairing=args.clustering.pairing, shuffle_candidates=args.shuffle_candidates,
-                                  verbose=args.verbose))
+                                  verbose=args.verbose, weight_type=args.clustering.weight_type))
     return results
 
 
@@ -172,7 +172,8 @@ def compare_measures(args):
         runs = {}
         for name in names:
             runs[name] = _run_greedy(args, assignments, clustering_types, args.subset.size, args.subset.ratio, measure_name=name,
-                                     cluster_pairing=args.clustering.pairing, shuffle_candidates=False, verbose=False)
+                                     cluster_pairing=args.clustering.pairing, shuffle_candidates=False, verbose=False,
+                                     weight_type=args.clustering.weight_type)
         keys = list(runs)
         for a in range(len(keys)):
             for b in range(a + 1, len(keys)):
@@ -213,7 +214,8 @@ def _run_chunks_lockstep(args, chunk_args, mine, rank, width):
             measure, start, subset = _prepare(chunk_args, assignments, clustering_types, chunk_args.subset.size,
                                               chunk_args.subset.ratio, chunk_args.measure_name,
                                               chunk_args.clustering.pairing, chunk_args.shuffle_candidates,
-                                              chunk_args.verbose, generator=Generator(base_seed + 1 + num))
+                                              chunk_args.verbose, generator=Generator(base_seed + 1 + num),
+                                              weight_type=chunk_args.clustering.weight_type)
             prepared.append((measure, start, subset, shard_names, filenames, metas))
         return prepared
 

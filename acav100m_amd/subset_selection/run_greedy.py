@@ -7,6 +7,8 @@ Plan of a run (reference run_greedy.py:9-74):
   B, k         = batch.batch_size clamped to V - 1, batch.selection_size clamped to B
   candidates   = 0..V-1, shuffled with Python's `random` when asked; the first one becomes the start index
   measure      = get_measure(name)(...); measure.init(pairs, candidates); measure.run_greedy(...)
+  weight_type  = None, or a layer weighting of the pairs (pairing.get_weights; correspondence_retrieval's weight_type) for
+                 the measures that weight their pairs (WEIGHTED_MEASURES)
 `_prepare` builds everything up to the measure call so that several chunks can be prepared first and then selected
 in lockstep (run.py).
 """
@@ -14,6 +16,16 @@ import numpy as np
 
 from .measures import get_measure
 from .pairing import get_cluster_pairing
+
+# the measures whose score the pair weights scale (correspondence_retrieval: EfficientMI / EfficientMemMI / EfficientBatchMI);
+# the others override the weighted _calc_score there, so a weight_type would be dropped without a word
+WEIGHTED_MEASURES = ('mi', 'mem_mi', 'batch_mi')
+
+
+def check_weight_type(measure_name, weight_type):
+    if weight_type is not None and str(measure_name).lower() not in WEIGHTED_MEASURES:
+        raise ValueError("clustering.weight_type={!r} needs one of the measures {}, not {!r}: the others ignore pair weights"
+                         .format(weight_type, list(WEIGHTED_MEASURES), measure_name))
 
 
 class _Plan:
@@ -35,8 +47,9 @@ class _Plan:
 
 
 def _prepare(args, assignments, clustering_types, subset_size, subset_ratio, measure_name='mi',
-             cluster_pairing='combination', shuffle_candidates=True, verbose=False, generator=None):
+             cluster_pairing='combination', shuffle_candidates=True, verbose=False, generator=None, weight_type=None):
     """-> (measure ready to run, start_indices, subset_size)"""
+    check_weight_type(measure_name, weight_type)
     plan = _Plan(args, assignments, subset_size, subset_ratio)
     if verbose:
         print("extracting {} samples from {} total datapoints".format(plan.subset, plan.rows))
@@ -47,14 +60,14 @@ def _prepare(args, assignments, clustering_types, subset_size, subset_ratio, mea
     measure = get_measure(measure_name)(assignments, **options)
     order = plan.candidate_order(shuffle_candidates)
     head, rest = order[:1], order[1:]  # a singleton start: it seeds the tables, it is never selected (batch.py:205-206)
-    measure.init(get_cluster_pairing(clustering_types, cluster_pairing), rest)
+    measure.init(get_cluster_pairing(clustering_types, cluster_pairing, weight_type), rest)
     return measure, head, plan.subset
 
 
 def _run_greedy(args, assignments, clustering_types, subset_size, subset_ratio, measure_name='mi',
-                cluster_pairing='combination', shuffle_candidates=True, verbose=False):
+                cluster_pairing='combination', shuffle_candidates=True, verbose=False, weight_type=None):
     measure, head, subset = _prepare(args, assignments, clustering_types, subset_size, subset_ratio, measure_name,
-                                     cluster_pairing, shuffle_candidates, verbose)
+                                     cluster_pairing, shuffle_candidates, verbose, weight_type=weight_type)
     picked, gains, seconds, _lookups = measure.run_greedy(subset, head, None, verbose=verbose,
                                                          log_every=args.log_every, log_times=args.log_times,
                                                          node_rank=args.node_rank, pid=args.parent_pid)
@@ -62,8 +75,8 @@ def _run_greedy(args, assignments, clustering_types, subset_size, subset_ratio, 
 
 
 def run_greedy(args, assignments, shard_names, filenames, clustering_types, subset_size, subset_ratio,
-               measure_name='mi', cluster_pairing='combination', shuffle_candidates=True, verbose=False):
+               measure_name='mi', cluster_pairing='combination', shuffle_candidates=True, verbose=False, weight_type=None):
     """-> rows {'filename', 'shard_name'} of the selected clips, ordered by clip index (run_greedy.py:72)"""
     picked, _, _ = _run_greedy(args, assignments, clustering_types, subset_size, subset_ratio, measure_name,
-                               cluster_pairing, shuffle_candidates, verbose)
+                               cluster_pairing, shuffle_candidates, verbose, weight_type=weight_type)
     return [dict(filename=filenames[i], shard_name=shard_names[i]) for i in sorted(picked)]
