@@ -151,6 +151,9 @@ SUBSET_DEFAULTS = {
     'contrastive': {'num_epochs': 3, 'num_warmup_steps': 1, 'base_lr': 2e-4, 'train_batch_size': 128, 'test_batch_size': 128,
                     'cached_epoch': None, 'train_from_cached': False},
     'measure_name': 'batch_mi',
+    # celf_ratio: share of the picks of an exact-greedy measure taken by CELF lazy greedy (correspondence_retrieval args.py:32);
+    #   0 = plain greedy.  batch_mi and contrastive refuse a nonzero value
+    'celf_ratio': 0,
     'shuffle_candidates': True,
     'chunk_size': None,
     'save_cache_as_csvs': True,

@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "acav_common.h"
+#include <rocprim/rocprim.hpp>
 #include <vector>
 
 using namespace acav;
@@ -746,6 +747,484 @@ __global__ __launch_bounds__(256) void k_mi_exact_iter(
             ps[p] = st;
         }
     }
+}
+
+// ------------------------------------------------------------------- CELF lazy greedy (acav_mi_run_celf)
+// correspondence_retrieval/code/measures/efficient.py:140-196 (calc_measure_celf / init_celf_q): a priority queue of stale
+// marginal gains; a pick re-scores the head until the head stays on top.  Canonical order (DESIGN.md "CELF"): the queue is
+// totally ordered by (value descending, stamp descending); an entry never re-scored carries the stamp -(original position),
+// an entry re-scored at the run's t-th lookup the stamp t; NaN ranks above every number.  Under it a pick walks the STALE
+// entries s_1, s_2, ... in queue order, re-scoring each (d_k), and stops at the first k at which the best re-scored value
+// (ties: the later one) is >= the next stale value; that entry is accepted, after one more lookup of it (same value)
+// unless it is s_k itself.  The tables do not change within a pick, so the d_k of a batch of stale entries are computed in
+// parallel and the walk is replayed over them.
+// Layout: value / stamp / removed by original position; per block of `bs` positions the two largest stale keys (global,
+// kept current from pick to pick).  One workgroup per pick: it stages the block keys in LDS, extracts the next stale
+// entries in order from them (a block gives its first and second key; a block that gave both is an upper BOUND until it is
+// rescanned), scores them lanes-over-pairs, replays, and rescans the blocks it consumed from.
+struct CelfCtx {
+    const int *asg;
+    int D, C, P;
+    const int *pairs;
+    int *Nc, *ac, *bc;
+    double *SN, *Sa, *Sb;
+    const double *phi;
+    MiScalars *sc;
+    int measure;
+    const double *lnk, *lf;
+    int avg;
+    PairStat *ps;
+    const float *pw;
+};
+struct CelfState {
+    double gain;   // EfficientMI.gain: the accumulated gain of the CELF phase
+    long long t;   // lookups of the run so far
+};
+constexpr int CELF_NBMAX = 1024;  // block keys staged in LDS; the block size grows with L beyond 256 * CELF_NBMAX positions
+constexpr int CELF_MMAX = 64;     // widest batch of speculatively scored entries
+constexpr int CELF_PCH = 32;      // pairs scored per pass (LDS: CELF_MMAX * CELF_PCH doubles)
+constexpr long long CELF_ALL = 0x7fffffffffffffffLL;
+
+// the score of k_mi_exact_iter's pair_score / pair_mean, for the same template arguments
+template <bool PAIR, bool W>
+__device__ __forceinline__ double celf_pair_score(const CelfCtx &c, int p, int id, long long n)
+{
+    if constexpr (PAIR) {
+        return pair_count_score(c.asg, c.D, c.C, p, c.pairs, id, c.Nc, c.ac, c.bc, c.ps, n, c.measure);
+    } else if constexpr (W) {
+        return mi_pair_score(c.asg, c.D, c.C, p, c.pairs, id, c.Nc, c.ac, c.bc, c.SN, c.Sa, c.Sb, c.phi, n) * (double)c.pw[p];
+    } else {
+        if (c.measure == 1)
+            return ami_pair_score(c.asg, c.D, c.C, p, c.pairs, id, c.Nc, c.ac, c.bc, c.SN, c.Sa, c.Sb, c.phi, c.lnk, c.lf, n, c.avg);
+        if (c.measure == 2)
+            return nmi_pair_score(c.asg, c.D, c.C, p, c.pairs, id, c.Nc, c.ac, c.bc, c.SN, c.Sa, c.Sb, c.phi, c.lnk, n, c.avg);
+        if (c.measure == 3) return 1.0;
+        return mi_pair_score(c.asg, c.D, c.C, p, c.pairs, id, c.Nc, c.ac, c.bc, c.SN, c.Sa, c.Sb, c.phi, n);
+    }
+}
+template <bool PAIR>
+__device__ __forceinline__ double celf_pair_mean(const CelfCtx &c, double tot, long long n)
+{
+    if constexpr (PAIR)
+        if (c.measure == 5) return tot / ((double)c.P * (double)(n * (n + 1) / 2));
+    return tot / (double)c.P;
+}
+
+// queue order: key (va, sa) sorts before key (vb, sb)
+__device__ __forceinline__ bool celf_key_gt(double va, long long sa, double vb, long long sb)
+{
+    const bool an = va != va, bn = vb != vb;
+    if (an || bn) return an && bn ? sa > sb : an;
+    return va > vb || (va == vb && sa > sb);
+}
+// value a ranks at least as high as value b (NaN above every number)
+__device__ __forceinline__ bool celf_val_geq(double a, double b)
+{
+    if (a != a) return true;
+    if (b != b) return false;
+    return a >= b;
+}
+
+struct CelfTop2 {
+    double v1, v2;
+    long long s1, s2;
+    int p1, p2;  // -1: none
+};
+__device__ __forceinline__ void celf_top2_insert(CelfTop2 &t, double v, long long s, int p)
+{
+    if (p < 0) return;
+    if (t.p1 < 0 || celf_key_gt(v, s, t.v1, t.s1)) {
+        t.v2 = t.v1, t.s2 = t.s1, t.p2 = t.p1;
+        t.v1 = v, t.s1 = s, t.p1 = p;
+    } else if (t.p2 < 0 || celf_key_gt(v, s, t.v2, t.s2)) {
+        t.v2 = v, t.s2 = s, t.p2 = p;
+    }
+}
+// one wave: the two largest keys among the entries of block b that are alive and not fresher than `tmax`; every lane returns them
+__device__ __forceinline__ CelfTop2 celf_block_top2(int b, int bs, int L, const unsigned char *removed, const double *qval,
+                                                    const long long *qst, long long tmax)
+{
+    const int lane = threadIdx.x & 63;
+    const long long lo = (long long)b * bs;
+    const long long hi = lo + bs < (long long)L ? lo + bs : (long long)L;
+    CelfTop2 t{0.0, 0.0, 0, 0, -1, -1};
+    for (long long w = lo + lane; w < hi; w += 64) {
+        if (removed[w]) continue;
+        const long long s = qst[w];
+        if (s > tmax) continue;
+        celf_top2_insert(t, qval[w], s, (int)w);
+    }
+#pragma unroll
+    for (int dlt = 1; dlt < 64; dlt <<= 1) {
+        const double ov1 = __shfl_xor(t.v1, dlt), ov2 = __shfl_xor(t.v2, dlt);
+        const long long os1 = __shfl_xor(t.s1, dlt), os2 = __shfl_xor(t.s2, dlt);
+        const int op1 = __shfl_xor(t.p1, dlt), op2 = __shfl_xor(t.p2, dlt);
+        celf_top2_insert(t, ov1, os1, op1);
+        celf_top2_insert(t, ov2, os2, op2);
+    }
+    return t;
+}
+
+// update_cache_celf (efficient.py:188-196): the accepted clip joins the tables, as k_mi_exact_iter's tail does (one workgroup)
+template <bool PAIR>
+__device__ __forceinline__ void celf_commit_tables(const CelfCtx &c, int id, int tid)
+{
+    for (int p = tid; p < c.P; p += 256) {
+        const int *row = c.asg + (size_t)id * c.D;
+        const int i = row[c.pairs[2 * p]], j = row[c.pairs[2 * p + 1]];
+        const size_t cell = ((size_t)p * c.C + i) * c.C + j;
+        const int cN = c.Nc[cell], ca = c.ac[(size_t)p * c.C + j], cb = c.bc[(size_t)p * c.C + i];
+        PairStat st{};
+        if constexpr (PAIR) st = c.ps[p];
+        c.Nc[cell] = cN + 1;
+        c.ac[(size_t)p * c.C + j] = ca + 1;
+        c.bc[(size_t)p * c.C + i] = cb + 1;
+        c.SN[p] = c.SN[p] - c.phi[cN] + c.phi[cN + 1];
+        c.Sa[p] = c.Sa[p] - c.phi[ca] + c.phi[ca + 1];
+        c.Sb[p] = c.Sb[p] - c.phi[cb] + c.phi[cb + 1];
+        if constexpr (PAIR) {
+            st.tab += cN, st.ta += ca, st.tb += cb;
+            st.rtp = st.tab ? 0 : st.rtp + 1;
+            st.rfp = st.ta - st.tab ? 0 : st.rfp + (ca == 0 ? c.C - 1 : 0);
+            st.rfn = st.tb - st.tab ? 0 : st.rfn + (cb == 0 ? c.C - 1 : 0);
+            c.ps[p] = st;
+        }
+    }
+}
+
+// init_celf_q (efficient.py:169-175): Q_val = the absolute scores of tables + candidate for every remaining candidate,
+// stamp -(position); gain = the last greedy GAIN (prev), or 0
+template <bool PAIR, bool W>
+__global__ __launch_bounds__(256) void k_celf_init(CelfCtx c, const int *__restrict__ A, int L,
+                                                   const unsigned char *__restrict__ removed, double *__restrict__ qval,
+                                                   long long *__restrict__ qst, CelfState *__restrict__ state,
+                                                   const double *__restrict__ prev)
+{
+    const int w = blockIdx.x * 256 + threadIdx.x;
+    const long long nc = c.sc->nc;
+    if (w == 0) {
+        state->gain = prev ? *prev : 0.0;
+        state->t = 0;
+    }
+    if (w >= L) return;
+    qst[w] = -(long long)w;
+    if (removed[w]) return;
+    const int id = A[w];
+    double tot = 0.0;
+    for (int p = 0; p < c.P; ++p) tot = tot + celf_pair_score<PAIR, W>(c, p, id, nc);
+    qval[w] = celf_pair_mean<PAIR>(c, tot, nc);
+}
+
+// the block keys of every block (one wave per block)
+__global__ __launch_bounds__(256) void k_celf_blocks(int L, int bs, int nb, const unsigned char *__restrict__ removed,
+                                                     const double *__restrict__ qval, const long long *__restrict__ qst,
+                                                     double *__restrict__ bv, long long *__restrict__ bst, int *__restrict__ bp)
+{
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= nb) return;
+    const CelfTop2 t = celf_block_top2(b, bs, L, removed, qval, qst, CELF_ALL);
+    if ((threadIdx.x & 63) == 0) {
+        bv[b] = t.v1, bst[b] = t.s1, bp[b] = t.p1;
+        bv[nb + b] = t.v2, bst[nb + b] = t.s2, bp[nb + b] = t.p2;
+    }
+}
+
+// one CELF pick (one workgroup).  bv / bst / bp: [2][nb] first and second key of every block.  M: widest batch.
+template <bool PAIR, bool W>
+__global__ __launch_bounds__(256) void k_celf_pick(CelfCtx c, const int *__restrict__ A, int L, int bs, int nb,
+                                                   unsigned char *removed, double *qval, long long *qst, double *bv,
+                                                   long long *bst, int *bp, CelfState *state, int M,
+                                                   long long *__restrict__ S_out, double *__restrict__ G_out,
+                                                   long long *__restrict__ LK_out, long long *__restrict__ tr_ids,
+                                                   double *__restrict__ tr_vals, int tr_cap)
+{
+    __shared__ double kv[2][CELF_NBMAX];
+    __shared__ long long ks[2][CELF_NBMAX];
+    __shared__ int kp[2][CELF_NBMAX];
+    __shared__ unsigned char kstate[CELF_NBMAX], touched[CELF_NBMAX];  // kstate: keys of the block already extracted (0..2)
+    __shared__ double sc[CELF_MMAX * CELF_PCH];
+    __shared__ double eV[CELF_MMAX], eD[CELF_MMAX];  // stale value, fresh value of the batch's entries
+    __shared__ int eP[CELF_MMAX], eB[CELF_MMAX];     // their position and block
+    __shared__ double rV[4];
+    __shared__ long long rS[4];
+    __shared__ int rB[4], rK[4];
+    __shared__ double sNextV, sBestV;
+    __shared__ int sNextKind, sDone, sBestP, sBestLast, sWin;
+    __shared__ long long sT, sK;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long nc = c.sc->nc;
+    const double gain0 = state->gain;
+    const long long t0 = state->t;
+    for (int b = tid; b < nb; b += 256) {
+        kv[0][b] = bv[b], ks[0][b] = bst[b], kp[0][b] = bp[b];
+        kv[1][b] = bv[nb + b], ks[1][b] = bst[nb + b], kp[1][b] = bp[nb + b];
+        kstate[b] = 0, touched[b] = 0;
+    }
+    if (tid == 0) sBestP = -1, sBestV = 0.0, sBestLast = 0, sT = t0, sK = 0, sDone = 0, sWin = -1;
+    __syncthreads();
+    for (int round = 0;; ++round) {
+        const int mr = min(M, 8 << min(round, 3));
+        // ---- the next stale entries in queue order, and what follows them (1 = its exact value, 2 = an upper bound, 0 = nothing)
+        int m = 0;
+        for (int j = 0; j <= mr; ++j) {
+            double v = 0.0;
+            long long s = 0;
+            int bb = -1, known = 0;
+            for (int b = tid; b < nb; b += 256) {
+                const int st = kstate[b];
+                const int q = st < 2 ? st : 1;
+                if (kp[q][b] < 0) continue;
+                if (bb < 0 || celf_key_gt(kv[q][b], ks[q][b], v, s)) v = kv[q][b], s = ks[q][b], bb = b, known = st < 2;
+            }
+#pragma unroll
+            for (int dlt = 1; dlt < 64; dlt <<= 1) {
+                const double ov = __shfl_xor(v, dlt);
+                const long long os = __shfl_xor(s, dlt);
+                const int ob = __shfl_xor(bb, dlt), ok = __shfl_xor(known, dlt);
+                if (ob >= 0 && (bb < 0 || celf_key_gt(ov, os, v, s))) v = ov, s = os, bb = ob, known = ok;
+            }
+            if (lane == 0) rV[wave] = v, rS[wave] = s, rB[wave] = bb, rK[wave] = known;
+            __syncthreads();
+            v = rV[0], s = rS[0], bb = rB[0], known = rK[0];
+            for (int q = 1; q < 4; ++q)
+                if (rB[q] >= 0 && (bb < 0 || celf_key_gt(rV[q], rS[q], v, s))) v = rV[q], s = rS[q], bb = rB[q], known = rK[q];
+            m = j;
+            if (j == mr || bb < 0 || !known) {  // uniform
+                if (tid == 0) sNextV = v, sNextKind = bb < 0 ? 0 : known ? 1 : 2;
+                __syncthreads();
+                break;
+            }
+            if (tid == 0) {
+                const int st = kstate[bb];
+                eP[j] = kp[st][bb], eV[j] = v, eB[j] = bb;
+                kstate[bb] = (unsigned char)(st + 1);
+            }
+            __syncthreads();
+        }
+        // ---- fresh values of the m entries: lanes over (entry, pair), summed over the pairs in order
+        double tot = 0.0;
+        for (int pc = 0; pc < c.P; pc += CELF_PCH) {
+            const int np = min(CELF_PCH, c.P - pc);
+            for (int q = tid; q < m * np; q += 256) {
+                const int j = q / np, p = q - j * np;
+                sc[j * CELF_PCH + p] = celf_pair_score<PAIR, W>(c, pc + p, A[eP[j]], nc);
+            }
+            __syncthreads();
+            if (tid < m)
+                for (int p = 0; p < np; ++p) tot = tot + sc[tid * CELF_PCH + p];
+            __syncthreads();
+        }
+        if (tid < m) eD[tid] = celf_pair_mean<PAIR>(c, tot, nc) - gain0;
+        __syncthreads();
+        // ---- the sequential walk over the batch
+        if (tid == 0) {
+            long long t = sT, k = sK;
+            double bestV = sBestV;
+            int bestP = sBestP, bestLast = sBestLast, done = 0;
+            if (bestP >= 0) {  // the walk of the last round ended undecided: its best against what follows, now known
+                const int kind = m > 0 ? 1 : sNextKind;
+                const double nv = m > 0 ? eV[0] : sNextV;
+                if (kind == 0 || celf_val_geq(bestV, nv)) done = 1;
+            }
+            for (int j = 0; j < m && !done; ++j) {
+                const int pos = eP[j];
+                const double d = eD[j];
+                ++t;
+                if (k < tr_cap) {
+                    if (tr_ids) tr_ids[k] = (long long)A[pos];
+                    if (tr_vals) tr_vals[k] = d;
+                }
+                ++k;
+                qval[pos] = d, qst[pos] = t;
+                touched[eB[j]] = 1;
+                if (bestP < 0 || celf_val_geq(d, bestV)) bestV = d, bestP = pos, bestLast = 1;
+                else bestLast = 0;
+                const int kind = j + 1 < m ? 1 : sNextKind;
+                const double nv = j + 1 < m ? eV[j + 1] : sNextV;
+                if (kind == 0 || celf_val_geq(bestV, nv)) done = 1;  // against a bound: >= the bound is >= what it bounds
+            }
+            if (done) {
+                if (!bestLast) {  // the accepted entry is back at the head: one more lookup, the same value
+                    ++t;
+                    if (k < tr_cap) {
+                        if (tr_ids) tr_ids[k] = (long long)A[bestP];
+                        if (tr_vals) tr_vals[k] = bestV;
+                    }
+                    ++k;
+                }
+                removed[bestP] = 1;
+                state->gain = gain0 + bestV;
+                state->t = t;
+                *S_out = (long long)A[bestP];
+                *G_out = gain0 + bestV;
+                *LK_out = k;
+                c.sc->nc = nc + 1;
+                sWin = bestP;
+            }
+            sT = t, sK = k, sBestV = bestV, sBestP = bestP, sBestLast = bestLast, sDone = done;
+        }
+        __syncthreads();
+        if (sDone) break;  // uniform
+        // ---- every entry of the batch is fresh now: the stale keys of the blocks they came from
+        for (int j = wave; j < m; j += 4) {
+            const int b = eB[j];
+            const CelfTop2 t2 = celf_block_top2(b, bs, L, removed, qval, qst, t0);
+            if (lane == 0) {
+                kv[0][b] = t2.v1, ks[0][b] = t2.s1, kp[0][b] = t2.p1;
+                kv[1][b] = t2.v2, ks[1][b] = t2.s2, kp[1][b] = t2.p2;
+                kstate[b] = 0;
+            }
+        }
+        __syncthreads();
+    }
+    // ---- the keys of the next pick: every block that lost or changed an entry (all entries are stale again)
+    for (int b = wave; b < nb; b += 4) {
+        if (!touched[b]) continue;  // uniform within the wave
+        const CelfTop2 t2 = celf_block_top2(b, bs, L, removed, qval, qst, CELF_ALL);
+        if (lane == 0) {
+            bv[b] = t2.v1, bst[b] = t2.s1, bp[b] = t2.p1;
+            bv[nb + b] = t2.v2, bst[nb + b] = t2.s2, bp[nb + b] = t2.p2;
+        }
+    }
+    celf_commit_tables<PAIR>(c, A[sWin], tid);
+}
+
+// ---- the dense form of a pick (a pick that re-scores most of the queue: the first one after the queue was filled against
+// a gain).  The same walk, evaluated for the WHOLE queue at once: fresh values of every stale entry in one dense launch
+// (k_celf_dense_prep), the queue order from two stable device-wide radix sorts of the old keys (stamp, then value), the
+// running best fresh value as an inclusive max-scan along that order (pm), the stopping point as the one rank r where
+// pm_r >= v_(r+1) first holds (both sides are monotone in r), the accepted entry as the last rank <= r that attains pm_r.
+struct CelfDense {
+    int kstop;   // lookups of the walk (entries re-scored), >= 1
+    int winner;  // rank of the accepted entry
+};
+// order-preserving 64-bit key of a queue value: NaN above every number, -0 = +0; 0 is below every value (removed entries)
+__device__ __forceinline__ unsigned long long celf_value_key(double v)
+{
+    if (v != v) return 0xffffffffffffffffULL;
+    v = v + 0.0;
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    const unsigned long long k = (b >> 63) ? ~b : (b | 0x8000000000000000ULL);
+    return k == 0xffffffffffffffffULL ? k - 1 : k;
+}
+struct CelfMaxOp {  // the better of two fresh values in walk order: the later one on a tie
+    __device__ __forceinline__ double operator()(const double &a, const double &b) const { return celf_val_geq(b, a) ? b : a; }
+};
+
+template <bool PAIR, bool W>
+__global__ __launch_bounds__(256) void k_celf_dense_prep(CelfCtx c, const int *__restrict__ A, int L,
+                                                         const unsigned char *__restrict__ removed,
+                                                         const long long *__restrict__ qst, const CelfState *__restrict__ state,
+                                                         double *__restrict__ fresh, long long *__restrict__ key_stamp,
+                                                         int *__restrict__ idx, CelfDense *__restrict__ dn)
+{
+    const int w = blockIdx.x * 256 + threadIdx.x;
+    if (w == 0) dn->kstop = 0, dn->winner = -1;
+    if (w >= L) return;
+    idx[w] = w;
+    if (removed[w]) {
+        key_stamp[w] = (long long)0x8000000000000000ULL;  // below every stamp: removed entries sort last
+        return;
+    }
+    key_stamp[w] = qst[w];
+    const long long nc = c.sc->nc;
+    const int id = A[w];
+    double tot = 0.0;
+    for (int p = 0; p < c.P; ++p) tot = tot + celf_pair_score<PAIR, W>(c, p, id, nc);
+    fresh[w] = celf_pair_mean<PAIR>(c, tot, nc) - state->gain;
+}
+__global__ __launch_bounds__(256) void k_celf_dense_valkey(int L, const int *__restrict__ idx, const unsigned char *__restrict__ removed,
+                                                           const double *__restrict__ qval, unsigned long long *__restrict__ key)
+{
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= L) return;
+    const int w = idx[r];
+    key[r] = removed[w] ? 0ULL : celf_value_key(qval[w]);
+}
+__global__ __launch_bounds__(256) void k_celf_dense_gather(int n, const int *__restrict__ order, const double *__restrict__ fresh,
+                                                           double *__restrict__ d)
+{
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r < n) d[r] = fresh[order[r]];
+}
+// the stopping rank: pred(r) = pm_r >= v_(r+1) (true at the last rank); exactly one r has pred(r) and not pred(r - 1)
+__global__ __launch_bounds__(256) void k_celf_dense_stop(int n, const int *__restrict__ order, const double *__restrict__ qval,
+                                                         const double *__restrict__ pm, CelfDense *__restrict__ dn)
+{
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= n) return;
+    const bool here = r == n - 1 || celf_val_geq(pm[r], qval[order[r + 1]]);
+    const bool before = r > 0 && celf_val_geq(pm[r - 1], qval[order[r]]);
+    if (here && !before) dn->kstop = r + 1;
+}
+__global__ __launch_bounds__(256) void k_celf_dense_winner(int n, const double *__restrict__ d, const double *__restrict__ pm,
+                                                           CelfDense *__restrict__ dn)
+{
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    const int k = dn->kstop;
+    if (r >= k) return;
+    const double best = pm[k - 1], v = d[r];
+    if ((v != v && best != best) || v == best) atomicMax(&dn->winner, r);
+}
+// the re-scored entries take their fresh values and stamps (old values are not needed any more), and the lookup traces
+__global__ __launch_bounds__(256) void k_celf_dense_apply(int n, const int *__restrict__ A, const int *__restrict__ order,
+                                                          const double *__restrict__ d, const CelfDense *__restrict__ dn,
+                                                          const CelfState *__restrict__ state, double *__restrict__ qval,
+                                                          long long *__restrict__ qst, long long *__restrict__ tr_ids,
+                                                          double *__restrict__ tr_vals, int tr_cap)
+{
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= dn->kstop) return;
+    const int w = order[r];
+    qval[w] = d[r];
+    qst[w] = state->t + r + 1;
+    if (r < tr_cap) {
+        if (tr_ids) tr_ids[r] = (long long)A[w];
+        if (tr_vals) tr_vals[r] = d[r];
+    }
+}
+// acceptance: one more lookup of the accepted entry unless it was the last one re-scored; outputs, state, tables
+template <bool PAIR>
+__global__ __launch_bounds__(256) void k_celf_dense_commit(CelfCtx c, const int *__restrict__ A, const int *__restrict__ order,
+                                                           const double *__restrict__ d, const CelfDense *__restrict__ dn,
+                                                           CelfState *state, unsigned char *removed,
+                                                           long long *__restrict__ S_out, double *__restrict__ G_out,
+                                                           long long *__restrict__ LK_out, long long *__restrict__ tr_ids,
+                                                           double *__restrict__ tr_vals, int tr_cap)
+{
+    const int tid = threadIdx.x;
+    const int k = dn->kstop, a = dn->winner;
+    const int pos = order[a];
+    const long long nc = c.sc->nc;
+    const double gain0 = state->gain;
+    const long long t0 = state->t;
+    __syncthreads();
+    if (tid == 0) {
+        long long lk = k;
+        if (a != k - 1) {
+            if (k < tr_cap) {
+                if (tr_ids) tr_ids[k] = (long long)A[pos];
+                if (tr_vals) tr_vals[k] = d[a];
+            }
+            ++lk;
+        }
+        removed[pos] = 1;
+        state->gain = gain0 + d[a];
+        state->t = t0 + lk;
+        *S_out = (long long)A[pos];
+        *G_out = gain0 + d[a];
+        *LK_out = lk;
+        c.sc->nc = nc + 1;
+    }
+    celf_commit_tables<PAIR>(c, A[pos], tid);
+}
+
+// queue values by original position at the end of a run (-inf: the entry has left the queue)
+__global__ void k_celf_queue_out(int L, const unsigned char *__restrict__ removed, const double *__restrict__ qval,
+                                 double *__restrict__ out)
+{
+    const int w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w < L) out[w] = removed[w] ? -INFINITY : qval[w];
 }
 
 // ------------------------------------------------------------------------------ MT19937
@@ -1584,6 +2063,8 @@ struct acav_mi {
     // greedy buffers
     DevBuf A0, A1, draws, draws2, h, head, head2, next, g, g2, mt, batch, S, G, tr_pos, tr_ids, tr_sc, forced;
     DevBuf removed, blockbest, ticket, tr_am;  // exact greedy
+    DevBuf celf_val, celf_stamp, celf_bv, celf_bst, celf_bp, celf_state, celf_lk, celf_qout;  // CELF queue (acav_mi_run_celf)
+    DevBuf celf_fresh, celf_ks, celf_ks2, celf_kv, celf_kv2, celf_i0, celf_i1, celf_i2, celf_d, celf_pm, celf_dn, celf_tmp;  // its dense pick
     DevBuf chunk_desc;                         // descriptor array of a multi-chunk run (lead handle)
     DevBuf lane_states, ring, polys;           // MT19937 lanes of the single-chunk greedy (MtStream)
     DevBuf lnk, lf;   // ln k and ln k! tables of the `ami` score (acav_mi_set_measure)
@@ -2676,6 +3157,208 @@ ACAV_EXPORT int acav_mi_run_exact(acav_mi *mi, const int64_t *candidates, int64_
     ACAV_HIP_TRY(hipStreamSynchronize(st));
     if (trace_argmax)
         for (int64_t i = 0; i < iters; ++i) trace_argmax[i] = am[(size_t)i];
+    return ACAV_OK;
+}
+
+// EfficientMI.run(subset_size, start_indices, intermediate_target, celf_ratio) of the correspondence_retrieval stage
+// (efficient.py:240-299): the exact greedy for the first round(niters * (1 - celf_ratio)) picks, CELF for the rest
+ACAV_EXPORT int acav_mi_run_celf(acav_mi *mi, const int64_t *candidates, int64_t L, int ns, int64_t subset, double celf_ratio,
+                                 int64_t *S_out, double *GAIN_out, int64_t *LOOKUPS_out, int64_t *n_selected,
+                                 int64_t trace_cap, int64_t *trace_ids, double *trace_vals, double *queue_final)
+{
+    ACAV_REQUIRE(mi && candidates && S_out && GAIN_out && LOOKUPS_out && n_selected, ACAV_EINVAL, "NULL argument");
+    ACAV_REQUIRE(L > 0 && L < 0x7fffffff && ns >= 0, ACAV_EINVAL, "bad candidate count %lld", (long long)L);
+    ACAV_REQUIRE(celf_ratio >= 0.0 && celf_ratio <= 1.0, ACAV_EINVAL, "invalid celf_ratio %g", celf_ratio);
+    ACAV_REQUIRE(trace_cap >= 0 && trace_cap < 0x7fffffff && (trace_cap > 0 || (!trace_ids && !trace_vals)), ACAV_EINVAL,
+                 "bad trace capacity");
+    ACAV_HIP_TRY(hipSetDevice(mi->ctx.device));
+    hipStream_t st = mi->ctx.stream;
+    int64_t iters = subset - 1 - ns;
+    if (iters < 0) iters = 0;
+    if (iters > L) iters = L;
+    *n_selected = iters;
+    if (iters == 0) return ACAV_OK;
+    for (int64_t i = 0; i < L; ++i)
+        ACAV_REQUIRE(candidates[i] >= 0 && candidates[i] < mi->V, ACAV_EINVAL, "candidate id %lld outside [0, %lld)",
+                     (long long)candidates[i], (long long)mi->V);
+    // round() of the reference is Python's: half to even, on the same double product
+    int64_t greedy = (int64_t)std::nearbyint((double)iters * (1.0 - celf_ratio));
+    if (greedy < 0) greedy = 0;
+    if (greedy > iters) greedy = iters;
+    const int64_t celf = iters - greedy;
+    int M = 32;  // widest speculative batch; ACAV_CELF_M narrows or widens it (tests: the result does not depend on it)
+    if (const char *e = getenv("ACAV_CELF_M")) M = atoi(e);
+    M = M < 1 ? 1 : M > CELF_MMAX ? CELF_MMAX : M;
+    const unsigned grid = (unsigned)((L + 255) / 256);
+    const int bs = 256 * (int)((L + 256LL * CELF_NBMAX - 1) / (256LL * CELF_NBMAX));
+    const int nb = (int)((L + bs - 1) / bs);
+    ACAV_TRY(mi->A0.ensure(sizeof(int) * (size_t)L));
+    ACAV_TRY(ids_to_device32(mi, candidates, L, mi->stage, mi->A0));
+    ACAV_TRY(mi->removed.ensure((size_t)L));
+    ACAV_TRY(mi->blockbest.ensure(sizeof(ExactBest) * grid));
+    ACAV_TRY(mi->ticket.ensure(sizeof(unsigned)));
+    ACAV_TRY(mi->S.ensure(sizeof(long long) * (size_t)iters));
+    ACAV_TRY(mi->G.ensure(sizeof(double) * (size_t)iters));
+    ACAV_HIP_TRY(hipMemsetAsync(mi->removed.p, 0, (size_t)L, st));
+    ACAV_HIP_TRY(hipMemsetAsync(mi->ticket.p, 0, sizeof(unsigned), st));
+    if (mi->measure < 4) mi->pst_valid = false;
+    if (mi->measure >= 4) {
+        if (mi->measure != 6) {
+            MiScalars s{};
+            ACAV_HIP_TRY(hipMemcpyAsync(&s, mi->scalars.p, sizeof(s), hipMemcpyDeviceToHost, st));
+            ACAV_HIP_TRY(hipStreamSynchronize(st));
+            ACAV_REQUIRE(s.nc >= 1, ACAV_EINVAL, "fm / rand: the tables hold no sample -- add the start clips first "
+                         "(the reference's pair-count check fails on an empty start)");
+        }
+        ACAV_TRY(pair_stats_init(mi));
+    }
+    const bool pair = mi->measure >= 4;
+    const bool wt = mi->weighted && mi->measure == 0;
+    const auto exact_kernel = pair ? k_mi_exact_iter<true> : wt ? k_mi_exact_iter<false, true> : k_mi_exact_iter<false>;
+    for (int64_t it = 0; it < greedy; ++it) {
+        hipLaunchKernelGGL(exact_kernel, dim3(grid), dim3(256), 0, st, mi->asg.as<int>(), mi->D, mi->C, mi->P,
+                           mi->pairs.as<int>(), mi->A0.as<int>(), (int)L, mi->removed.as<unsigned char>(), mi->Nc.as<int>(),
+                           mi->ac.as<int>(), mi->bc.as<int>(), mi->SN.as<double>(), mi->Sa.as<double>(), mi->Sb.as<double>(),
+                           mi->phi.as<double>(), mi->scalars.as<MiScalars>(), mi->blockbest.as<ExactBest>(),
+                           mi->ticket.as<unsigned>(), mi->S.as<long long>() + it, mi->G.as<double>() + it, nullptr, nullptr,
+                           nullptr, mi->measure, mi->lnk.as<double>(), mi->lf.as<double>(), mi->avg, mi->pst.as<PairStat>(),
+                           wt ? mi_weights(mi) : nullptr);
+    }
+    ACAV_HIP_TRY(hipGetLastError());
+    const size_t cap = (size_t)trace_cap;
+    if (celf > 0) {
+        ACAV_TRY(mi->celf_val.ensure(sizeof(double) * (size_t)L));
+        ACAV_TRY(mi->celf_stamp.ensure(sizeof(long long) * (size_t)L));
+        ACAV_TRY(mi->celf_bv.ensure(sizeof(double) * 2 * (size_t)nb));
+        ACAV_TRY(mi->celf_bst.ensure(sizeof(long long) * 2 * (size_t)nb));
+        ACAV_TRY(mi->celf_bp.ensure(sizeof(int) * 2 * (size_t)nb));
+        ACAV_TRY(mi->celf_state.ensure(sizeof(CelfState)));
+        ACAV_TRY(mi->celf_lk.ensure(sizeof(long long) * (size_t)celf));
+        if (trace_ids) {
+            ACAV_TRY(mi->tr_ids.ensure(sizeof(long long) * (size_t)celf * cap));
+            ACAV_HIP_TRY(hipMemsetAsync(mi->tr_ids.p, 0xFF, sizeof(long long) * (size_t)celf * cap, st));  // -1
+        }
+        if (trace_vals) {
+            ACAV_TRY(mi->tr_sc.ensure(sizeof(double) * (size_t)celf * cap));
+            ACAV_HIP_TRY(hipMemsetAsync(mi->tr_sc.p, 0xFF, sizeof(double) * (size_t)celf * cap, st));  // NaN
+        }
+        const CelfCtx cx{mi->asg.as<int>(), mi->D, mi->C, mi->P, mi->pairs.as<int>(), mi->Nc.as<int>(), mi->ac.as<int>(),
+                         mi->bc.as<int>(), mi->SN.as<double>(), mi->Sa.as<double>(), mi->Sb.as<double>(), mi->phi.as<double>(),
+                         mi->scalars.as<MiScalars>(), mi->measure, mi->lnk.as<double>(), mi->lf.as<double>(), mi->avg,
+                         mi->pst.as<PairStat>(), wt ? mi_weights(mi) : nullptr};
+        const auto init_kernel = pair ? k_celf_init<true, false> : wt ? k_celf_init<false, true> : k_celf_init<false, false>;
+        const auto pick_kernel = pair ? k_celf_pick<true, false> : wt ? k_celf_pick<false, true> : k_celf_pick<false, false>;
+        hipLaunchKernelGGL(init_kernel, dim3(grid), dim3(256), 0, st, cx, mi->A0.as<int>(), (int)L,
+                           mi->removed.as<unsigned char>(), mi->celf_val.as<double>(), mi->celf_stamp.as<long long>(),
+                           mi->celf_state.as<CelfState>(), greedy > 0 ? mi->G.as<double>() + (greedy - 1) : nullptr);
+        hipLaunchKernelGGL(k_celf_blocks, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, st, (int)L, bs, nb,
+                           mi->removed.as<unsigned char>(), mi->celf_val.as<double>(), mi->celf_stamp.as<long long>(),
+                           mi->celf_bv.as<double>(), mi->celf_bst.as<long long>(), mi->celf_bp.as<int>());
+        // the pick that re-scores (nearly) the whole queue takes the dense form: the first one when the queue was filled against a
+        // gain (absolute scores exceed gains), the second one otherwise (the first accepts the largest absolute score at once).
+        // Both forms are the same walk, so the choice changes no result: ACAV_CELF_DENSE=0 never, =all every pick (tests)
+        int64_t dense_at = greedy > 0 ? 0 : 1;
+        bool dense_all = false;
+        if (const char *e = getenv("ACAV_CELF_DENSE")) {
+            if (e[0] == '0') dense_at = -1;
+            if (e[0] == 'a') dense_all = true;
+        }
+        const auto prep_kernel = pair ? k_celf_dense_prep<true, false> : wt ? k_celf_dense_prep<false, true> : k_celf_dense_prep<false, false>;
+        const auto commit_kernel = pair ? k_celf_dense_commit<true> : k_celf_dense_commit<false>;
+        size_t tmp_bytes = 0;
+        if (dense_all || (dense_at >= 0 && dense_at < celf)) {
+            const size_t n = (size_t)L;
+            ACAV_TRY(mi->celf_fresh.ensure(8 * n));
+            ACAV_TRY(mi->celf_ks.ensure(8 * n));
+            ACAV_TRY(mi->celf_ks2.ensure(8 * n));
+            ACAV_TRY(mi->celf_kv.ensure(8 * n));
+            ACAV_TRY(mi->celf_kv2.ensure(8 * n));
+            ACAV_TRY(mi->celf_i0.ensure(4 * n));
+            ACAV_TRY(mi->celf_i1.ensure(4 * n));
+            ACAV_TRY(mi->celf_i2.ensure(4 * n));
+            ACAV_TRY(mi->celf_d.ensure(8 * n));
+            ACAV_TRY(mi->celf_pm.ensure(8 * n));
+            ACAV_TRY(mi->celf_dn.ensure(sizeof(CelfDense)));
+            size_t a = 0, b = 0, cbytes = 0;
+            ACAV_HIP_TRY(rocprim::radix_sort_pairs_desc(nullptr, a, mi->celf_ks.as<long long>(), mi->celf_ks2.as<long long>(),
+                                                        mi->celf_i0.as<int>(), mi->celf_i1.as<int>(), n, 0, 64, st));
+            ACAV_HIP_TRY(rocprim::radix_sort_pairs_desc(nullptr, b, mi->celf_kv.as<unsigned long long>(),
+                                                        mi->celf_kv2.as<unsigned long long>(), mi->celf_i1.as<int>(),
+                                                        mi->celf_i2.as<int>(), n, 0, 64, st));
+            ACAV_HIP_TRY(rocprim::inclusive_scan(nullptr, cbytes, mi->celf_d.as<double>(), mi->celf_pm.as<double>(), n, CelfMaxOp(), st));
+            tmp_bytes = a > b ? a : b;
+            tmp_bytes = tmp_bytes > cbytes ? tmp_bytes : cbytes;
+            ACAV_TRY(mi->celf_tmp.ensure(tmp_bytes ? tmp_bytes : 8));
+        }
+        for (int64_t it = 0; it < celf; ++it) {
+            if (dense_all || it == dense_at) {
+                const size_t n = (size_t)L;
+                const int alive = (int)(L - greedy - it);  // every pick removes one entry
+                const unsigned ga = (unsigned)((alive + 255) / 256);
+                long long *tri = trace_ids ? mi->tr_ids.as<long long>() + (size_t)it * cap : nullptr;
+                double *trv = trace_vals ? mi->tr_sc.as<double>() + (size_t)it * cap : nullptr;
+                size_t tb = tmp_bytes;
+                hipLaunchKernelGGL(prep_kernel, dim3(grid), dim3(256), 0, st, cx, mi->A0.as<int>(), (int)L,
+                                   mi->removed.as<unsigned char>(), mi->celf_stamp.as<long long>(), mi->celf_state.as<CelfState>(),
+                                   mi->celf_fresh.as<double>(), mi->celf_ks.as<long long>(), mi->celf_i0.as<int>(),
+                                   mi->celf_dn.as<CelfDense>());
+                ACAV_HIP_TRY(rocprim::radix_sort_pairs_desc(mi->celf_tmp.p, tb, mi->celf_ks.as<long long>(), mi->celf_ks2.as<long long>(),
+                                                            mi->celf_i0.as<int>(), mi->celf_i1.as<int>(), n, 0, 64, st));
+                hipLaunchKernelGGL(k_celf_dense_valkey, dim3(grid), dim3(256), 0, st, (int)L, mi->celf_i1.as<int>(),
+                                   mi->removed.as<unsigned char>(), mi->celf_val.as<double>(), mi->celf_kv.as<unsigned long long>());
+                tb = tmp_bytes;
+                ACAV_HIP_TRY(rocprim::radix_sort_pairs_desc(mi->celf_tmp.p, tb, mi->celf_kv.as<unsigned long long>(),
+                                                            mi->celf_kv2.as<unsigned long long>(), mi->celf_i1.as<int>(),
+                                                            mi->celf_i2.as<int>(), n, 0, 64, st));
+                hipLaunchKernelGGL(k_celf_dense_gather, dim3(ga), dim3(256), 0, st, alive, mi->celf_i2.as<int>(),
+                                   mi->celf_fresh.as<double>(), mi->celf_d.as<double>());
+                tb = tmp_bytes;
+                ACAV_HIP_TRY(rocprim::inclusive_scan(mi->celf_tmp.p, tb, mi->celf_d.as<double>(), mi->celf_pm.as<double>(),
+                                                     (size_t)alive, CelfMaxOp(), st));
+                hipLaunchKernelGGL(k_celf_dense_stop, dim3(ga), dim3(256), 0, st, alive, mi->celf_i2.as<int>(),
+                                   mi->celf_val.as<double>(), mi->celf_pm.as<double>(), mi->celf_dn.as<CelfDense>());
+                hipLaunchKernelGGL(k_celf_dense_winner, dim3(ga), dim3(256), 0, st, alive, mi->celf_d.as<double>(),
+                                   mi->celf_pm.as<double>(), mi->celf_dn.as<CelfDense>());
+                hipLaunchKernelGGL(k_celf_dense_apply, dim3(ga), dim3(256), 0, st, alive, mi->A0.as<int>(), mi->celf_i2.as<int>(),
+                                   mi->celf_d.as<double>(), mi->celf_dn.as<CelfDense>(), mi->celf_state.as<CelfState>(),
+                                   mi->celf_val.as<double>(), mi->celf_stamp.as<long long>(), tri, trv, (int)trace_cap);
+                hipLaunchKernelGGL(commit_kernel, dim3(1), dim3(256), 0, st, cx, mi->A0.as<int>(), mi->celf_i2.as<int>(),
+                                   mi->celf_d.as<double>(), mi->celf_dn.as<CelfDense>(), mi->celf_state.as<CelfState>(),
+                                   mi->removed.as<unsigned char>(), mi->S.as<long long>() + greedy + it,
+                                   mi->G.as<double>() + greedy + it, mi->celf_lk.as<long long>() + it, tri, trv, (int)trace_cap);
+                hipLaunchKernelGGL(k_celf_blocks, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, st, (int)L, bs, nb,
+                                   mi->removed.as<unsigned char>(), mi->celf_val.as<double>(), mi->celf_stamp.as<long long>(),
+                                   mi->celf_bv.as<double>(), mi->celf_bst.as<long long>(), mi->celf_bp.as<int>());
+                continue;
+            }
+            hipLaunchKernelGGL(pick_kernel, dim3(1), dim3(256), 0, st, cx, mi->A0.as<int>(), (int)L, bs, nb,
+                               mi->removed.as<unsigned char>(), mi->celf_val.as<double>(), mi->celf_stamp.as<long long>(),
+                               mi->celf_bv.as<double>(), mi->celf_bst.as<long long>(), mi->celf_bp.as<int>(),
+                               mi->celf_state.as<CelfState>(), M, mi->S.as<long long>() + greedy + it,
+                               mi->G.as<double>() + greedy + it, mi->celf_lk.as<long long>() + it,
+                               trace_ids ? mi->tr_ids.as<long long>() + (size_t)it * cap : nullptr,
+                               trace_vals ? mi->tr_sc.as<double>() + (size_t)it * cap : nullptr, (int)trace_cap);
+        }
+        ACAV_HIP_TRY(hipGetLastError());
+        ACAV_HIP_TRY(hipMemcpyAsync(LOOKUPS_out + greedy, mi->celf_lk.p, sizeof(long long) * (size_t)celf, hipMemcpyDeviceToHost, st));
+        if (trace_ids)
+            ACAV_HIP_TRY(hipMemcpyAsync(trace_ids, mi->tr_ids.p, sizeof(long long) * (size_t)celf * cap, hipMemcpyDeviceToHost, st));
+        if (trace_vals)
+            ACAV_HIP_TRY(hipMemcpyAsync(trace_vals, mi->tr_sc.p, sizeof(double) * (size_t)celf * cap, hipMemcpyDeviceToHost, st));
+        if (queue_final) {
+            ACAV_TRY(mi->celf_qout.ensure(sizeof(double) * (size_t)L));
+            hipLaunchKernelGGL(k_celf_queue_out, dim3(grid), dim3(256), 0, st, (int)L, mi->removed.as<unsigned char>(),
+                               mi->celf_val.as<double>(), mi->celf_qout.as<double>());
+            ACAV_HIP_TRY(hipGetLastError());
+            ACAV_HIP_TRY(hipMemcpyAsync(queue_final, mi->celf_qout.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToHost, st));
+        }
+    }
+    if (celf == 0 && queue_final)
+        for (int64_t i = 0; i < L; ++i) queue_final[i] = -INFINITY;  // no lazy pick: no queue was ever filled
+    for (int64_t i = 0; i < greedy; ++i) LOOKUPS_out[i] = 1;  // calc_measure_greedy returns lookup 1 (efficient.py:132-138)
+    ACAV_HIP_TRY(hipMemcpyAsync(S_out, mi->S.p, sizeof(long long) * (size_t)iters, hipMemcpyDeviceToHost, st));
+    ACAV_HIP_TRY(hipMemcpyAsync(GAIN_out, mi->G.p, sizeof(double) * (size_t)iters, hipMemcpyDeviceToHost, st));
+    ACAV_HIP_TRY(hipStreamSynchronize(st));
     return ACAV_OK;
 }
 

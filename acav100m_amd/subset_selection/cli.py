@@ -47,8 +47,9 @@ def prepare(**kwargs):
 
 def run(args):
     """cli.py:90-100"""
-    from .run_greedy import check_weight_type
+    from .run_greedy import check_celf_ratio, check_weight_type
     check_weight_type(args.measure_name, args.clustering.weight_type)  # before any shard is read
+    check_celf_ratio(args.measure_name, args.get('celf_ratio', 0))
     if args.measure_name == 'contrastive':
         from .run_contrastive import run_chunks_contrastive, run_single_contrastive
         return run_single_contrastive(args) if args.chunk_size is None else run_chunks_contrastive(args)

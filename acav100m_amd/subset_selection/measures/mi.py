@@ -56,12 +56,61 @@ class EfficientMI(EfficientBatchMI):
             self.candidate_ids = np.ascontiguousarray([c for c in cand.tolist() if c not in picked], np.int64)
         return S[:n].tolist(), G[:n].tolist()
 
+    CELF_TRACE_CAP = 64  # lookups recorded per CELF pick by record_trace
+
+    def _run_celf(self, subset_size, ns, celf_ratio, record_trace):
+        """acav_mi_run_celf: the exact greedy, then CELF lazy greedy (correspondence_retrieval efficient.py:140-196)."""
+        cand = self.candidate_ids
+        L = len(cand)
+        niters = max(0, min(int(subset_size) - 1 - int(ns), L))
+        S = np.empty(niters + 1, np.int64)
+        G = np.empty(niters + 1, np.float64)
+        K = np.zeros(niters + 1, np.int64)
+        cap = self.CELF_TRACE_CAP if record_trace else 0
+        tr_ids = np.empty((niters + 1, cap), np.int64) if record_trace else None
+        tr_vals = np.empty((niters + 1, cap), np.float64) if record_trace else None
+        queue = np.empty(L, np.float64) if record_trace else None
+        nsel = C.c_int64(0)
+        _lib.check(_lib._lib.acav_mi_run_celf(self._h, _lib.ptr(cand), L, int(ns), int(subset_size), float(celf_ratio),
+                                              _lib.ptr(S), _lib.ptr(G), _lib.ptr(K), C.byref(nsel), cap, _lib.ptr(tr_ids),
+                                              _lib.ptr(tr_vals), _lib.ptr(queue)))
+        n = nsel.value
+        if record_trace:
+            ngreedy = int(round(n * (1 - celf_ratio)))
+            self.trace = dict(lookup_ids=tr_ids[:n - ngreedy], lookup_values=tr_vals[:n - ngreedy], queue=queue,
+                              greedy_picks=ngreedy)
+        picked = set(S[:n].tolist())
+        if picked:
+            self.candidate_ids = np.ascontiguousarray([c for c in cand.tolist() if c not in picked], np.int64)
+        return S[:n].tolist(), G[:n].tolist(), K[:n].tolist()
+
+    def run(self, subset_size, start_indices, intermediate_target=None, celf_ratio=0):
+        """EfficientMI.run of the correspondence_retrieval stage (efficient.py:240-299), same signature."""
+        return self.run_greedy(subset_size, start_indices, intermediate_target, celf_ratio=celf_ratio)
+
     def run_greedy(self, subset_size, start_indices, intermediate_target=None, verbose=False, log_every=1,
-                   log_times=None, node_rank=None, pid=None, record_trace=False, forced_pos=None):
+                   log_times=None, node_rank=None, pid=None, record_trace=False, forced_pos=None, celf_ratio=0):
         """mi.py:150-192: returns (S, GAIN, timelapse, LOOKUPS) with S = start_indices + the picks.
         forced_pos: ORIGINAL positions (indices into the candidate list given to init) to commit instead of the
-        argmax -- replays a recorded run."""
+        argmax -- replays a recorded run.
+        celf_ratio (efficient.py:240-299): the last round(niters * celf_ratio) picks are CELF lazy greedy -- a queue of stale
+        gains of which only the head is re-scored until it stays on top; GAIN is then the accumulated gain and LOOKUPS the
+        number of re-scorings (1 per greedy pick).  0 is the plain greedy, LOOKUPS all 0 as before.  The queue order among
+        equal values is pinned ("CELF"): a free-running lazy selection equals the reference's up to its first
+        exact tie."""
+        if not 0 <= celf_ratio <= 1:
+            raise ValueError("celf_ratio must lie in [0, 1], got {!r}".format(celf_ratio))
         start = list(start_indices)
+        if celf_ratio:
+            if forced_pos is not None:
+                raise ValueError("forced_pos replays the plain greedy only: celf_ratio must be 0")
+            t0 = time.time()
+            S, GAIN, LOOKUPS = self._run_celf(subset_size, len(start), celf_ratio, record_trace)
+            elapsed = time.time() - t0
+            if verbose:
+                print("(LEN: {}, MEASURE: {})".format(len(start) + len(S), GAIN[-1] if GAIN else float('nan')))
+                print("Time Consumed: {} seconds".format(elapsed))
+            return (start + S, GAIN, [elapsed / max(len(S), 1)] * len(S), LOOKUPS)
         t0 = time.time()
         S, GAIN = self._run(subset_size, len(start), forced_pos, record_trace)
         elapsed = time.time() - t0

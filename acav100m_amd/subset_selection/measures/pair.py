@@ -48,14 +48,15 @@ class _PairCountingMeasure(EfficientMI):
             self.candidate_ids = np.ascontiguousarray(self.candidate_ids[~gone])
 
     def run_greedy(self, subset_size, start_indices, intermediate_target=None, verbose=False, log_every=1,
-                   log_times=None, node_rank=None, pid=None, record_trace=False, forced_pos=None):
-        """EfficientMI.run (efficient.py:240-302) without CELF: add the start clips to the tables, then the exact greedy.
+                   log_times=None, node_rank=None, pid=None, record_trace=False, forced_pos=None, celf_ratio=0):
+        """EfficientMI.run (efficient.py:240-302): add the start clips to the tables, then the exact greedy, the last
+        round(niters * celf_ratio) picks of it as CELF lazy greedy (EfficientMI.run_greedy).
         forced_pos: positions in the candidate list as it stands after the start clips left it."""
         start = [int(i) for i in start_indices]
         self.add_samples(start)
         return super().run_greedy(subset_size, start, intermediate_target, verbose=verbose, log_every=log_every,
                                   log_times=log_times, node_rank=node_rank, pid=pid, record_trace=record_trace,
-                                  forced_pos=forced_pos)
+                                  forced_pos=forced_pos, celf_ratio=celf_ratio)
 
 
 class FowlkesMallowsScore(_PairCountingMeasure):

@@ -39,7 +39,8 @@ def run_partition(args, shard_paths):
     assignments, clustering_types, shard_names, filenames = io.load_assignment_shards(shard_paths)
     return run_greedy(args, assignments, shard_names, filenames, clustering_types, args.subset.size,
                       args.subset.ratio, measure_name=args.measure_name, cluster_pairing=args.clustering.pairing,
-                      shuffle_candidates=args.shuffle_candidates, verbose=args.verbose, weight_type=args.clustering.weight_type)
+                      shuffle_candidates=args.shuffle_candidates, verbose=args.verbose, weight_type=args.clustering.weight_type,
+                      celf_ratio=args.get('celf_ratio', 0))
 
 
 def _load(args, path):
@@ -56,7 +57,8 @@ def _select(args, data):
         results.append(run_greedy(args, assignments, shard_names, filenames, clustering_types, args.subset.size,
                                   args.subset.ratio, measure_name=args.measure_name,
                                   cluster_pairing=args.clustering.pairing, shuffle_candidates=args.shuffle_candidates,
-                                  verbose=args.verbose, weight_type=args.clustering.weight_type))
+                                  verbose=args.verbose, weight_type=args.clustering.weight_type,
+                                  celf_ratio=args.get('celf_ratio', 0)))
     return results
 
 
@@ -173,7 +175,7 @@ def compare_measures(args):
         for name in names:
             runs[name] = _run_greedy(args, assignments, clustering_types, args.subset.size, args.subset.ratio, measure_name=name,
                                      cluster_pairing=args.clustering.pairing, shuffle_candidates=False, verbose=False,
-                                     weight_type=args.clustering.weight_type)
+                                     weight_type=args.clustering.weight_type, celf_ratio=args.get('celf_ratio', 0))
         keys = list(runs)
         for a in range(len(keys)):
             for b in range(a + 1, len(keys)):
@@ -215,7 +217,8 @@ def _run_chunks_lockstep(args, chunk_args, mine, rank, width):
                                               chunk_args.subset.ratio, chunk_args.measure_name,
                                               chunk_args.clustering.pairing, chunk_args.shuffle_candidates,
                                               chunk_args.verbose, generator=Generator(base_seed + 1 + num),
-                                              weight_type=chunk_args.clustering.weight_type)
+                                              weight_type=chunk_args.clustering.weight_type,
+                                              celf_ratio=chunk_args.get('celf_ratio', 0))
             prepared.append((measure, start, subset, shard_names, filenames, metas))
         return prepared
 

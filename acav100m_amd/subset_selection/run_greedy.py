@@ -7,6 +7,7 @@ Plan of a run (reference run_greedy.py:9-74):
   B, k         = batch.batch_size clamped to V - 1, batch.selection_size clamped to B
   candidates   = 0..V-1, shuffled with Python's `random` when asked; the first one becomes the start index
   measure      = get_measure(name)(...); measure.init(pairs, candidates); measure.run_greedy(...)
+  celf_ratio   = share of the picks an exact-greedy measure takes lazily (CELF; correspondence_retrieval's celf_ratio)
   weight_type  = None, or a layer weighting of the pairs (pairing.get_weights; correspondence_retrieval's weight_type) for
                  the measures that weight their pairs (WEIGHTED_MEASURES)
 `_prepare` builds everything up to the measure call so that several chunks can be prepared first and then selected
@@ -28,6 +29,20 @@ def check_weight_type(measure_name, weight_type):
                          .format(weight_type, list(WEIGHTED_MEASURES), measure_name))
 
 
+# the measures that cannot run CELF: the reference asserts efficient_greedy for celf_ratio and its batch measure drops the value
+NO_CELF_MEASURES = ('batch_mi', 'contrastive')
+
+
+def check_celf_ratio(measure_name, celf_ratio):
+    ratio = 0 if celf_ratio is None else celf_ratio
+    if not 0 <= ratio <= 1:
+        raise ValueError("celf_ratio must lie in [0, 1], got {!r}".format(celf_ratio))
+    if ratio != 0 and str(measure_name).lower() in NO_CELF_MEASURES:
+        raise ValueError("celf_ratio={!r} needs an exact-greedy measure, not {!r}: it has no lazy variant"
+                         .format(celf_ratio, measure_name))
+    return ratio
+
+
 class _Plan:
     """sizes of one selection, derived once from the assignment matrix and the `batch` options"""
 
@@ -47,9 +62,10 @@ class _Plan:
 
 
 def _prepare(args, assignments, clustering_types, subset_size, subset_ratio, measure_name='mi',
-             cluster_pairing='combination', shuffle_candidates=True, verbose=False, generator=None, weight_type=None):
+             cluster_pairing='combination', shuffle_candidates=True, verbose=False, generator=None, weight_type=None, celf_ratio=0):
     """-> (measure ready to run, start_indices, subset_size)"""
     check_weight_type(measure_name, weight_type)
+    check_celf_ratio(measure_name, celf_ratio)  # checked here, before any device work; it is run_greedy's keyword, not init's
     plan = _Plan(args, assignments, subset_size, subset_ratio)
     if verbose:
         print("extracting {} samples from {} total datapoints".format(plan.subset, plan.rows))
@@ -65,18 +81,21 @@ def _prepare(args, assignments, clustering_types, subset_size, subset_ratio, mea
 
 
 def _run_greedy(args, assignments, clustering_types, subset_size, subset_ratio, measure_name='mi',
-                cluster_pairing='combination', shuffle_candidates=True, verbose=False, weight_type=None):
+                cluster_pairing='combination', shuffle_candidates=True, verbose=False, weight_type=None, celf_ratio=0):
+    ratio = check_celf_ratio(measure_name, celf_ratio)
     measure, head, subset = _prepare(args, assignments, clustering_types, subset_size, subset_ratio, measure_name,
-                                     cluster_pairing, shuffle_candidates, verbose, weight_type=weight_type)
+                                     cluster_pairing, shuffle_candidates, verbose, weight_type=weight_type, celf_ratio=ratio)
+    lazy = dict(celf_ratio=ratio) if ratio else {}  # only the exact measures take the keyword
     picked, gains, seconds, _lookups = measure.run_greedy(subset, head, None, verbose=verbose,
                                                          log_every=args.log_every, log_times=args.log_times,
-                                                         node_rank=args.node_rank, pid=args.parent_pid)
+                                                         node_rank=args.node_rank, pid=args.parent_pid, **lazy)
     return picked, gains, seconds
 
 
 def run_greedy(args, assignments, shard_names, filenames, clustering_types, subset_size, subset_ratio,
-               measure_name='mi', cluster_pairing='combination', shuffle_candidates=True, verbose=False, weight_type=None):
+               measure_name='mi', cluster_pairing='combination', shuffle_candidates=True, verbose=False, weight_type=None,
+               celf_ratio=0):
     """-> rows {'filename', 'shard_name'} of the selected clips, ordered by clip index (run_greedy.py:72)"""
     picked, _, _ = _run_greedy(args, assignments, clustering_types, subset_size, subset_ratio, measure_name,
-                               cluster_pairing, shuffle_candidates, verbose, weight_type=weight_type)
+                               cluster_pairing, shuffle_candidates, verbose, weight_type=weight_type, celf_ratio=celf_ratio)
     return [dict(filename=filenames[i], shard_name=shard_names[i]) for i in sorted(picked)]

@@ -1,0 +1,83 @@
+#!/usr/bin/env python3
+"""CELF lazy greedy against the dense exact pick: V = 200 000, C = 256, P = 3 and P = 45; a 200-pick greedy prefix, then 2 000
+picks timed with celf_ratio 0 (k_mi_exact_iter, one dense launch per pick: the kernel and launch loop of acav_mi_run_exact,
+which this entry point shares unchanged) and celf_ratio 1 (the lazy phase, queue fill and the full re-scoring pick
+included).  The library call alone is timed (median of 3), for all picks and for the first tenth: `*_us_per_pick` is the
+whole call over its picks, `*_us_per_pick_steady` the difference of the two over the remaining picks.  One JSON line per
+shape, with mean / median / p99 / max LOOKUPS.
+
+    python tools/bench_mi_celf.py [--v 200000] [--picks 2000] [--prefix 200] [--limit 600]
+
+Every shape runs in a child process under --limit seconds."""
+import argparse
+import itertools
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def one(v, c, d, picks, prefix, reps=3):
+    import ctypes as C
+    import numpy as np
+    import acav100m_amd
+    from acav100m_amd import _lib
+    from acav100m_amd.subset_selection import get_measure
+    acav100m_amd.load_library()
+    rs = np.random.RandomState(0)
+    comp = rs.randint(0, c, size=v)
+    a = np.stack([np.where(rs.rand(v) < 0.5, comp, rs.randint(0, c, size=v)) for _ in range(d)], 1).astype(np.int64)
+    pairs = list(itertools.combinations(range(d), 2))
+    res = dict(V=v, C=c, P=len(pairs), picks=picks, prefix=prefix, reps=reps)
+
+    def call(ratio, n):
+        """seconds of ONE library call (n picks, from the table state after the greedy prefix), and its LOOKUPS"""
+        m = get_measure("mi")(a, ncentroids=c, device="cuda:0")
+        m.init(pairs, list(range(1, v)))
+        m.run_greedy(prefix + 2, [0])
+        cand = np.ascontiguousarray(m.candidate_ids, np.int64)
+        S, G, K = np.empty(n + 1, np.int64), np.empty(n + 1, np.float64), np.zeros(n + 1, np.int64)
+        nsel = C.c_int64(0)
+        t0 = time.perf_counter()
+        _lib.check(_lib._lib.acav_mi_run_celf(m._h, _lib.ptr(cand), len(cand), 0, n + 1, float(ratio), _lib.ptr(S), _lib.ptr(G),
+                                              _lib.ptr(K), C.byref(nsel), 0, None, None, None))
+        return time.perf_counter() - t0, K[:n]
+
+    short = max(picks // 10, 2)
+    for key, ratio in (("dense", 0.0), ("lazy", 1.0)):
+        full, head, K = [], [], None
+        for _ in range(reps):
+            t, K = call(ratio, picks)
+            full.append(t)
+            head.append(call(ratio, short)[0])
+        tf, th = float(np.median(full)), float(np.median(head))
+        res[key + "_us_per_pick"] = 1e6 * tf / picks                         # everything: queue fill and the full re-scoring pick
+        res[key + "_us_per_pick_steady"] = 1e6 * (tf - th) / (picks - short)  # picks short..picks: what a further pick costs
+        if ratio:
+            res.update(lookups_mean=float(K.mean()), lookups_median=float(np.median(K)), lookups_p99=float(np.percentile(K, 99)),
+                       lookups_max=int(K.max()), lookups_mean_steady=float(K[short:].mean()),
+                       lookups_p99_steady=float(np.percentile(K[short:], 99)))
+    print(json.dumps(res), flush=True)
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--v", type=int, default=200000)
+    ap.add_argument("--c", type=int, default=256)
+    ap.add_argument("--picks", type=int, default=2000)
+    ap.add_argument("--prefix", type=int, default=200)
+    ap.add_argument("--limit", type=int, default=600)
+    ap.add_argument("--child", type=int, default=0)
+    args = ap.parse_args()
+    if args.child:
+        one(args.v, args.c, args.child, args.picks, args.prefix)
+    else:
+        for d in (3, 10):  # P = 3, P = 45
+            rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", str(d), "--v", str(args.v), "--c", str(args.c),
+                                 "--picks", str(args.picks), "--prefix", str(args.prefix)], timeout=args.limit).returncode
+            if rc != 0:
+                sys.exit(rc)
