@@ -147,6 +147,10 @@ SUBSET_DEFAULTS = {
     # weight_type: None, or linear|log|exp[_<coeff>] / onehot_<layer>: per-layer weights of the clustering pairs
     #   (correspondence_retrieval cluster_pairing.py / pair_weights.py) for the mi, mem_mi and batch_mi measures
     'clustering': {'pairing': 'combination', 'weight_type': None},
+    # batch_mi: batch_size candidates are scored per iteration, the best selection_size of them selected.  Supported:
+    #   1 <= selection_size <= batch_size <= 1024 and batch_size x clustering pairs <= 8192 (both are clamped to the number of
+    #   clips first).  The defaults are the reference CLI's; its paper grids run at batch_size 100 / selection_size 25 (every
+    #   correspondence_retrieval search target) -- 6 x fewer iterations, hence permutations of the candidate list, per subset
     'batch': {'batch_size': 20, 'selection_size': 4, 'keep_unselected': True},
     'contrastive': {'num_epochs': 3, 'num_warmup_steps': 1, 'base_lr': 2e-4, 'train_batch_size': 128, 'test_batch_size': 128,
                     'cached_epoch': None, 'train_from_cached': False},

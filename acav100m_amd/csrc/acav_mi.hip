@@ -288,7 +288,8 @@ __device__ __forceinline__ double pair_count_score(const int *__restrict__ asg, 
 }
 
 
-constexpr int SEL_MAXB = 64;
+constexpr int SEL_MAXB = 64;      // batch sizes up to here: the NARROW selection (one wave ranks the batch, lane = batch position)
+constexpr int SEL_WIDEB = 1024;   // batch sizes up to here: the WIDE selection (the workgroup ranks the batch out of LDS)
 constexpr int SEL_MAXBP = 8192;
 
 // One workgroup per greedy iteration: score the B candidates (mean over P pairs), pick the top k
@@ -353,12 +354,124 @@ __host__ __device__ inline SelLayout sel_layout(int B, int P, int D, int k, int 
     return l;
 }
 
+// The WIDE selection (SEL_MAXB < B <= SEL_WIDEB) keeps what SelShared holds per batch position in dynamic LDS instead, behind the
+// launch's SelLayout:  score, key [B] f64 | id, pos, used, req [B] i32  (req: the re-queued ids of the fused gather + selection
+// kernel).  The narrow launches neither reserve nor address it.
+struct SelWide {
+    double *score, *key;
+    int *id, *pos, *used, *req;
+};
+__host__ __device__ inline unsigned sel_wide_off(const SelLayout &l) { return (l.total + 7u) & ~7u; }
+__host__ __device__ inline SelWide sel_wide(unsigned char *smem, const SelLayout &l, int B)
+{
+    SelWide w;
+    w.score = reinterpret_cast<double *>(smem + sel_wide_off(l));
+    w.key = w.score + B;
+    w.id = reinterpret_cast<int *>(w.key + B);
+    w.pos = w.id + B, w.used = w.pos + B, w.req = w.used + B;
+    return w;
+}
+// dynamic LDS of a selection launch, narrow or wide
+__host__ __device__ inline size_t sel_smem_bytes(int B, int P, int D, int k, int mode)
+{
+    const SelLayout l = sel_layout(B, P, D, k, mode);
+    return B > SEL_MAXB ? (size_t)sel_wide_off(l) + 32u * (size_t)B : (size_t)l.total;
+}
+
 // workgroup barrier that orders LDS traffic only: __syncthreads() also waits for every outstanding global store to be
 // acknowledged (~1 us each time on the selection's critical path)
 __device__ __forceinline__ void lds_barrier()
 {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
+}
+
+// Candidate means, top-k and re-queue ranking of the WIDE selection: what wave 0 does for B <= 64 in mi_select_body, by the whole
+// workgroup (256 threads; thread t owns the batch positions t, t + 256, ...: at most SEL_WPT of them).  Same order: the mean
+// is (sum over p in pair order, from 0.0) / P; rank = number of candidates that beat this one (score descending, NaN as -inf,
+// ties -> lower batch position); the un-selected ids are ranked ascending, ties by position.  Every thread walks the B keys
+// in LDS once (all lanes read the same address: a broadcast) and compares each with the keys of its own positions.
+// Leaves w.pos[0 .. k) for the commit; ends without a barrier.
+constexpr int SEL_WPT = SEL_WIDEB / 256;
+__device__ __forceinline__ void mi_select_rank_wide(
+    const double *sS, const SelWide &w, int B, int P, int k, double *__restrict__ scores_out, long long *__restrict__ S_out,
+    double *__restrict__ G_out, const int *__restrict__ forced_pos, int *__restrict__ trace_pos,
+    long long *__restrict__ trace_ids, double *__restrict__ trace_scores, int keep_unselected, int *requeue_out,
+    int requeue_stride)
+{
+    const int tid = threadIdx.x;
+    for (int b = tid; b < B; b += 256) {
+        double tot = 0.0;
+        for (int p = 0; p < P; ++p) tot = tot + sS[(size_t)b * P + p];
+        const double s = tot / (double)P;
+        w.score[b] = s;
+        w.key[b] = s == s ? s : -INFINITY;
+        if (scores_out) scores_out[b] = s;
+        if (trace_scores) trace_scores[b] = s;
+        if (trace_ids) trace_ids[b] = w.id[b];
+    }
+    if (k == 0) return;
+    lds_barrier();
+    {
+        double key[SEL_WPT];
+        int rank[SEL_WPT];
+#pragma unroll
+        for (int q = 0; q < SEL_WPT; ++q) {
+            const int b = tid + 256 * q;
+            key[q] = b < B ? w.key[b] : -INFINITY;
+            rank[q] = 0;
+        }
+        for (int o = 0; o < B; ++o) {
+            const double ok = w.key[o];
+#pragma unroll
+            for (int q = 0; q < SEL_WPT; ++q) rank[q] += (ok > key[q] || (ok == key[q] && o < tid + 256 * q)) ? 1 : 0;
+        }
+#pragma unroll
+        for (int q = 0; q < SEL_WPT; ++q) {
+            const int b = tid + 256 * q;
+            if (b >= B) continue;
+            const bool picked = rank[q] < k;
+            if (picked) {
+                if (!forced_pos) w.pos[rank[q]] = b;
+                if (trace_pos) trace_pos[rank[q]] = b;  // the free-running choice, also under teacher forcing
+            }
+            w.used[b] = picked && !forced_pos ? 1 : 0;
+        }
+    }
+    lds_barrier();
+    if (forced_pos) {
+        for (int r = tid; r < k; r += 256) {
+            const int f = forced_pos[r];
+            w.pos[r] = f;
+            w.used[f] = 1;
+        }
+        lds_barrier();
+    }
+    for (int r = tid; r < k; r += 256) {
+        const int pos = w.pos[r];
+        S_out[r] = (long long)w.id[pos];
+        G_out[r] = w.score[pos];
+    }
+    if (keep_unselected) {  // get_unselected: torch.unique -> ascending ids (batch.py:167-171)
+        int myid[SEL_WPT], rq[SEL_WPT];
+#pragma unroll
+        for (int q = 0; q < SEL_WPT; ++q) {
+            const int b = tid + 256 * q;
+            myid[q] = b < B ? w.id[b] : 0;
+            rq[q] = 0;
+        }
+        for (int o = 0; o < B; ++o) {
+            if (w.used[o]) continue;  // uniform
+            const int oid = w.id[o];
+#pragma unroll
+            for (int q = 0; q < SEL_WPT; ++q) rq[q] += (oid < myid[q] || (oid == myid[q] && o < tid + 256 * q)) ? 1 : 0;
+        }
+#pragma unroll
+        for (int q = 0; q < SEL_WPT; ++q) {
+            const int b = tid + 256 * q;
+            if (b < B && !w.used[b]) requeue_out[(size_t)rq[q] * requeue_stride] = myid[q];
+        }
+    }
 }
 
 // everything the selection needs that does not depend on the batch; a barrier must separate it from mi_select_body.
@@ -386,7 +499,10 @@ __device__ __forceinline__ void mi_select_stage(SelSharedOf<W> &ss, int P, const
 // W: every pair score is multiplied by its fp32 weight (pw, staged in ss.w up to SEL_LDSP pairs) where it is written to sS, so
 // the candidate's score is sum_p(s_p w_p) / P -- the reference's einsum('wp,p->wp') before .mean(-1) (correspondence_retrieval
 // measures/efficient.py:95-101)
-template <bool W>
+// WIDE: B > SEL_MAXB (batch != nullptr): the per-position arrays live in dynamic LDS (SelWide) and the workgroup ranks the batch
+// (mi_select_rank_wide); scoring and commit are the same code.  An instantiation of its own, chosen on the host: the narrow
+// one is what it was before the wide one existed (registers and LDS, which the gather workgroups of the fused launch inherit)
+template <bool W, bool WIDE = false>
 __device__ __forceinline__ void mi_select_body(
     SelSharedOf<W> &ss, const int *__restrict__ asg, int D, int C, int P, const int *__restrict__ pairs,
     const int *__restrict__ batch, int reg_id, const int *__restrict__ lab_in, int B, int k, int mode, int *__restrict__ Nc,
@@ -406,15 +522,22 @@ __device__ __forceinline__ void mi_select_body(
     double *sPhiK = reinterpret_cast<double *>(smem_raw + lay.off_phik);   // [k*P][6]  (fast)
     int *sLab = reinterpret_cast<int *>(smem_raw + lay.off_lab);           // [B][D]
     const int tid = threadIdx.x;
+    SelWide sw{};
+    if constexpr (WIDE) sw = sel_wide(smem_raw, lay, B);
+    int *const sId = WIDE ? sw.id : ss.id, *const sPos = WIDE ? sw.pos : ss.pos;
     FY_CLK0();
-    if (tid < B) ss.id[tid] = batch ? batch[tid] : reg_id;
+    if constexpr (WIDE) {
+        for (int b = tid; b < B; b += blockDim.x) sId[b] = batch[b];
+    } else {
+        if (tid < B) ss.id[tid] = batch ? batch[tid] : reg_id;
+    }
     if (lab_in)
         for (int t = tid; t < B * D; t += blockDim.x) sLab[t] = lab_in[t];
     lds_barrier();  // also: the staged constants are visible
     if (!lab_in) {
         for (int t = tid; t < B * D; t += blockDim.x) {
             const int w = t / D;
-            sLab[t] = asg[(size_t)ss.id[w] * D + (t - w * D)];
+            sLab[t] = asg[(size_t)sId[w] * D + (t - w * D)];
         }
         lds_barrier();
     }
@@ -449,7 +572,10 @@ __device__ __forceinline__ void mi_select_body(
     // beat it, their keys broadcast lane by lane (v_readlane; k rounds of a wave-wide argmax were 2.6 us of shuffles, a
     // loop of LDS reads 1 us).  Order: score descending, ties -> lower batch position; a NaN score never wins against a
     // number and ranks by position among its like (as the argmax rounds did).  The un-selected ids are ranked the same way.
-    if (tid < 64) {
+    if constexpr (WIDE) {
+        mi_select_rank_wide(sS, sw, B, P, k, scores_out, S_out, G_out, forced_pos, trace_pos, trace_ids, trace_scores, keep_unselected,
+                            requeue_out, requeue_stride);
+    } else if (tid < 64) {
         double s = 0.0, key = -INFINITY;
         const int myid = tid < B ? ss.id[tid] : 0;
         if (tid < B) {
@@ -510,7 +636,7 @@ __device__ __forceinline__ void mi_select_body(
         // the kernel to 253 VGPRs -- 2 waves per SIMD for every gather workgroup of the same launch.)
         for (int t = tid; t < k * P; t += blockDim.x) {
             const int r = t / P, p = t - r * P;
-            const int me = ss.pos[r] * P + p;
+            const int me = sPos[r] * P + p;
             const int ci = sCi[me], cj = sCj[me];
             const int bN = sCN[me], ba = sCa[me], bb = sCb[me];
             int cN = bN, ca = ba, cb = bb;
@@ -518,7 +644,7 @@ __device__ __forceinline__ void mi_select_body(
 #pragma unroll 4
             for (int e = 0; e < k; ++e) {
                 if (e == r) continue;
-                const int o = ss.pos[e] * P + p;
+                const int o = sPos[e] * P + p;
                 const bool mi_ = sCi[o] == ci, mj = sCj[o] == cj;
                 if (e < r) {
                     cN += (mi_ && mj) ? 1 : 0;
@@ -562,7 +688,7 @@ __device__ __forceinline__ void mi_select_body(
             double sN = lp ? ss.SN[p] : SN[p], sa = lp ? ss.Sa[p] : Sa[p], sb = lp ? ss.Sb[p] : Sb[p];
             const int d0 = lp ? ss.pairs[2 * p] : pairs[2 * p], d1 = lp ? ss.pairs[2 * p + 1] : pairs[2 * p + 1];
             for (int r = 0; r < k; ++r) {
-                const int *row = sLab + (size_t)ss.pos[r] * D;
+                const int *row = sLab + (size_t)sPos[r] * D;
                 const int i = row[d0], j = row[d1];
                 const size_t cell = ((size_t)p * C + i) * C + j;
                 const int cN = Nc[cell], ca = ac[(size_t)p * C + j], cb = bc[(size_t)p * C + i];
@@ -582,8 +708,8 @@ __device__ __forceinline__ void mi_select_body(
     FY_CLK(12);
 }
 
-// W: the weighted instantiation (pw = the handle's pair weights); the unweighted one never reads pw
-template <bool W>
+// W: the weighted instantiation (pw = the handle's pair weights); the unweighted one never reads pw.  WIDE: B > SEL_MAXB
+template <bool W, bool WIDE>
 __global__ __launch_bounds__(256) void k_mi_select(
     const int *__restrict__ asg, int D, int C, int P, const int *__restrict__ pairs,
     const int *__restrict__ batch, int B, int k, int mode, int *__restrict__ Nc, int *__restrict__ ac,
@@ -595,8 +721,8 @@ __global__ __launch_bounds__(256) void k_mi_select(
 {
     __shared__ SelSharedOf<W> ss;
     mi_select_stage<W>(ss, P, pairs, SN, Sa, Sb, sc, pw);
-    mi_select_body<W>(ss, asg, D, C, P, pairs, batch, 0, nullptr, B, k, mode, Nc, ac, bc, SN, Sa, Sb, phi, sc, scores_out, S_out, G_out,
-                      forced_pos, trace_pos, trace_ids, trace_scores, keep_unselected, requeue_out, 1, pw);
+    mi_select_body<W, WIDE>(ss, asg, D, C, P, pairs, batch, 0, nullptr, B, k, mode, Nc, ac, bc, SN, Sa, Sb, phi, sc, scores_out, S_out,
+                            G_out, forced_pos, trace_pos, trace_ids, trace_scores, keep_unselected, requeue_out, 1, pw);
 }
 
 // ------------------------------------------------------------------- exact greedy (mi / mem_mi)
@@ -1806,11 +1932,11 @@ struct TileChunk {
     unsigned *src[FY_GROUP]; // content references and last pullers, per iteration of the group in flight
     int *g[FY_GROUP];
     unsigned *perm[FY_NBUF]; // source position of every output position, per iteration (FY_DEPTH groups deep)
-    int *tailinv;            // [FY_NBUF][SEL_MAXB] the output position that reads the r-th of the last `nreq` list positions
+    int *tailinv;            // [FY_NBUF][bcap] the output position that reads the r-th of the last `nreq` list positions
     int *A[2];
     unsigned *err;
     const int *asg, *pairs;
-    int *batch, *Nc, *ac, *bc;  // batch: [2][SEL_MAXB (1 + D)]: ids and label rows of the batch of iteration t in half t & 1
+    int *batch, *Nc, *ac, *bc;  // batch: [2][bcap (1 + D)]: ids and label rows of the batch of iteration t in half t & 1
     double *SN, *Sa, *Sb;
     const double *phi;
     MiScalars *sc;
@@ -1820,7 +1946,8 @@ struct TileChunk {
     int *tr_pos;
     long long *tr_ids;
     double *tr_sc;
-    int L0, iters, ntab, gsh, NT, capg, ecap, wcap, D, C, P, pad;
+    int L0, iters, ntab, gsh, NT, capg, ecap, wcap, D, C, P;
+    int bcap;                // batch capacity of tailinv and batch: SEL_MAXB for the narrow launches (which do not read it), else B
     const float *w;          // fp32 pair weights [P] (acav_mi_set_pair_weights), NULL: unweighted
 };
 
@@ -1863,6 +1990,7 @@ __global__ __launch_bounds__(FYT_THREADS) void k_fy_tile_multi(const TileChunk *
 
 // perm[i] = the position (before the iteration) whose content output position i receives: the E-ref chains are walked
 // here, beside the content path -- the gather that waits for the previous selection is then one indexed copy
+template <bool WIDE>
 __global__ __launch_bounds__(256) void k_fy_resolve_multi(const TileChunk *__restrict__ cd, int it0, int dl, int nreq)
 {
     ACAV_MI_EMPTY_RETURN
@@ -1887,7 +2015,7 @@ __global__ __launch_bounds__(256) void k_fy_resolve_multi(const TileChunk *__res
     c.perm[it % FY_NBUF][i] = (unsigned)a;
     // the last nreq positions of the list hold what the PREVIOUS iteration's selection re-queues (see
     // k_fy_gather_select_multi): who reads them
-    if (a >= L - nreq) c.tailinv[(size_t)(it % FY_NBUF) * SEL_MAXB + (a - (L - nreq))] = i;
+    if (a >= L - nreq) c.tailinv[(size_t)(it % FY_NBUF) * (WIDE ? c.bcap : SEL_MAXB) + (a - (L - nreq))] = i;
 }
 
 // Launch `it` of the content stream, two things that do not depend on each other (software pipelining: the selection is a
@@ -1900,8 +2028,10 @@ __global__ __launch_bounds__(256) void k_fy_resolve_multi(const TileChunk *__res
 //   workgroup 0      SELECTION of iteration it-1 (mi_select_body: scoring / top-k / commit on the batch gathered by the
 //                    previous launch), then the nreq re-queued ids go straight to the outputs of iteration `it` that read them.
 // Launches run it = 0 .. iters (the first has no selection, the last no gather).
-// W: the weighted selection (some chunk of the launch has pair weights); launched only then
-template <bool W>
+// W: the weighted selection (some chunk of the launch has pair weights); launched only then.  WIDE: B > SEL_MAXB -- tailinv and the
+// batch buffers are laid out for c.bcap positions (the narrow launch keeps SEL_MAXB), the batch ids and the re-queued ids go
+// through LDS instead of one register per thread, and the hand-over loops over the nreq (up to B - 1) positions
+template <bool W, bool WIDE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_fy_gather_select_multi(
     const TileChunk *__restrict__ cd, int it, int dl, int B, int k, int mode, int keep_unselected)
 {
@@ -1909,7 +2039,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     const TileChunk &c = cd[blockIdx.y];
     const int L = c.L0 - it * dl;  // list length of iteration `it`
     const int nreq = keep_unselected ? B - k : 0;
-    const int bstride = SEL_MAXB * (1 + c.D);  // one half of the batch buffer: ids [SEL_MAXB], label rows [SEL_MAXB][D]
+    const int bcap = WIDE ? c.bcap : SEL_MAXB;
+    const int bstride = bcap * (1 + c.D);  // one half of the batch buffer: ids [bcap], label rows [bcap][D]
     if (blockIdx.x != 0) {
         if (it >= c.iters) return;
         // GS_EPT outputs per thread, every index load before the first content load (1 -> 4 per thread: 34.9 -> 33.7 us per
@@ -1933,7 +2064,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
             if (i < B) {  // a batch entry travels with its label row: the next launch's selection starts one level further on
                 int *bb = c.batch + (it & 1) * bstride;
                 bb[i] = v;
-                for (int d = 0; d < c.D; ++d) bb[SEL_MAXB + i * c.D + d] = c.asg[(size_t)v * c.D + d];
+                for (int d = 0; d < c.D; ++d) bb[bcap + i * c.D + d] = c.asg[(size_t)v * c.D + d];
             } else {
                 c.A[(it + 1) & 1][i - B] = v;
             }
@@ -1943,9 +2074,31 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     if (it < 1 || it > c.iters) return;
     const int ps = it - 1;  // the iteration whose selection this is
     __shared__ SelSharedOf<W> ss;
-    __shared__ int sReq[SEL_MAXB];
+    __shared__ int sReq[SEL_MAXB];  // (narrow)
     const int *bprev = c.batch + (ps & 1) * bstride;
     mi_select_stage<W>(ss, c.P, c.pairs, c.SN, c.Sa, c.Sb, c.sc, W ? c.w : nullptr);
+    if constexpr (WIDE) {
+        extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+        int *sReqW = sel_wide(smem_raw, sel_layout(B, c.P, c.D, k, mode), B).req;
+        mi_select_body<W, true>(ss, c.asg, c.D, c.C, c.P, c.pairs, bprev, 0, bprev + bcap, B, k, mode, c.Nc, c.ac, c.bc, c.SN, c.Sa, c.Sb,
+                                c.phi, c.sc, nullptr, c.S + (size_t)ps * k, c.G + (size_t)ps * k,
+                                c.forced ? c.forced + (size_t)ps * k : nullptr, c.tr_pos ? c.tr_pos + (size_t)ps * k : nullptr,
+                                c.tr_ids ? c.tr_ids + (size_t)ps * B : nullptr, c.tr_sc ? c.tr_sc + (size_t)ps * B : nullptr,
+                                keep_unselected, sReqW, 1, W ? c.w : nullptr);
+        if (it >= c.iters || nreq == 0) return;  // no gather left to feed
+        lds_barrier();
+        int *bb = c.batch + (it & 1) * bstride;
+        for (int r = threadIdx.x; r < nreq; r += 256) {
+            const int v = sReqW[r], dest = c.tailinv[(size_t)(it % FY_NBUF) * bcap + r];
+            if (dest < B) {
+                bb[dest] = v;
+                for (int d = 0; d < c.D; ++d) bb[bcap + dest * c.D + d] = c.asg[(size_t)v * c.D + d];
+            } else {
+                c.A[(it + 1) & 1][dest - B] = v;
+            }
+        }
+        return;
+    }
     const int id = (int)threadIdx.x < B ? bprev[threadIdx.x] : 0;
     const bool feeds = it < c.iters && (int)threadIdx.x < nreq;  // this thread delivers a re-queued id to the gather of `it`
     const int dest = feeds ? c.tailinv[(size_t)(it % FY_NBUF) * SEL_MAXB + threadIdx.x] : 0;
@@ -2031,7 +2184,7 @@ __global__ __launch_bounds__(256) void k_fy_apply_multi(const ChunkDesc *__restr
                   c.head[(it + 1) & 1], c.g[(it + 1) & 1], (int)(blockIdx.x * blockDim.x + threadIdx.x));
 }
 
-template <bool W>
+template <bool W, bool WIDE>
 __global__ __launch_bounds__(256) void k_mi_select_multi(const ChunkDesc *__restrict__ cd, int it, int dl, int B, int k,
                                                          int mode, int keep_unselected)
 {
@@ -2040,9 +2193,9 @@ __global__ __launch_bounds__(256) void k_mi_select_multi(const ChunkDesc *__rest
     __shared__ SelSharedOf<W> ss;
     const float *pw = W ? chunk_weights(c) : nullptr;
     mi_select_stage<W>(ss, c.P, c.pairs, c.SN, c.Sa, c.Sb, c.sc, pw);
-    mi_select_body<W>(ss, c.asg, c.D, c.C, c.P, c.pairs, c.batch, 0, nullptr, B, k, mode, c.Nc, c.ac, c.bc, c.SN, c.Sa, c.Sb, c.phi, c.sc,
-                      nullptr, c.S + (size_t)it * k, c.G + (size_t)it * k, nullptr, nullptr, nullptr, nullptr, keep_unselected,
-                      c.A[(it + 1) & 1] + (c.L0 - it * dl - B), 1, pw);
+    mi_select_body<W, WIDE>(ss, c.asg, c.D, c.C, c.P, c.pairs, c.batch, 0, nullptr, B, k, mode, c.Nc, c.ac, c.bc, c.SN, c.Sa, c.Sb, c.phi,
+                            c.sc, nullptr, c.S + (size_t)it * k, c.G + (size_t)it * k, nullptr, nullptr, nullptr, nullptr,
+                            keep_unselected, c.A[(it + 1) & 1] + (c.L0 - it * dl - B), 1, pw);
 }
 
 __global__ void k_i64_to_i32(const long long *__restrict__ in, int *__restrict__ out, long long n)
@@ -2304,6 +2457,18 @@ struct FyPlan {
     size_t tile_smem() const { return (size_t)wcap * 8 + (size_t)ecap_lds * 8; }
 };
 
+// dynamic LDS of a selection launch; a WIDE batch whose label rows [B][D] do not fit one workgroup's LDS beside the rest is
+// refused here (the narrow launches keep leaving that to the runtime)
+static int sel_smem_checked(int B, int P, int D, int k, int mode, size_t *out)
+{
+    *out = sel_smem_bytes(B, P, D, k, mode);
+    constexpr size_t lds = 160 * 1024;  // per workgroup on gfx950
+    ACAV_REQUIRE(B <= SEL_MAXB || *out + sizeof(SelSharedW) <= lds, ACAV_EINVAL,
+                 "batch_size %d x %d clusterings (x %d pairs) needs %zu bytes of LDS: more than a workgroup has (%zu); lower batch_size",
+                 B, D, P, *out + sizeof(SelSharedW), lds);
+    return ACAV_OK;
+}
+
 static size_t fy_part_smem(int NT, size_t ntab, bool staged, bool pack = false)
 {
     return sizeof(int) * ((staged ? 3 : 2) + (pack ? 1 : 0)) * (size_t)NT + (staged ? sizeof(int2) * FYA_CH + sizeof(int) * 16 : 0) +
@@ -2314,7 +2479,7 @@ static size_t fy_part_smem(int NT, size_t ntab, bool staged, bool pack = false)
 // counters (one set per iteration of a group; zeroed), error flag (cleared), src / g (per iteration of a group) and perm
 // (two groups deep) buffers; uploads are stream-ordered on st (fp must stay alive
 // until st has been synchronised)
-static int fy_setup(acav_mi *mi, int64_t L, FyPlan &fp, hipStream_t st)
+static int fy_setup(acav_mi *mi, int64_t L, int bcap, FyPlan &fp, hipStream_t st)
 {
     fp.build(L);
     ACAV_TRY(mi->fy_table.ensure(sizeof(unsigned short) * fp.table.size()));
@@ -2327,7 +2492,7 @@ static int fy_setup(acav_mi *mi, int64_t L, FyPlan &fp, hipStream_t st)
         ACAV_TRY(mi->fy_g[q].ensure(sizeof(int) * (size_t)L));
     }
     for (int q = 0; q < FY_NBUF; ++q) ACAV_TRY(mi->fy_perm[q].ensure(sizeof(unsigned) * (size_t)L));
-    ACAV_TRY(mi->fy_tail.ensure(sizeof(int) * (size_t)FY_NBUF * SEL_MAXB));
+    ACAV_TRY(mi->fy_tail.ensure(sizeof(int) * (size_t)FY_NBUF * (size_t)bcap));
     ACAV_HIP_TRY(hipMemcpyAsync(mi->fy_table.p, fp.table.data(), sizeof(unsigned short) * fp.table.size(), hipMemcpyHostToDevice, st));
     ACAV_HIP_TRY(hipMemcpyAsync(mi->fy_bounds.p, fp.ebound.data(), sizeof(int) * fp.ebound.size(), hipMemcpyHostToDevice, st));
     ACAV_HIP_TRY(hipMemsetAsync(mi->fy_count.p, 0, sizeof(int) * (size_t)FY_GROUP * fp.NT * FY_SHARDS, st));
@@ -2604,6 +2769,8 @@ static int run_greedy_tiled(acav_mi **mis, int nchunks, const int64_t *const *ca
     const auto t_setup0 = clk::now();
     double t_ids = 0, t_fy = 0, t_mt = 0, t_add = 0;
     const int64_t dl = B - (keep_unselected ? B - k : 0);  // candidates consumed per iteration
+    const bool wide = B > SEL_MAXB;
+    const int bcap = wide ? B : SEL_MAXB;  // batch capacity of tailinv and the batch buffers: the narrow layout up to SEL_MAXB
     std::vector<TileChunk> desc((size_t)nchunks);
     std::vector<int64_t> iters((size_t)nchunks, 0), r0((size_t)nchunks, 0);
     std::vector<FyPlan> plans((size_t)nchunks);
@@ -2650,7 +2817,7 @@ static int run_greedy_tiled(acav_mi **mis, int nchunks, const int64_t *const *ca
         ACAV_TRY(ids_to_device32(mi, candidates[c], L[c], mi->stage, mi->A0, st));
         t_ids += ms_since(t0); }
         ACAV_TRY(mi->A1.ensure(sizeof(int) * (Lc + B)));
-        ACAV_TRY(mi->batch.ensure(sizeof(int) * 2 * SEL_MAXB * (size_t)(1 + mi->D)));
+        ACAV_TRY(mi->batch.ensure(sizeof(int) * 2 * (size_t)bcap * (size_t)(1 + mi->D)));
         ACAV_TRY(mi->S.ensure(sizeof(long long) * (size_t)(itc * k + 1)));
         ACAV_TRY(mi->G.ensure(sizeof(double) * (size_t)(itc * k + 1)));
         if (ex.trace_pos) ACAV_TRY(mi->tr_pos.ensure(sizeof(int) * (size_t)(itc * k + 1)));
@@ -2664,7 +2831,7 @@ static int run_greedy_tiled(acav_mi **mis, int nchunks, const int64_t *const *ca
         }
         FyPlan &fp = plans[(size_t)c];
         { const auto t0 = clk::now();
-        ACAV_TRY(fy_setup(mi, L[c], fp, st));
+        ACAV_TRY(fy_setup(mi, L[c], bcap, fp, st));
         t_fy += ms_since(t0); }
         ntmax = fp.NT > ntmax ? fp.NT : ntmax;
         const size_t ps = fy_part_smem(fp.NT, fp.table.size(), false, pack), pss = fy_part_smem(fp.NT, fp.table.size(), true, pack);
@@ -2710,7 +2877,7 @@ static int run_greedy_tiled(acav_mi **mis, int nchunks, const int64_t *const *ca
         d.tr_ids = ex.trace_ids ? mi->tr_ids.as<long long>() : nullptr;
         d.tr_sc = ex.trace_scores ? mi->tr_sc.as<double>() : nullptr;
         d.L0 = (int)L[c], d.iters = (int)itc, d.ntab = (int)fp.table.size(), d.gsh = fp.gsh, d.NT = fp.NT, d.capg = fp.capg;
-        d.ecap = fp.ecap_lds, d.wcap = fp.wcap, d.D = mi->D, d.C = mi->C, d.P = mi->P, d.pad = 0;
+        d.ecap = fp.ecap_lds, d.wcap = fp.wcap, d.D = mi->D, d.C = mi->C, d.P = mi->P, d.bcap = bcap;
         d.w = mi_weights(mi);
         weighted = weighted || mi->weighted;
     }
@@ -2732,8 +2899,11 @@ static int run_greedy_tiled(acav_mi **mis, int nchunks, const int64_t *const *ca
     }
     const TileChunk *dcd = lead->chunk_desc.as<TileChunk>();
     const int sel_f = sel_mode(B, pmax, k);  // one mode for every chunk of the launch: sized for the largest P and D
-    const size_t sel_smem = sel_layout(B, pmax, dmax, k, sel_f).total;
-    const auto gs_kernel = weighted ? k_fy_gather_select_multi<true> : k_fy_gather_select_multi<false>;
+    size_t sel_smem = 0;
+    ACAV_TRY(sel_smem_checked(B, pmax, dmax, k, sel_f, &sel_smem));
+    const auto gs_kernel = wide ? (weighted ? k_fy_gather_select_multi<true, true> : k_fy_gather_select_multi<false, true>)
+                                : (weighted ? k_fy_gather_select_multi<true, false> : k_fy_gather_select_multi<false, false>);
+    const auto resolve_kernel = wide ? k_fy_resolve_multi<true> : k_fy_resolve_multi<false>;
     if (sel_smem > 48 * 1024)
         ACAV_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(gs_kernel),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)sel_smem));
@@ -2762,7 +2932,7 @@ static int run_greedy_tiled(acav_mi **mis, int nchunks, const int64_t *const *ca
             if (g0 < iters[(size_t)c]) ACAV_TRY(streams[(size_t)c].release(r0[(size_t)c]));  // k_fy_part is the only reader of the draws
         hipLaunchKernelGGL(tile_kernel, dim3((unsigned)ntmax, (unsigned)nchunks, gz), dim3(FYT_THREADS), tile_smem, sf, dcd, (int)g0,
                            (int)dl);
-        hipLaunchKernelGGL(k_fy_resolve_multi, dim3((unsigned)((lt + 255) / 256), (unsigned)nchunks, gz), dim3(256), 0, sf, dcd, (int)g0,
+        hipLaunchKernelGGL(resolve_kernel, dim3((unsigned)((lt + 255) / 256), (unsigned)nchunks, gz), dim3(256), 0, sf, dcd, (int)g0,
                            (int)dl, keep_unselected ? B - k : 0);
         ACAV_HIP_TRY(hipEventRecord(lead->ev_tile[ge], sf));
         // ---- main stream: the group's gathers (each with the selection of the iteration before it), back to back
@@ -2833,8 +3003,8 @@ ACAV_EXPORT int acav_mi_run_greedy_multi(acav_mi **mis, int nchunks, const int64
 {
     ACAV_REQUIRE(mis && nchunks > 0 && candidates && L && ns && subset && rngs && S_out && GAIN_out, ACAV_EINVAL,
                  "NULL argument");
-    ACAV_REQUIRE(B > 0 && B <= SEL_MAXB && k > 0 && k <= B, ACAV_EINVAL, "batch_size %d / selection_size %d out of range", B,
-                 k);
+    ACAV_REQUIRE(B > 0 && B <= SEL_WIDEB && k > 0 && k <= B, ACAV_EINVAL,
+                 "batch_size %d / selection_size %d out of range (1 <= selection_size <= batch_size <= %d)", B, k, SEL_WIDEB);
     acav_mi *lead = mis[0];
     ACAV_REQUIRE(lead, ACAV_EINVAL, "handle is NULL");
     for (int c = 0; c < nchunks; ++c)
@@ -2849,7 +3019,8 @@ ACAV_EXPORT int acav_mi_run_greedy_multi(acav_mi **mis, int nchunks, const int64
             ACAV_REQUIRE(mi->ctx.device == lead->ctx.device, ACAV_EINVAL, "chunk %d lives on another device", c);
             ACAV_REQUIRE(L[c] > 0 && L[c] <= mi->V && ns[c] >= 0 && (ns[c] == 0 || (start && start[c])) && subset[c] >= 0,
                          ACAV_EINVAL, "chunk %d: bad sizes", c);
-            ACAV_REQUIRE((int64_t)B * mi->P <= SEL_MAXBP, ACAV_EINVAL, "chunk %d: B*P exceeds %d", c, SEL_MAXBP);
+            ACAV_REQUIRE((int64_t)B * mi->P <= SEL_MAXBP, ACAV_EINVAL, "chunk %d: batch_size %d x %d pairs exceeds B*P <= %d", c, B, mi->P,
+                         SEL_MAXBP);
             for (int e = 0; e < c; ++e)
                 ACAV_REQUIRE(mis[e] != mi && rngs[e] != rngs[c], ACAV_EINVAL, "chunks must not share a handle or a generator");
             tiled = tiled && L[c] <= FY_TILED_MAX;
@@ -2872,7 +3043,8 @@ ACAV_EXPORT int acav_mi_run_greedy_multi(acav_mi **mis, int nchunks, const int64
         ACAV_REQUIRE(mi->ctx.device == lead->ctx.device, ACAV_EINVAL, "chunk %d lives on another device", c);
         ACAV_REQUIRE(L[c] > 0 && L[c] <= mi->V && ns[c] >= 0 && (ns[c] == 0 || (start && start[c])) && subset[c] >= 0,
                      ACAV_EINVAL, "chunk %d: bad sizes", c);
-        ACAV_REQUIRE((int64_t)B * mi->P <= SEL_MAXBP, ACAV_EINVAL, "chunk %d: B*P exceeds %d", c, SEL_MAXBP);
+        ACAV_REQUIRE((int64_t)B * mi->P <= SEL_MAXBP, ACAV_EINVAL, "chunk %d: batch_size %d x %d pairs exceeds B*P <= %d", c, B, mi->P,
+                         SEL_MAXBP);
         for (int e = 0; e < c; ++e) ACAV_REQUIRE(mis[e] != mi && rngs[e] != rngs[c], ACAV_EINVAL, "chunks must not share a handle or a generator");
         ACAV_HIP_TRY(hipStreamSynchronize(mi->ctx.stream));  // whatever the handle was doing on its own stream is over
         if (ns[c]) ACAV_TRY(acav_mi_add_samples(mi, start[c], ns[c]));
@@ -2905,7 +3077,7 @@ ACAV_EXPORT int acav_mi_run_greedy_multi(acav_mi **mis, int nchunks, const int64
         ACAV_HIP_TRY(hipMemsetAsync(mi->head.p, 0xFF, sizeof(int) * Lc, sc));
         ACAV_HIP_TRY(hipMemsetAsync(mi->g.p, 0xFF, sizeof(int) * Lc, sc));
         ACAV_TRY(mi->mt.ensure(sizeof(unsigned) * 625));
-        ACAV_TRY(mi->batch.ensure(sizeof(int) * SEL_MAXB));
+        ACAV_TRY(mi->batch.ensure(sizeof(int) * (size_t)(B > SEL_MAXB ? B : SEL_MAXB)));
         ACAV_TRY(mi->S.ensure(sizeof(long long) * (size_t)(itc * k + 1)));
         ACAV_TRY(mi->G.ensure(sizeof(double) * (size_t)(itc * k + 1)));
         unsigned mtbuf[625];
@@ -2945,8 +3117,10 @@ ACAV_EXPORT int acav_mi_run_greedy_multi(acav_mi **mis, int nchunks, const int64
     };
     if (iters_max > 0) ACAV_TRY(launch_mt(0));
     const int sel_f = sel_mode(B, pmax, k);
-    const size_t smem = sel_layout(B, pmax, dmax, k, sel_f).total;
-    const auto sel_kernel = weighted ? k_mi_select_multi<true> : k_mi_select_multi<false>;
+    size_t smem = 0;
+    ACAV_TRY(sel_smem_checked(B, pmax, dmax, k, sel_f, &smem));
+    const auto sel_kernel = B > SEL_MAXB ? (weighted ? k_mi_select_multi<true, true> : k_mi_select_multi<false, true>)
+                                         : (weighted ? k_mi_select_multi<true, false> : k_mi_select_multi<false, false>);
     if (smem > 48 * 1024)
         ACAV_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(sel_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                          (int)smem));
@@ -3400,8 +3574,10 @@ static int launch_select(acav_mi *mi, const int *batch, int B, int k, double *sc
                          double *trace_scores, int keep, int *requeue_out)
 {
     const int mode = sel_mode(B, mi->P, k);
-    const size_t smem = sel_layout(B, mi->P, mi->D, k, mode).total;
-    const auto kernel = mi->weighted ? k_mi_select<true> : k_mi_select<false>;
+    size_t smem = 0;
+    ACAV_TRY(sel_smem_checked(B, mi->P, mi->D, k, mode, &smem));
+    const auto kernel = B > SEL_MAXB ? (mi->weighted ? k_mi_select<true, true> : k_mi_select<false, true>)
+                                     : (mi->weighted ? k_mi_select<true, false> : k_mi_select<false, false>);
     if (smem > 48 * 1024)
         ACAV_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                          (int)smem));
@@ -3417,11 +3593,11 @@ static int launch_select(acav_mi *mi, const int *batch, int B, int k, double *sc
 ACAV_EXPORT int acav_mi_score_batch(acav_mi *mi, const int64_t *ids, int B, double *scores_host)
 {
     ACAV_REQUIRE(mi && ids && scores_host, ACAV_EINVAL, "NULL argument");
-    ACAV_REQUIRE(B > 0 && B <= SEL_MAXB && (int64_t)B * mi->P <= SEL_MAXBP, ACAV_EINVAL,
-                 "batch %d x pairs %d outside the supported range (B<=%d, B*P<=%d)", B, mi->P, SEL_MAXB, SEL_MAXBP);
+    ACAV_REQUIRE(B > 0 && B <= SEL_WIDEB && (int64_t)B * mi->P <= SEL_MAXBP, ACAV_EINVAL,
+                 "batch %d x pairs %d outside the supported range (B<=%d, B*P<=%d)", B, mi->P, SEL_WIDEB, SEL_MAXBP);
     ACAV_HIP_TRY(hipSetDevice(mi->ctx.device));
     ACAV_TRY(ids_to_device32(mi, ids, B, mi->stage, mi->ids32));
-    ACAV_TRY(mi->scores.ensure(sizeof(double) * SEL_MAXB));
+    ACAV_TRY(mi->scores.ensure(sizeof(double) * (size_t)(B > SEL_MAXB ? B : SEL_MAXB)));
     ACAV_TRY(launch_select(mi, mi->ids32.as<int>(), B, 0, mi->scores.as<double>(), nullptr, nullptr, nullptr, nullptr,
                            nullptr, nullptr, 0, nullptr));
     ACAV_TRY(from_device(scores_host, mi->scores.p, sizeof(double) * (size_t)B, mi->ctx.stream));
@@ -3454,9 +3630,9 @@ ACAV_EXPORT int acav_mi_run_greedy(acav_mi *mi, const int64_t *candidates, int64
     ACAV_REQUIRE(mi && candidates && rng && S_out && GAIN_out, ACAV_EINVAL, "NULL argument");
     mi->pst_valid = false;  // the batch greedy changes the tables without the pair sums
     ACAV_REQUIRE(L > 0 && L <= mi->V && ns >= 0 && (start || ns == 0) && subset >= 0, ACAV_EINVAL, "bad sizes");
-    ACAV_REQUIRE(B > 0 && B <= SEL_MAXB && k > 0 && k <= B && (int64_t)B * mi->P <= SEL_MAXBP, ACAV_EINVAL,
-                 "batch_size %d / selection_size %d / pairs %d outside the supported range (B<=%d, B*P<=%d)", B, k,
-                 mi->P, SEL_MAXB, SEL_MAXBP);
+    ACAV_REQUIRE(B > 0 && B <= SEL_WIDEB && k > 0 && k <= B && (int64_t)B * mi->P <= SEL_MAXBP, ACAV_EINVAL,
+                 "batch_size %d / selection_size %d / pairs %d out of range (1 <= selection_size <= batch_size <= %d, B*P<=%d)", B, k,
+                 mi->P, SEL_WIDEB, SEL_MAXBP);
     ACAV_HIP_TRY(hipSetDevice(mi->ctx.device));
     // the permutation of every iteration: tiled evaluation (all atomics in LDS; run_greedy_tiled) unless the list is too long
     // for its tile table, or ACAV_FY_LEGACY=1 asks for the global-atomic kernels (k_fy_build / k_fy_apply) below
@@ -3497,7 +3673,7 @@ ACAV_EXPORT int acav_mi_run_greedy(acav_mi *mi, const int64_t *candidates, int64
     ACAV_HIP_TRY(hipMemsetAsync(mi->head.p, 0xFF, sizeof(int) * (size_t)L, st));
     ACAV_HIP_TRY(hipMemsetAsync(mi->g.p, 0xFF, sizeof(int) * (size_t)L, st));
     ACAV_TRY(mi->mt.ensure(sizeof(unsigned) * 625));
-    ACAV_TRY(mi->batch.ensure(sizeof(int) * SEL_MAXB));
+    ACAV_TRY(mi->batch.ensure(sizeof(int) * (size_t)(B > SEL_MAXB ? B : SEL_MAXB)));
     ACAV_TRY(mi->S.ensure(sizeof(long long) * (size_t)cap));
     ACAV_TRY(mi->G.ensure(sizeof(double) * (size_t)cap));
     if (trace_pos) ACAV_TRY(mi->tr_pos.ensure(sizeof(int) * (size_t)(iters * k + 1)));
