@@ -220,17 +220,19 @@ __global__ __launch_bounds__(256) void k_ct_bias_grad(const float *__restrict__ 
 }
 
 // torch.optim.AdamW, amsgrad=True, on the flat parameter buffer: decoupled decay, moments of the ACCUMULATED gradient,
-// running max of the second moment, p -= lr / bc1 * m / (sqrt(vmax) / sqrt(bc2) + eps)
+// running max of the second moment, p -= lr / bc1 * m / (sqrt(vmax) / sqrt(bc2) + eps).  omb1 / omb2 = 1 - beta rounded from
+// double, as torch passes them: 1.0f - 0.999f is 1.3e-5 below 0.001f (6.6e-6 on every update through sqrt(v))
 __global__ __launch_bounds__(256) void k_ct_adamw(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
                                                   float *__restrict__ v, float *__restrict__ vmax, long n, float decay,
-                                                  float b1, float b2, float sqrt_bc2, float eps, float step_size)
+                                                  float b1, float b2, float omb1, float omb2, float sqrt_bc2, float eps,
+                                                  float step_size)
 {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float gi = g[i];
     float pi = p[i] * decay;
-    const float mi = m[i] * b1 + gi * (1.0f - b1);
-    const float vi = v[i] * b2 + (gi * gi) * (1.0f - b2);
+    const float mi = m[i] * b1 + gi * omb1;
+    const float vi = v[i] * b2 + (gi * gi) * omb2;
     const float vm = fmaxf(vmax[i], vi);
     m[i] = mi, v[i] = vi, vmax[i] = vm;
     const float denom = __builtin_sqrtf(vm) / sqrt_bc2 + eps;
@@ -439,7 +441,8 @@ static int ct_step(acav_contrastive *c, double lr)
     const double b1 = 0.9, b2 = 0.999, bc1 = 1.0 - pow(b1, (double)c->step), bc2 = 1.0 - pow(b2, (double)c->step);
     hipLaunchKernelGGL(k_ct_adamw, dim3((unsigned)((c->nparam + 255) / 256)), dim3(256), 0, c->ctx.stream, c->params.as<float>(),
                        c->grads.as<float>(), c->m.as<float>(), c->v.as<float>(), c->vmax.as<float>(), (long)c->nparam,
-                       (float)(1.0 - lr * 0.01), (float)b1, (float)b2, (float)sqrt(bc2), 1e-6f, (float)(lr / bc1));
+                       (float)(1.0 - lr * 0.01), (float)b1, (float)b2, (float)(1.0 - b1), (float)(1.0 - b2), (float)sqrt(bc2), 1e-6f,
+                       (float)(lr / bc1));
     ACAV_HIP_TRY(hipGetLastError());
     return ACAV_OK;
 }
