@@ -4,7 +4,7 @@
 //
 // What one greedy iteration is in the reference, and what runs here instead:
 //   shuffle_candidate_ids (batch.py:29-32)  candidate_ids[torch.randperm(L)]: L-1 MT19937 draws and a
-//        sequential Fisher-Yates.  Here: k_mt_generate continues the same MT19937 stream on the
+//        sequential Fisher-Yates.  Here: k_mt_generate_lanes continues the same MT19937 stream on the
 //        GPU, k_fy_build / k_fy_apply evaluate the SAME swap sequence in parallel (dependence
 //        chains instead of a serial loop) -- integer work, bit-identical by construction.
 //   sample_batch + get_last + calc_MI (batch.py:34-54, mi.py:85-98)  dense [B,P,C,C] fp32 tensors.
@@ -1354,8 +1354,8 @@ __global__ void k_celf_queue_out(int L, const unsigned char *__restrict__ remove
 }
 
 // ------------------------------------------------------------------------------ MT19937
-// Continues torch's CPU generator stream on the device: mt[624] + idx in global memory, one
-// workgroup.  A block of 624 words is regenerated in three dependent phases (k<227, <454, <624).
+// Continues torch's CPU generator stream on the device from a state in global memory, mt[624] + idx (MtStream hands
+// the host generator's state over and takes the final one back).
 __device__ __forceinline__ unsigned mt_temper(unsigned y)
 {
     y ^= y >> 11;
@@ -1375,18 +1375,15 @@ __device__ __forceinline__ unsigned mt_twist(unsigned y) { return (y >> 1) ^ ((y
 // the stream in steps of 623 words (the first 454 words past the state in two plain 227-word steps), one barrier
 // per step.  The window is LINEAR in LDS (all seven operands at constant offsets from one address register) and is
 // slid back every MT_EPOCH steps.  The loop is VALU-issue bound (10 waves on 4 SIMDs), hence the folding, and hence
-// the words are stored RAW: the consumer (k_fy_build) applies the tempering.  `out` must hold n + MT_PAD words.
-// The state is left exactly as the sequential generator would leave it (block holding the last drawn word,
-// idx in 1..624).
+// the words are stored RAW: the consumer (k_fy_build, k_fy_part) applies the tempering.  `out` holds n words: nothing is
+// stored past the last draw.  mt_state is only read: a lane's state moves on by k_mt_jump, and the state the host
+// continues from is cut out of the draws themselves (MtStream::final_state).
 constexpr int MT_THREADS = 640;
 constexpr int MT_WIDE = 623;
 constexpr int MT_BACK = 1078;
 constexpr int MT_EPOCH = 24;                              // wide steps between two slides of the window
 constexpr int MT_WIN = MT_BACK + MT_WIDE * MT_EPOCH;      // 16030 words = 62.6 KB of LDS
-constexpr int MT_GROUP = 8;   // greedy iterations whose draws one launch generates
-constexpr int MT_PAD = 1280;  // the generator completes the 624-word block of the last draw (+ up to 622 words of the last step)
-template <bool WRITE_BACK = true>
-__device__ __forceinline__ void mt_generate_body(unsigned *__restrict__ mt_state, unsigned *__restrict__ out, long long n)
+__device__ __forceinline__ void mt_generate_body(const unsigned *__restrict__ mt_state, unsigned *__restrict__ out, long long n)
 {
     __shared__ unsigned X[MT_WIN];
     const unsigned tid = threadIdx.x;
@@ -1394,8 +1391,7 @@ __device__ __forceinline__ void mt_generate_body(unsigned *__restrict__ mt_state
     const long long p = (long long)mt_state[624];  // first draw = X[p], 0 <= p <= 624
     for (unsigned k = tid; k < 624; k += MT_THREADS) X[k] = mt_state[k];
     const long long q = p + n;                      // one past the last draw
-    const long long base = 624 * ((q - 1) / 624);   // block the sequential generator would hold
-    const long long need = base + 624;              // generate at least up to here
+    const long long need = 624 * ((q - 1) / 624) + 624;  // generate at least up to here: the end of the block holding the last draw
     __syncthreads();
     for (long long m = p + tid; m < 624 && m < q; m += MT_THREADS) out[m - p] = X[m];  // draws left in the block
     unsigned *outp = out + (624 - p);  // raw word of stream index m goes to outp[m - 624]; nothing is stored past q
@@ -1448,17 +1444,6 @@ __device__ __forceinline__ void mt_generate_body(unsigned *__restrict__ mt_state
         __builtin_amdgcn_s_barrier();
     }
     __syncthreads();
-    if (!WRITE_BACK) return;
-    // words [base, base+624) are inside the window: at most 622 words were generated past `need`
-    const unsigned wb = (unsigned)(base - shift);
-    for (unsigned k = tid; k < 624; k += MT_THREADS) mt_state[k] = X[wb + k];
-    if (tid == 0) mt_state[624] = (unsigned)(q - base);
-}
-
-__global__ __launch_bounds__(MT_THREADS) void k_mt_generate(unsigned *__restrict__ mt_state, unsigned *__restrict__ out,
-                                                           long long n)
-{
-    mt_generate_body(mt_state, out, n);
 }
 
 // ONE stream from several workgroups ("lanes").  The stream past the host state is cut into blocks of `blk` words
@@ -1473,7 +1458,7 @@ __global__ __launch_bounds__(MT_THREADS) void k_mt_generate_lanes(unsigned *__re
     ACAV_MI_EMPTY_RETURN
     const long long lane = blockIdx.x;
     const long long extra = lane == 0 ? head : 0;  // leftover draws of the host block, placed right before block 0
-    mt_generate_body<false>(states + lane * 625, out0 + lane * blk - extra, blk + extra);  // the state stays at the block start
+    mt_generate_body(states + lane * 625, out0 + lane * blk - extra, blk + extra);  // the state stays at the block start
 }
 
 // states[dst0 + e] <- the window J words ahead of states[src0 + e] (e = blockIdx.x), J given by its polynomial
@@ -1540,7 +1525,7 @@ __device__ __forceinline__ void fy_build_body(const unsigned *__restrict__ draws
         next[i] = -1;
         return;
     }
-    const int hh = i + (int)(mt_temper(draws[i]) % (unsigned)(L - i));  // k_mt_generate stores raw words
+    const int hh = i + (int)(mt_temper(draws[i]) % (unsigned)(L - i));  // the generator stores raw words
     h[i] = hh;
     if (hh != i) {
         next[i] = atomicExch(&head[hh], i);
@@ -2120,84 +2105,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     }
 }
 
-// ------------------------------------------------------------------ several chunks in lockstep
-// The greedy loop of ONE chunk is a chain of small dependent kernels: most of the GPU idles, and several chunks
-// driven from several host threads do not overlap (the HIP runtime serialises the launches).  Chunks are
-// independent (chunk.py:21-53), so the same three launches per iteration (+ one generator launch per group) can
-// serve a whole batch of them: blockIdx.y (or .x for the one-workgroup kernels) picks the chunk, every per-chunk
-// pointer and size comes from a descriptor array in device memory, and everything that changes per iteration is a
-// function of the iteration number (L_t = L0 - t * dl, buffer parities, offsets).  Same device functions as the
-// single-chunk kernels, hence the same results.
-struct ChunkDesc {
-    const int *asg, *pairs;
-    int *Nc, *ac, *bc;
-    double *SN, *Sa, *Sb;
-    const double *phi;
-    MiScalars *sc;
-    int *A[2];
-    unsigned *draws[2];
-    int *h, *next, *head[2], *g[2];
-    unsigned *mt;
-    int *batch;
-    long long *S;
-    double *G;
-    int D, C, P, L0, iters;
-    int wt;  // 1: the chunk has pair weights, fp32 [P] right behind its pairs (pairs + 2 P; acav_mi_set_pair_weights).  (Not a
-             // pointer: the kernels copy the descriptor to scratch, and a larger one would grow every unweighted kernel's scratch)
-};
-__device__ __forceinline__ const float *chunk_weights(const ChunkDesc &c)
-{
-    return c.wt ? reinterpret_cast<const float *>(c.pairs + 2 * (size_t)c.P) : nullptr;
-}
-
-__device__ __forceinline__ long long chunk_draws(const ChunkDesc &c, int t0, int t1, int dl)
-{  // draws of iterations [t0, t1) of the chunk: sum of (L_t - 1)
-    long long tot = 0;
-    for (int t = t0; t < t1 && t < c.iters; ++t) {
-        const int lt = c.L0 - t * dl;
-        tot += lt > 1 ? lt - 1 : 0;
-    }
-    return tot;
-}
-
-__global__ __launch_bounds__(MT_THREADS) void k_mt_generate_multi(const ChunkDesc *__restrict__ cd, int group, int dl)
-{
-    const ChunkDesc c = cd[blockIdx.x];
-    const long long n = chunk_draws(c, group * MT_GROUP, (group + 1) * MT_GROUP, dl);
-    if (n > 0) mt_generate_body(c.mt, c.draws[group & 1], n);
-}
-
-__global__ __launch_bounds__(256) void k_fy_build_multi(const ChunkDesc *__restrict__ cd, int it, int dl)
-{
-    const ChunkDesc c = cd[blockIdx.y];
-    if (it >= c.iters) return;
-    const int group = it / MT_GROUP;
-    const unsigned *draws = c.draws[group & 1] + chunk_draws(c, group * MT_GROUP, it, dl);
-    fy_build_body(draws, c.L0 - it * dl, c.h, c.head[it & 1], c.next, c.g[it & 1], (int)(blockIdx.x * blockDim.x + threadIdx.x));
-}
-
-__global__ __launch_bounds__(256) void k_fy_apply_multi(const ChunkDesc *__restrict__ cd, int it, int dl, int B)
-{
-    const ChunkDesc c = cd[blockIdx.y];
-    if (it >= c.iters) return;
-    fy_apply_body(c.A[it & 1], c.L0 - it * dl, B, c.h, c.head[it & 1], c.next, c.g[it & 1], c.batch, c.A[(it + 1) & 1],
-                  c.head[(it + 1) & 1], c.g[(it + 1) & 1], (int)(blockIdx.x * blockDim.x + threadIdx.x));
-}
-
-template <bool W, bool WIDE>
-__global__ __launch_bounds__(256) void k_mi_select_multi(const ChunkDesc *__restrict__ cd, int it, int dl, int B, int k,
-                                                         int mode, int keep_unselected)
-{
-    const ChunkDesc c = cd[blockIdx.x];
-    if (it >= c.iters) return;
-    __shared__ SelSharedOf<W> ss;
-    const float *pw = W ? chunk_weights(c) : nullptr;
-    mi_select_stage<W>(ss, c.P, c.pairs, c.SN, c.Sa, c.Sb, c.sc, pw);
-    mi_select_body<W, WIDE>(ss, c.asg, c.D, c.C, c.P, c.pairs, c.batch, 0, nullptr, B, k, mode, c.Nc, c.ac, c.bc, c.SN, c.Sa, c.Sb, c.phi,
-                            c.sc, nullptr, c.S + (size_t)it * k, c.G + (size_t)it * k, nullptr, nullptr, nullptr, nullptr,
-                            keep_unselected, c.A[(it + 1) & 1] + (c.L0 - it * dl - B), 1, pw);
-}
-
 __global__ void k_i64_to_i32(const long long *__restrict__ in, int *__restrict__ out, long long n)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2214,7 +2121,7 @@ struct acav_mi {
     DevBuf asg, pairs, Nc, ac, bc, SN, Sa, Sb, phi, scalars;
     DevBuf stage, ids32, scores;
     // greedy buffers
-    DevBuf A0, A1, draws, draws2, h, head, head2, next, g, g2, mt, batch, S, G, tr_pos, tr_ids, tr_sc, forced;
+    DevBuf A0, A1, h, head, head2, next, g, g2, batch, S, G, tr_pos, tr_ids, tr_sc, forced;
     DevBuf removed, blockbest, ticket, tr_am;  // exact greedy
     DevBuf celf_val, celf_stamp, celf_bv, celf_bst, celf_bp, celf_state, celf_lk, celf_qout;  // CELF queue (acav_mi_run_celf)
     DevBuf celf_fresh, celf_ks, celf_ks2, celf_kv, celf_kv2, celf_i0, celf_i1, celf_i2, celf_d, celf_pm, celf_dn, celf_tmp;  // its dense pick
@@ -2553,7 +2460,7 @@ static bool mi_streams_share_queue(hipStream_t a, hipStream_t b)
     }
     return best >= 160.0;
 }
-static void mi_separate_queues(acav_mi *mi, bool own_content, int class_mt, int class_fy);
+static void mi_separate_queues(acav_mi *mi);
 static int mi_ensure_streams(acav_mi *mi);  // st_mt / st_fy on first need
 
 
@@ -2646,7 +2553,7 @@ ACAV_EXPORT int acav_mi_create(acav_mi **out, int device, const int64_t *assignm
     return ACAV_OK;
 }
 
-static int mi_ensure_gen_events(acav_mi *mi)  // the generator ring's events of THIS handle's draws (MtStream::plan, legacy loop)
+static int mi_ensure_gen_events(acav_mi *mi)  // the generator ring's events of THIS handle's draws (MtStream::plan)
 {
     for (int q = 0; q < 2; ++q) {
         if (!mi->ev_mt[q]) ACAV_HIP_TRY(hipEventCreateWithFlags(&mi->ev_mt[q], hipEventDisableTiming));
@@ -2676,10 +2583,9 @@ static int mi_ensure_streams(acav_mi *mi)
     return ACAV_OK;
 }
 
-static void mi_separate_queues(acav_mi *mi, bool own_content, int class_mt, int class_fy)
+static void mi_separate_queues(acav_mi *mi)
 {
     if (mi_ensure_streams(mi) != ACAV_OK) return;
-    (void)own_content, (void)class_mt, (void)class_fy;
     std::vector<hipStream_t> parked;
     for (int attempt = 0; attempt < 6; ++attempt) {
         hipStream_t *victim = nullptr;
@@ -2736,6 +2642,63 @@ struct TiledExtras {
     int64_t max_iters = -1;
 };
 
+// The argument checks of one chunk, shared by both entry points (c < 0: the single-chunk call, which names no chunk).
+static int check_chunk_args(int c, const acav_mi *mi, const int64_t *candidates, int64_t L, const int64_t *start, int ns,
+                            int64_t subset, const acav_rng *rng, const int64_t *S_out, const double *GAIN_out)
+{
+    char at[24] = "";
+    if (c >= 0) snprintf(at, sizeof(at), "chunk %d: ", c);
+    ACAV_REQUIRE(mi && candidates && rng && S_out && GAIN_out, ACAV_EINVAL, "%sNULL argument", at);
+    ACAV_REQUIRE(L > 0 && L <= mi->V && ns >= 0 && (start || ns == 0) && subset >= 0, ACAV_EINVAL, "%sbad sizes", at);
+    return ACAV_OK;
+}
+
+// The iteration plan of one chunk: how many iterations the greedy loop runs and how many MT19937 draws their
+// permutations take.  Every L_t is known on the host (the list shrinks by dl per iteration: no device feedback).
+struct GreedyPlan {
+    int64_t iters = 0, draws = 0;
+    int64_t short_l = -1;  // >= 0: the list is down to this many candidates, fewer than a batch, with the subset not yet full (ACAV_ERANGE)
+};
+static GreedyPlan greedy_plan(int64_t L, int64_t subset, int B, int k, int64_t dl, int64_t max_iters)
+{
+    GreedyPlan gp;
+    int64_t l = L;
+    for (int64_t nS = 0; nS < subset && (max_iters < 0 || gp.iters < max_iters); nS += k, l -= dl, ++gp.iters) {
+        if (l < B) {
+            gp.short_l = l;
+            break;
+        }
+        gp.draws += l > 1 ? l - 1 : 0;
+    }
+    return gp;
+}
+
+// Enqueues the copies of one chunk's results (S, GAIN, the traces) to the host on `st` and fills its counts.
+static int read_back(acav_mi *mi, hipStream_t st, int64_t iters, int64_t subset, int B, int k, int64_t *S_out, double *GAIN_out,
+                     const TiledExtras &ex, int64_t *n_selected, int64_t *n_iters)
+{
+    const int64_t nsel = iters * k < subset ? iters * k : subset;
+    if (iters > 0) {
+        ACAV_HIP_TRY(hipMemcpyAsync(S_out, mi->S.p, sizeof(long long) * (size_t)nsel, hipMemcpyDeviceToHost, st));
+        ACAV_HIP_TRY(hipMemcpyAsync(GAIN_out, mi->G.p, sizeof(double) * (size_t)(iters * k), hipMemcpyDeviceToHost, st));
+        if (ex.trace_pos)
+            ACAV_HIP_TRY(hipMemcpyAsync(ex.trace_pos, mi->tr_pos.p, sizeof(int) * (size_t)(iters * k), hipMemcpyDeviceToHost, st));
+        if (ex.trace_ids)
+            ACAV_HIP_TRY(hipMemcpyAsync(ex.trace_ids, mi->tr_ids.p, sizeof(long long) * (size_t)(iters * B), hipMemcpyDeviceToHost, st));
+        if (ex.trace_scores)
+            ACAV_HIP_TRY(hipMemcpyAsync(ex.trace_scores, mi->tr_sc.p, sizeof(double) * (size_t)(iters * B), hipMemcpyDeviceToHost, st));
+    }
+    if (n_selected) *n_selected = nsel;
+    if (n_iters) *n_iters = iters;
+    return ACAV_OK;
+}
+
+// The greedy run of ONE chunk on the global-atomic Fisher-Yates kernels (k_fy_build / k_fy_apply) and k_mi_select, on the
+// handle's own streams: lists beyond FY_TILED_MAX, and ACAV_FY_LEGACY=1.
+static int run_greedy_legacy(acav_mi *mi, const int64_t *candidates, int64_t L, const int64_t *start, int ns, int64_t subset,
+                             int B, int k, int keep_unselected, acav_rng *rng, int64_t *S_out, double *GAIN_out,
+                             int64_t *n_selected, int64_t *n_iters, const TiledExtras &ex);
+
 // The greedy run on the lane generator + tiled Fisher-Yates kernels: one chunk (acav_mi_run_greedy) or several independent
 // chunks in lockstep (acav_mi_run_greedy_multi; one handle, candidate list, start set, subset size and generator each;
 // every list within FY_TILED_MAX).  All handles live on the same device; the first handle's streams carry the work.
@@ -2758,7 +2721,7 @@ static int run_greedy_tiled(acav_mi **mis, int nchunks, const int64_t *const *ca
     // (3.53 / 2.48 / 2.50): tools/exp/NOTES_r06.md section 5.
     if (nchunks == 1 && lead->queue_probe_pending && L[0] >= 250000) {
         const char *vq = getenv("ACAV_MI_QUEUE_PROBE");
-        if (!(vq && vq[0] == '0')) mi_separate_queues(lead, true, 0, 0);
+        if (!(vq && vq[0] == '0')) mi_separate_queues(lead);
         lead->queue_probe_pending = false;
     }
     ACAV_TRY(mi_ensure_streams(lead));
@@ -2794,16 +2757,11 @@ static int run_greedy_tiled(acav_mi **mis, int nchunks, const int64_t *const *ca
         if (ns[c]) ACAV_TRY(acav_mi_add_samples(mi, start[c], ns[c]));  // batch.py:215
         t_add += ms_since(t0); }
         // plan: the number of iterations and every L_t are known on the host (no device feedback)
-        int64_t nS = 0, l = L[c], itc = 0, draws = 0;
-        while (nS < subset[c] && (ex.max_iters < 0 || itc < ex.max_iters)) {
-            ACAV_REQUIRE(l >= B, ACAV_ERANGE,
-                         "chunk %d: %lld candidates left < batch_size %d: the reference's topk(k=floor(B/k*B')) raises here "
-                         "(batch.py:143-150)", c, (long long)l, B);
-            draws += l > 1 ? l - 1 : 0;
-            nS += k;
-            l -= dl;
-            ++itc;
-        }
+        const GreedyPlan gp = greedy_plan(L[c], subset[c], B, k, dl, ex.max_iters);
+        ACAV_REQUIRE(gp.short_l < 0, ACAV_ERANGE,
+                     "chunk %d: %lld candidates left < batch_size %d: the reference's topk(k=floor(B/k*B')) raises here "
+                     "(batch.py:143-150)", c, (long long)gp.short_l, B);
+        const int64_t itc = gp.iters, draws = gp.draws;
         iters[(size_t)c] = itc;
         iters_max = itc > iters_max ? itc : iters_max;
         lmax = L[c] > lmax ? L[c] : lmax;
@@ -2961,21 +2919,8 @@ static int run_greedy_tiled(acav_mi **mis, int nchunks, const int64_t *const *ca
     }
     const auto t_tail0 = clk::now();
     for (int c = 0; c < nchunks; ++c) {
-        acav_mi *mi = mis[c];
-        const int64_t itc = iters[(size_t)c];
-        const int64_t nsel = itc * k < subset[c] ? itc * k : subset[c];
-        if (itc > 0) {
-            ACAV_HIP_TRY(hipMemcpyAsync(S_out[c], mi->S.p, sizeof(long long) * (size_t)nsel, hipMemcpyDeviceToHost, st));
-            ACAV_HIP_TRY(hipMemcpyAsync(GAIN_out[c], mi->G.p, sizeof(double) * (size_t)(itc * k), hipMemcpyDeviceToHost, st));
-            if (ex.trace_pos)
-                ACAV_HIP_TRY(hipMemcpyAsync(ex.trace_pos, mi->tr_pos.p, sizeof(int) * (size_t)(itc * k), hipMemcpyDeviceToHost, st));
-            if (ex.trace_ids)
-                ACAV_HIP_TRY(hipMemcpyAsync(ex.trace_ids, mi->tr_ids.p, sizeof(long long) * (size_t)(itc * B), hipMemcpyDeviceToHost, st));
-            if (ex.trace_scores)
-                ACAV_HIP_TRY(hipMemcpyAsync(ex.trace_scores, mi->tr_sc.p, sizeof(double) * (size_t)(itc * B), hipMemcpyDeviceToHost, st));
-        }
-        if (n_selected) n_selected[c] = nsel;
-        if (n_iters) n_iters[c] = itc;
+        ACAV_TRY(read_back(mis[c], st, iters[(size_t)c], subset[c], B, k, S_out[c], GAIN_out[c], ex, n_selected ? n_selected + c : nullptr,
+                           n_iters ? n_iters + c : nullptr));
     }
     ACAV_HIP_TRY(hipStreamSynchronize(st));
     for (int c = 0; c < nchunks; ++c) {  // every generator continues on the host where its chunk stopped drawing
@@ -3010,153 +2955,36 @@ ACAV_EXPORT int acav_mi_run_greedy_multi(acav_mi **mis, int nchunks, const int64
     for (int c = 0; c < nchunks; ++c)
         if (mis[c]) mis[c]->pst_valid = false;  // the batch greedy changes the tables without the pair sums
     ACAV_HIP_TRY(hipSetDevice(lead->ctx.device));
-    {   // validation common to both evaluations, then the tiled one unless a list is too long for it (or ACAV_FY_LEGACY=1)
-        const char *legacy = getenv("ACAV_FY_LEGACY");
-        bool tiled = !(legacy && legacy[0] == '1');
-        for (int c = 0; c < nchunks; ++c) {
-            acav_mi *mi = mis[c];
-            ACAV_REQUIRE(mi && candidates[c] && rngs[c] && S_out[c] && GAIN_out[c], ACAV_EINVAL, "chunk %d: NULL argument", c);
-            ACAV_REQUIRE(mi->ctx.device == lead->ctx.device, ACAV_EINVAL, "chunk %d lives on another device", c);
-            ACAV_REQUIRE(L[c] > 0 && L[c] <= mi->V && ns[c] >= 0 && (ns[c] == 0 || (start && start[c])) && subset[c] >= 0,
-                         ACAV_EINVAL, "chunk %d: bad sizes", c);
-            ACAV_REQUIRE((int64_t)B * mi->P <= SEL_MAXBP, ACAV_EINVAL, "chunk %d: batch_size %d x %d pairs exceeds B*P <= %d", c, B, mi->P,
-                         SEL_MAXBP);
-            for (int e = 0; e < c; ++e)
-                ACAV_REQUIRE(mis[e] != mi && rngs[e] != rngs[c], ACAV_EINVAL, "chunks must not share a handle or a generator");
-            tiled = tiled && L[c] <= FY_TILED_MAX;
-        }
-        if (tiled)
-            return run_greedy_tiled(mis, nchunks, candidates, L, start, ns, subset, B, k, keep_unselected, rngs, S_out, GAIN_out,
-                                    n_selected, n_iters, TiledExtras());
-    }
-    ACAV_TRY(mi_ensure_streams(lead));
-    hipStream_t st = lead->ctx.stream, smt = lead->st_mt;
-    const int64_t dl = B - (keep_unselected ? B - k : 0);
-    std::vector<ChunkDesc> desc((size_t)nchunks);
-    std::vector<int64_t> iters((size_t)nchunks, 0);
-    int64_t iters_max = 0, lmax = 0;
-    int pmax = 1, dmax = 1;
-    bool weighted = false;  // some chunk has pair weights: the weighted selection for the whole launch
+    // the tiled evaluation, chunks in lockstep, unless a list is too long for it (or ACAV_FY_LEGACY=1)
+    const char *legacy = getenv("ACAV_FY_LEGACY");
+    bool tiled = !(legacy && legacy[0] == '1');
     for (int c = 0; c < nchunks; ++c) {
         acav_mi *mi = mis[c];
-        ACAV_REQUIRE(mi && candidates[c] && rngs[c] && S_out[c] && GAIN_out[c], ACAV_EINVAL, "chunk %d: NULL argument", c);
+        ACAV_TRY(check_chunk_args(c, mi, candidates[c], L[c], start ? start[c] : nullptr, ns[c], subset[c], rngs[c], S_out[c], GAIN_out[c]));
         ACAV_REQUIRE(mi->ctx.device == lead->ctx.device, ACAV_EINVAL, "chunk %d lives on another device", c);
-        ACAV_REQUIRE(L[c] > 0 && L[c] <= mi->V && ns[c] >= 0 && (ns[c] == 0 || (start && start[c])) && subset[c] >= 0,
-                     ACAV_EINVAL, "chunk %d: bad sizes", c);
         ACAV_REQUIRE((int64_t)B * mi->P <= SEL_MAXBP, ACAV_EINVAL, "chunk %d: batch_size %d x %d pairs exceeds B*P <= %d", c, B, mi->P,
-                         SEL_MAXBP);
-        for (int e = 0; e < c; ++e) ACAV_REQUIRE(mis[e] != mi && rngs[e] != rngs[c], ACAV_EINVAL, "chunks must not share a handle or a generator");
-        ACAV_HIP_TRY(hipStreamSynchronize(mi->ctx.stream));  // whatever the handle was doing on its own stream is over
-        if (ns[c]) ACAV_TRY(acav_mi_add_samples(mi, start[c], ns[c]));
-        int64_t nS = 0, l = L[c], itc = 0;
-        while (nS < subset[c]) {
-            ACAV_REQUIRE(l >= B, ACAV_ERANGE, "chunk %d: %lld candidates left < batch_size %d (batch.py:143-150)", c,
-                         (long long)l, B);
-            nS += k;
-            l -= dl;
-            ++itc;
-        }
-        iters[(size_t)c] = itc;
-        iters_max = itc > iters_max ? itc : iters_max;
-        lmax = L[c] > lmax ? L[c] : lmax;
-        pmax = mi->P > pmax ? mi->P : pmax;
-        dmax = mi->D > dmax ? mi->D : dmax;
-        const size_t Lc = (size_t)L[c];
-        hipStream_t sc = mi->ctx.stream;
-        ACAV_TRY(mi->A0.ensure(sizeof(int) * (Lc + B)));
-        ACAV_TRY(ids_to_device32(mi, candidates[c], L[c], mi->stage, mi->A0));
-        ACAV_TRY(mi->A1.ensure(sizeof(int) * (Lc + B)));
-        ACAV_TRY(mi->draws.ensure(sizeof(unsigned) * (Lc * MT_GROUP + MT_PAD)));
-        ACAV_TRY(mi->draws2.ensure(sizeof(unsigned) * (Lc * MT_GROUP + MT_PAD)));
-        ACAV_TRY(mi->h.ensure(sizeof(int) * Lc));
-        ACAV_TRY(mi->head.ensure(sizeof(int) * Lc));
-        ACAV_TRY(mi->next.ensure(sizeof(int) * Lc));
-        ACAV_TRY(mi->g.ensure(sizeof(int) * Lc));
-        ACAV_TRY(mi->head2.ensure(sizeof(int) * Lc));
-        ACAV_TRY(mi->g2.ensure(sizeof(int) * Lc));
-        ACAV_HIP_TRY(hipMemsetAsync(mi->head.p, 0xFF, sizeof(int) * Lc, sc));
-        ACAV_HIP_TRY(hipMemsetAsync(mi->g.p, 0xFF, sizeof(int) * Lc, sc));
-        ACAV_TRY(mi->mt.ensure(sizeof(unsigned) * 625));
-        ACAV_TRY(mi->batch.ensure(sizeof(int) * (size_t)(B > SEL_MAXB ? B : SEL_MAXB)));
-        ACAV_TRY(mi->S.ensure(sizeof(long long) * (size_t)(itc * k + 1)));
-        ACAV_TRY(mi->G.ensure(sizeof(double) * (size_t)(itc * k + 1)));
-        unsigned mtbuf[625];
-        int idx = 0;
-        ACAV_TRY(acav_rng_get_state(rngs[c], mtbuf, &idx));
-        mtbuf[624] = (unsigned)idx;
-        ACAV_HIP_TRY(hipMemcpyAsync(mi->mt.p, mtbuf, sizeof(mtbuf), hipMemcpyHostToDevice, sc));
-        ACAV_HIP_TRY(hipStreamSynchronize(sc));  // mtbuf is a local; the lead's streams take over from here
-        ChunkDesc &d = desc[(size_t)c];
-        d.asg = mi->asg.as<int>(), d.pairs = mi->pairs.as<int>();
-        d.Nc = mi->Nc.as<int>(), d.ac = mi->ac.as<int>(), d.bc = mi->bc.as<int>();
-        d.SN = mi->SN.as<double>(), d.Sa = mi->Sa.as<double>(), d.Sb = mi->Sb.as<double>();
-        d.phi = mi->phi.as<double>(), d.sc = mi->scalars.as<MiScalars>();
-        d.A[0] = mi->A0.as<int>(), d.A[1] = mi->A1.as<int>();
-        d.draws[0] = mi->draws.as<unsigned>(), d.draws[1] = mi->draws2.as<unsigned>();
-        d.h = mi->h.as<int>(), d.next = mi->next.as<int>();
-        d.head[0] = mi->head.as<int>(), d.head[1] = mi->head2.as<int>();
-        d.g[0] = mi->g.as<int>(), d.g[1] = mi->g2.as<int>();
-        d.mt = mi->mt.as<unsigned>(), d.batch = mi->batch.as<int>();
-        d.S = mi->S.as<long long>(), d.G = mi->G.as<double>();
-        d.D = mi->D, d.C = mi->C, d.P = mi->P, d.L0 = (int)L[c], d.iters = (int)itc, d.wt = mi->weighted ? 1 : 0;
-        weighted = weighted || mi->weighted;
+                     SEL_MAXBP);
+        for (int e = 0; e < c; ++e)
+            ACAV_REQUIRE(mis[e] != mi && rngs[e] != rngs[c], ACAV_EINVAL, "chunks must not share a handle or a generator");
+        tiled = tiled && L[c] <= FY_TILED_MAX;
     }
-    ACAV_TRY(lead->chunk_desc.ensure(sizeof(ChunkDesc) * (size_t)nchunks));
-    ACAV_HIP_TRY(hipMemcpyAsync(lead->chunk_desc.p, desc.data(), sizeof(ChunkDesc) * (size_t)nchunks, hipMemcpyHostToDevice, st));
-    ACAV_HIP_TRY(hipStreamSynchronize(st));  // desc is a local
-    const ChunkDesc *dcd = lead->chunk_desc.as<ChunkDesc>();
-    const int64_t ngroups = (iters_max + MT_GROUP - 1) / MT_GROUP;
-    ACAV_HIP_TRY(hipEventRecord(lead->ev_used[0], st));
-    ACAV_HIP_TRY(hipStreamWaitEvent(smt, lead->ev_used[0], 0));
-    auto launch_mt = [&](int64_t g_) -> int {
-        const int cur_ = (int)(g_ & 1);
-        if (g_ >= 2) ACAV_HIP_TRY(hipStreamWaitEvent(smt, lead->ev_used[cur_], 0));  // the readers of group g_-2 are done
-        hipLaunchKernelGGL(k_mt_generate_multi, dim3((unsigned)nchunks), dim3(MT_THREADS), 0, smt, dcd, (int)g_, (int)dl);
-        ACAV_HIP_TRY(hipEventRecord(lead->ev_mt[cur_], smt));
-        return ACAV_OK;
-    };
-    if (iters_max > 0) ACAV_TRY(launch_mt(0));
-    const int sel_f = sel_mode(B, pmax, k);
-    size_t smem = 0;
-    ACAV_TRY(sel_smem_checked(B, pmax, dmax, k, sel_f, &smem));
-    const auto sel_kernel = B > SEL_MAXB ? (weighted ? k_mi_select_multi<true, true> : k_mi_select_multi<false, true>)
-                                         : (weighted ? k_mi_select_multi<true, false> : k_mi_select_multi<false, false>);
-    if (smem > 48 * 1024)
-        ACAV_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(sel_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)smem));
-    for (int64_t it = 0; it < iters_max; ++it) {
-        const int64_t grp = it / MT_GROUP;
-        const int cur = (int)(grp & 1);
-        if (it % MT_GROUP == 0) {
-            if (grp + 1 < ngroups) ACAV_TRY(launch_mt(grp + 1));
-            ACAV_HIP_TRY(hipStreamWaitEvent(st, lead->ev_mt[cur], 0));
-        }
-        const int64_t lt = lmax - it * dl;  // the longest list still in play bounds the grid
-        const dim3 grid((unsigned)((lt + 255) / 256), (unsigned)nchunks);
-        hipLaunchKernelGGL(k_fy_build_multi, grid, dim3(256), 0, st, dcd, (int)it, (int)dl);
-        if (it % MT_GROUP == MT_GROUP - 1 || it + 1 == iters_max) ACAV_HIP_TRY(hipEventRecord(lead->ev_used[cur], st));
-        hipLaunchKernelGGL(k_fy_apply_multi, grid, dim3(256), 0, st, dcd, (int)it, (int)dl, B);
-        hipLaunchKernelGGL(sel_kernel, dim3((unsigned)nchunks), dim3(256), smem, st, dcd, (int)it, (int)dl, B, k, sel_f,
-                           keep_unselected);
-    }
-    ACAV_HIP_TRY(hipGetLastError());
-    ACAV_HIP_TRY(hipStreamSynchronize(smt));
+    if (tiled)
+        return run_greedy_tiled(mis, nchunks, candidates, L, start, ns, subset, B, k, keep_unselected, rngs, S_out, GAIN_out,
+                                n_selected, n_iters, TiledExtras());
+    // Otherwise the chunks run one after another, each as a single-chunk call would run it (run_greedy_legacy): lockstep is there
+    // to share launch latency among short lists, and the legacy kernels are for long ones.  Every chunk is planned before the
+    // first one starts: a chunk whose candidates run out leaves no earlier chunk selected.
+    const int64_t dl = B - (keep_unselected ? B - k : 0);
     for (int c = 0; c < nchunks; ++c) {
-        acav_mi *mi = mis[c];
-        const int64_t itc = iters[(size_t)c];
-        const int64_t nsel = itc * k < subset[c] ? itc * k : subset[c];
-        if (itc > 0) {
-            ACAV_HIP_TRY(hipMemcpyAsync(S_out[c], mi->S.p, sizeof(long long) * (size_t)nsel, hipMemcpyDeviceToHost, st));
-            ACAV_HIP_TRY(hipMemcpyAsync(GAIN_out[c], mi->G.p, sizeof(double) * (size_t)(itc * k), hipMemcpyDeviceToHost, st));
-        }
-        if (n_selected) n_selected[c] = nsel;
-        if (n_iters) n_iters[c] = itc;
+        const GreedyPlan gp = greedy_plan(L[c], subset[c], B, k, dl, -1);
+        ACAV_REQUIRE(gp.short_l < 0, ACAV_ERANGE, "chunk %d: %lld candidates left < batch_size %d (batch.py:143-150)", c,
+                     (long long)gp.short_l, B);
     }
-    ACAV_HIP_TRY(hipStreamSynchronize(st));
-    for (int c = 0; c < nchunks; ++c) {  // every generator continues on the host where its chunk stopped drawing
-        unsigned mtbuf[625];
-        ACAV_HIP_TRY(hipMemcpy(mtbuf, mis[c]->mt.p, sizeof(mtbuf), hipMemcpyDeviceToHost));
-        ACAV_TRY(acav_rng_set_state(rngs[c], mtbuf, (int)mtbuf[624]));
+    for (int c = 0; c < nchunks; ++c) {
+        ACAV_HIP_TRY(hipStreamSynchronize(mis[c]->ctx.stream));  // whatever the handle was doing on its own stream is over
+        ACAV_TRY(run_greedy_legacy(mis[c], candidates[c], L[c], start ? start[c] : nullptr, ns[c], subset[c], B, k, keep_unselected,
+                                   rngs[c], S_out[c], GAIN_out[c], n_selected ? n_selected + c : nullptr,
+                                   n_iters ? n_iters + c : nullptr, TiledExtras()));
     }
     return ACAV_OK;
 }
@@ -3627,40 +3455,36 @@ ACAV_EXPORT int acav_mi_run_greedy(acav_mi *mi, const int64_t *candidates, int64
                                    int64_t *trace_ids, double *trace_scores, int32_t *trace_pos,
                                    const int32_t *forced_pos, int64_t max_iters)
 {
-    ACAV_REQUIRE(mi && candidates && rng && S_out && GAIN_out, ACAV_EINVAL, "NULL argument");
+    ACAV_TRY(check_chunk_args(-1, mi, candidates, L, start, ns, subset, rng, S_out, GAIN_out));
     mi->pst_valid = false;  // the batch greedy changes the tables without the pair sums
-    ACAV_REQUIRE(L > 0 && L <= mi->V && ns >= 0 && (start || ns == 0) && subset >= 0, ACAV_EINVAL, "bad sizes");
     ACAV_REQUIRE(B > 0 && B <= SEL_WIDEB && k > 0 && k <= B && (int64_t)B * mi->P <= SEL_MAXBP, ACAV_EINVAL,
                  "batch_size %d / selection_size %d / pairs %d out of range (1 <= selection_size <= batch_size <= %d, B*P<=%d)", B, k,
                  mi->P, SEL_WIDEB, SEL_MAXBP);
     ACAV_HIP_TRY(hipSetDevice(mi->ctx.device));
+    TiledExtras ex;
+    ex.trace_ids = trace_ids, ex.trace_scores = trace_scores, ex.trace_pos = trace_pos, ex.forced_pos = forced_pos;
+    ex.max_iters = max_iters;
     // the permutation of every iteration: tiled evaluation (all atomics in LDS; run_greedy_tiled) unless the list is too long
-    // for its tile table, or ACAV_FY_LEGACY=1 asks for the global-atomic kernels (k_fy_build / k_fy_apply) below
+    // for its tile table, or ACAV_FY_LEGACY=1 asks for the global-atomic kernels (run_greedy_legacy)
     const char *legacy = getenv("ACAV_FY_LEGACY");
-    if (L <= FY_TILED_MAX && !(legacy && legacy[0] == '1')) {
-        TiledExtras ex;
-        ex.trace_ids = trace_ids, ex.trace_scores = trace_scores, ex.trace_pos = trace_pos, ex.forced_pos = forced_pos;
-        ex.max_iters = max_iters;
+    if (L <= FY_TILED_MAX && !(legacy && legacy[0] == '1'))
         return run_greedy_tiled(&mi, 1, &candidates, &L, &start, &ns, &subset, B, k, keep_unselected, &rng, &S_out, &GAIN_out,
                                 n_selected, n_iters, ex);
-    }
-    hipStream_t st = mi->ctx.stream;
-    if (ns) ACAV_TRY(acav_mi_add_samples(mi, start, ns));  // batch.py:215
+    return run_greedy_legacy(mi, candidates, L, start, ns, subset, B, k, keep_unselected, rng, S_out, GAIN_out, n_selected, n_iters, ex);
+}
 
-    // plan: the number of iterations and every L_t are known on the host (no device feedback)
-    int64_t iters = 0;
-    {
-        int64_t nS = 0, l = L;
-        while (nS < subset && (max_iters < 0 || iters < max_iters)) {
-            ACAV_REQUIRE(l >= B, ACAV_ERANGE,
-                         "%lld candidates left < batch_size %d: the reference's topk(k=floor(B/k*B')) raises here "
-                         "(batch.py:143-150)", (long long)l, B);
-            nS += k;
-            l = l - B + (keep_unselected ? B - k : 0);
-            ++iters;
-        }
-    }
-    const int64_t cap = iters * k + 1;
+static int run_greedy_legacy(acav_mi *mi, const int64_t *candidates, int64_t L, const int64_t *start, int ns, int64_t subset,
+                             int B, int k, int keep_unselected, acav_rng *rng, int64_t *S_out, double *GAIN_out,
+                             int64_t *n_selected, int64_t *n_iters, const TiledExtras &ex)
+{
+    hipStream_t st = mi->ctx.stream;
+    const int64_t dl = B - (keep_unselected ? B - k : 0);  // candidates consumed per iteration
+    if (ns) ACAV_TRY(acav_mi_add_samples(mi, start, ns));  // batch.py:215
+    const GreedyPlan gp = greedy_plan(L, subset, B, k, dl, ex.max_iters);
+    ACAV_REQUIRE(gp.short_l < 0, ACAV_ERANGE,
+                 "%lld candidates left < batch_size %d: the reference's topk(k=floor(B/k*B')) raises here "
+                 "(batch.py:143-150)", (long long)gp.short_l, B);
+    const int64_t iters = gp.iters;
     ACAV_TRY(mi->A0.ensure(sizeof(int) * (size_t)(L + B)));  // before the conversion: ensure() does not copy
     ACAV_TRY(ids_to_device32(mi, candidates, L, mi->stage, mi->A0));
     ACAV_TRY(mi->A1.ensure(sizeof(int) * (size_t)(L + B)));
@@ -3672,39 +3496,31 @@ ACAV_EXPORT int acav_mi_run_greedy(acav_mi *mi, const int64_t *candidates, int64
     ACAV_TRY(mi->g2.ensure(sizeof(int) * (size_t)L));
     ACAV_HIP_TRY(hipMemsetAsync(mi->head.p, 0xFF, sizeof(int) * (size_t)L, st));
     ACAV_HIP_TRY(hipMemsetAsync(mi->g.p, 0xFF, sizeof(int) * (size_t)L, st));
-    ACAV_TRY(mi->mt.ensure(sizeof(unsigned) * 625));
     ACAV_TRY(mi->batch.ensure(sizeof(int) * (size_t)(B > SEL_MAXB ? B : SEL_MAXB)));
-    ACAV_TRY(mi->S.ensure(sizeof(long long) * (size_t)cap));
-    ACAV_TRY(mi->G.ensure(sizeof(double) * (size_t)cap));
-    if (trace_pos) ACAV_TRY(mi->tr_pos.ensure(sizeof(int) * (size_t)(iters * k + 1)));
-    if (trace_ids) ACAV_TRY(mi->tr_ids.ensure(sizeof(long long) * (size_t)(iters * B + 1)));
-    if (trace_scores) ACAV_TRY(mi->tr_sc.ensure(sizeof(double) * (size_t)(iters * B + 1)));
-    if (forced_pos) {
+    ACAV_TRY(mi->S.ensure(sizeof(long long) * (size_t)(iters * k + 1)));
+    ACAV_TRY(mi->G.ensure(sizeof(double) * (size_t)(iters * k + 1)));
+    if (ex.trace_pos) ACAV_TRY(mi->tr_pos.ensure(sizeof(int) * (size_t)(iters * k + 1)));
+    if (ex.trace_ids) ACAV_TRY(mi->tr_ids.ensure(sizeof(long long) * (size_t)(iters * B + 1)));
+    if (ex.trace_scores) ACAV_TRY(mi->tr_sc.ensure(sizeof(double) * (size_t)(iters * B + 1)));
+    if (ex.forced_pos) {
         for (int64_t i = 0; i < iters * k; ++i)
-            ACAV_REQUIRE(forced_pos[i] >= 0 && forced_pos[i] < B, ACAV_EINVAL, "forced position out of range");
+            ACAV_REQUIRE(ex.forced_pos[i] >= 0 && ex.forced_pos[i] < B, ACAV_EINVAL, "forced position out of range");
         ACAV_TRY(mi->forced.ensure(sizeof(int) * (size_t)(iters * k + 1)));
-        ACAV_HIP_TRY(hipMemcpyAsync(mi->forced.p, forced_pos, sizeof(int) * (size_t)(iters * k), hipMemcpyHostToDevice, st));
+        ACAV_HIP_TRY(hipMemcpyAsync(mi->forced.p, ex.forced_pos, sizeof(int) * (size_t)(iters * k), hipMemcpyHostToDevice, st));
     }
     // hand the host MT19937 stream to the device: W lanes generate it superblock by superblock on their own stream
     // (MtStream); nothing they do depends on what gets selected (L shrinks by a fixed amount per iteration)
     unsigned mtbuf[625];
     int idx = 0;
     ACAV_TRY(acav_rng_get_state(rng, mtbuf, &idx));
-    const int64_t dl = B - (keep_unselected ? B - k : 0);  // candidates consumed per iteration
-    int64_t total_draws = 0;
-    for (int64_t t = 0; t < iters; ++t) {
-        const int64_t lt = L - t * dl;
-        total_draws += lt > 1 ? lt - 1 : 0;
-    }
     MtStream ms;
     ACAV_TRY(mi_ensure_streams(mi));  // the generator runs on the handle's own generator stream, as in the tiled loop (not the null stream)
-    ACAV_TRY(ms.plan(mi, st, mtbuf, idx, total_draws, L, L));
+    ACAV_TRY(ms.plan(mi, st, mtbuf, idx, gp.draws, L, L));
 
     int *Acur = mi->A0.as<int>(), *Anew = mi->A1.as<int>();
-    int64_t l = L;
     int64_t r0 = 0;  // first draw of this iteration, counted from the first draw of the run
     for (int64_t it = 0; it < iters; ++it) {
-        const int Li = (int)l;
+        const int Li = (int)(L - it * dl);
         const int64_t nd = Li > 1 ? Li - 1 : 0;
         const unsigned grid = (unsigned)((Li + 255) / 256);
         const unsigned *draws = nullptr;
@@ -3721,29 +3537,19 @@ ACAV_EXPORT int acav_mi_run_greedy(acav_mi *mi, const int64_t *candidates, int64
                            mi->next.as<int>(), gg, mi->batch.as<int>(), Anew, hd_n, gg_n);
         ACAV_HIP_TRY(hipGetLastError());
         ACAV_TRY(launch_select(mi, mi->batch.as<int>(), B, k, nullptr, mi->S.as<long long>() + it * k,
-                               mi->G.as<double>() + it * k, forced_pos ? mi->forced.as<int>() + it * k : nullptr,
-                               trace_pos ? mi->tr_pos.as<int>() + it * k : nullptr,
-                               trace_ids ? mi->tr_ids.as<long long>() + it * B : nullptr,
-                               trace_scores ? mi->tr_sc.as<double>() + it * B : nullptr, keep_unselected,
+                               mi->G.as<double>() + it * k, ex.forced_pos ? mi->forced.as<int>() + it * k : nullptr,
+                               ex.trace_pos ? mi->tr_pos.as<int>() + it * k : nullptr,
+                               ex.trace_ids ? mi->tr_ids.as<long long>() + it * B : nullptr,
+                               ex.trace_scores ? mi->tr_sc.as<double>() + it * B : nullptr, keep_unselected,
                                Anew + (Li - B)));
-        l = l - B + (keep_unselected ? B - k : 0);
         int *t = Acur;
         Acur = Anew;
         Anew = t;
     }
-    const int64_t nsel = iters * k < subset ? iters * k : subset;
-    if (iters > 0) {
-        ACAV_HIP_TRY(hipMemcpyAsync(S_out, mi->S.p, sizeof(long long) * (size_t)nsel, hipMemcpyDeviceToHost, st));
-        ACAV_HIP_TRY(hipMemcpyAsync(GAIN_out, mi->G.p, sizeof(double) * (size_t)(iters * k), hipMemcpyDeviceToHost, st));
-        if (trace_pos) ACAV_HIP_TRY(hipMemcpyAsync(trace_pos, mi->tr_pos.p, sizeof(int) * (size_t)(iters * k), hipMemcpyDeviceToHost, st));
-        if (trace_ids) ACAV_HIP_TRY(hipMemcpyAsync(trace_ids, mi->tr_ids.p, sizeof(long long) * (size_t)(iters * B), hipMemcpyDeviceToHost, st));
-        if (trace_scores) ACAV_HIP_TRY(hipMemcpyAsync(trace_scores, mi->tr_sc.p, sizeof(double) * (size_t)(iters * B), hipMemcpyDeviceToHost, st));
-    }
+    ACAV_TRY(read_back(mi, st, iters, subset, B, k, S_out, GAIN_out, ex, n_selected, n_iters));
     ACAV_HIP_TRY(hipStreamSynchronize(mi->st_mt));
     ACAV_HIP_TRY(hipStreamSynchronize(st));
     ACAV_TRY(ms.final_state(mtbuf, &idx));
     ACAV_TRY(acav_rng_set_state(rng, mtbuf, idx));  // the stream continues on the host
-    if (n_selected) *n_selected = nsel;
-    if (n_iters) *n_iters = iters;
     return ACAV_OK;
 }

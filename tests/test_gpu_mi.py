@@ -366,50 +366,98 @@ def test_exact_greedy_through_run_greedy(env):
     assert sorted(S_all) == list(range(400))
 
 
+def _lockstep_specs(keep):
+    # (V, D, C, subset): unequal list lengths and iteration counts (one chunk runs a single iteration), different D / P / C
+    # tables.  keep_unselected=False consumes a whole batch per iteration: chunk 3's 799 candidates last 39 iterations
+    return [(3000, 2, 16, 300), (1200, 3, 40, 100), (5000, 2, 256, 37), (800, 4, 8, 160 if keep else 120), (2500, 2, 64, 1)]
+
+
+def _lockstep_data(keep):
+    data = []
+    for i, (v, dd, c, subset) in enumerate(_lockstep_specs(keep)):
+        a = _correlated(900 + i, v, dd, c)
+        cand = np.random.RandomState(i).permutation(v)
+        data.append((a, c, list(itertools.combinations(range(dd), 2)), cand, subset))
+    return data
+
+
+def _lockstep_build(data, i, seed, keep=True):
+    from acav100m_amd.rng import Generator
+    from acav100m_amd.subset_selection import get_measure
+    a, c, pairs, cand, subset = data[i]
+    m = get_measure("batch_mi")(a, ncentroids=c, batch_size=20, selection_size=4, device="cuda:0",
+                                keep_unselected=keep, generator=Generator(seed))
+    m.init(pairs, [int(j) for j in cand[1:]])
+    return m
+
+
+def _check_lockstep_chunks(env, keep):
+    torch, acav, O = env
+    from acav100m_amd.subset_selection.measures.batch import EfficientBatchMI
+    data = _lockstep_data(keep)
+    n = len(data)
+    alone, tails = [], []
+    for i in range(n):
+        m = _lockstep_build(data, i, 50 + i, keep)
+        alone.append(m.run_greedy(data[i][4], [int(data[i][3][0])], None))
+        tails.append(m._generator.u32())
+    ms = [_lockstep_build(data, i, 50 + i, keep) for i in range(n)]
+    multi = EfficientBatchMI.run_greedy_multi(ms, [d[4] for d in data], [[int(d[3][0])] for d in data])
+    for i in range(n):
+        assert multi[i][0] == alone[i][0] and multi[i][1] == alone[i][1], f"chunk {i}"
+        assert ms[i]._generator.u32() == tails[i]
+        a, c, pairs, cand, subset = data[i]
+        r = O.BatchMI(a, c, pairs).run_greedy(cand[1:], cand[:1], subset, 20, 4, O.Rng(50 + i), keep_unselected=keep)
+        assert multi[i][0] == r["S"].tolist()
+        assert ms[i].cache["n"] == 1 + len(multi[i][1])
+
+
 def test_lockstep_chunks_equal_individual_runs(env):
     """acav_mi_run_greedy_multi: several chunks (different sizes, different D / P / C tables, own generators) driven
     by one set of launches per iteration give exactly what each chunk gives alone -- and hence the oracle's result;
     every generator ends where its own run would have left it."""
+    from acav100m_amd.rng import Generator
+    from acav100m_amd.subset_selection.measures.batch import EfficientBatchMI
+    _check_lockstep_chunks(env, True)
+    data = _lockstep_data(True)
+    with pytest.raises(AssertionError):
+        g = Generator(1)
+        m1, m2 = _lockstep_build(data, 0, 1), _lockstep_build(data, 1, 2)
+        m1._generator = m2._generator = g
+        EfficientBatchMI.run_greedy_multi([m1, m2], [10, 10], [[0], [0]])
+
+
+@pytest.mark.parametrize("keep", [True, False])
+def test_legacy_chunks_equal_individual_runs(env, monkeypatch, keep):
+    """The same under ACAV_FY_LEGACY=1 (also the path of a call with a list beyond the tile table), where the chunks of
+    acav_mi_run_greedy_multi run one after another on the global-atomic Fisher-Yates kernels: every chunk equals its run
+    alone and the oracle, tables and generator included -- with keep_unselected and without."""
+    monkeypatch.setenv("ACAV_FY_LEGACY", "1")
+    _check_lockstep_chunks(env, keep)
+
+
+def test_legacy_chunks_are_planned_before_any_chunk_runs(env, monkeypatch):
+    """ACAV_FY_LEGACY=1, two chunks, the LAST one's candidates run out below batch_size (as in test_mi_errors): the call
+    raises and chunk 0 is as it was before the call -- nothing added to its tables, not a draw taken from its generator."""
     torch, acav, O = env
     from acav100m_amd.rng import Generator
     from acav100m_amd.subset_selection import get_measure
     from acav100m_amd.subset_selection.measures.batch import EfficientBatchMI
-    specs = [(3000, 2, 16, 300), (1200, 3, 40, 100), (5000, 2, 256, 37), (800, 4, 8, 160), (2500, 2, 64, 1)]
-    data = []
-    for i, (v, dd, c, subset) in enumerate(specs):
-        a = _correlated(900 + i, v, dd, c)
-        cand = np.random.RandomState(i).permutation(v)
-        data.append((a, c, list(itertools.combinations(range(dd), 2)), cand, subset))
-
-    def build(i, seed):
-        a, c, pairs, cand, subset = data[i]
-        m = get_measure("batch_mi")(a, ncentroids=c, batch_size=20, selection_size=4, device="cuda:0",
-                                    keep_unselected=True, generator=Generator(seed))
-        m.init(pairs, [int(j) for j in cand[1:]])
-        return m
-
-    for keep in (True,):
-        alone, tails = [], []
-        for i in range(len(specs)):
-            m = build(i, 50 + i)
-            alone.append(m.run_greedy(data[i][4], [int(data[i][3][0])], None))
-            tails.append(m._generator.u32())
-        ms = [build(i, 50 + i) for i in range(len(specs))]
-        multi = EfficientBatchMI.run_greedy_multi(ms, [d[4] for d in data], [[int(d[3][0])] for d in data])
-        for i in range(len(specs)):
-            assert multi[i][0] == alone[i][0] and multi[i][1] == alone[i][1], f"chunk {i}"
-            assert ms[i]._generator.u32() == tails[i]
-            a, c, pairs, cand, subset = data[i]
-            r = O.BatchMI(a, c, pairs).run_greedy(cand[1:], cand[:1], subset, 20, 4, O.Rng(50 + i))
-            assert multi[i][0] == r["S"].tolist()
-            cache = ms[i].cache
-            Nc, ac, bc, nc = O.BatchMI(a, c, pairs).counts()
-            assert cache["n"] == 1 + len(multi[i][1])
-    with pytest.raises(AssertionError):
-        g = Generator(1)
-        m1, m2 = build(0, 1), build(1, 2)
-        m1._generator = m2._generator = g
-        EfficientBatchMI.run_greedy_multi([m1, m2], [10, 10], [[0], [0]])
+    monkeypatch.setenv("ACAV_FY_LEGACY", "1")
+    ms = []
+    for i, v in enumerate((400, 300)):
+        a = _correlated(40 + i, v, 2, 8)
+        m = get_measure("batch_mi")(a, ncentroids=8, batch_size=20, selection_size=4, device="cuda:0",
+                                    keep_unselected=True, generator=Generator(60 + i))
+        m.init([(0, 1)], list(range(2, v)))
+        ms.append(m)
+    ms[0].add_samples([1])
+    assert ms[0].cache["n"] == 1
+    # chunk 1: 298 candidates, 4 leave per iteration: iteration 70 finds 18 < 20 of them, 72 iterations are asked for
+    with pytest.raises(RuntimeError):
+        EfficientBatchMI.run_greedy_multi(ms, [40, 288], [[0], [0]])
+    assert ms[0].cache["n"] == 1
+    assert ms[0]._generator.u32() == Generator(60).u32()
 
 
 def test_recycled_device_blocks_change_nothing_and_can_be_trimmed(env):

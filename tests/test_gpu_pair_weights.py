@@ -224,6 +224,13 @@ def test_lockstep_weighted_chunks_equal_individual_runs(env):
         assert multi[i][0] == S and np.array_equal(np.array(multi[i][1]), np.array(G)), i
 
 
+def test_legacy_weighted_chunks_equal_individual_runs(env, monkeypatch):
+    """The same with ACAV_FY_LEGACY=1, where the chunks of one call run one after another: weighted and unweighted
+    handles mixed in one call."""
+    monkeypatch.setenv("ACAV_FY_LEGACY", "1")
+    test_lockstep_weighted_chunks_equal_individual_runs(env)
+
+
 # ----------------------------------------------------------------------------- 5. onehot_4 == penultimate
 def test_onehot_penultimate_selects_what_a_penultimate_run_selects(env):
     from acav100m_amd.subset_selection.pairing import get_cluster_pairing
