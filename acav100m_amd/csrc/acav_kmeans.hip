@@ -16,9 +16,12 @@
 //   sumsq = 32 interleaved FMA chains (class = j mod 32) + fixed butterfly tree;
 //   every other op is a single correctly-rounded fp32 op, compiled with -ffp-contract=off.
 #include <chrono>
+#include <cstddef>
+#include <memory>
 #include <thread>
 
 #include "acav_kmeans_shared.h"
+#include "acav_kmeans_form.h"
 
 namespace {
 
@@ -520,10 +523,7 @@ __global__ __launch_bounds__(256) void k_step_update(const float *__restrict__ x
 // grid against hipOccupancyMaxActiveBlocksPerMultiprocessor x CUs, every spin is bounded, and on `err` the host
 // re-runs the call on the per-step launch path from the saved state.
 // PROF (ACAV_PROFILE_STEPS=1): per-phase shader-clock timers; compiled out of the default kernel.
-constexpr int TP_NC = 8;
-constexpr int TP_NR = 8;
-constexpr int TP_DS = 1024;
-constexpr int TP_MAXB = 32;
+// (TP_NC = 8 centres x TP_NR = 8 rows per workgroup, rows of up to TP_DS = 1024 columns, TP_MAXB = 32 batch rows: acav_kmeans_form.h)
 constexpr unsigned TP_SPIN_LIMIT = 1u << 24;
 #ifndef ACAV_TP_FIRST_SLEEP
 #define ACAV_TP_FIRST_SLEEP 32
@@ -535,14 +535,8 @@ constexpr int TP_FIRST_SWEEP_PAUSE = ACAV_TP_FIRST_SLEEP;  // x 64 clocks betwee
 // in these kernels the compiler's own windows do better than the pinned ones, in k_train_persistent the pinned order wins (3.38k -> 2.98k)
 #define ACAV_WIDE_PIN 0
 #endif
-#ifndef ACAV_SWEEP_REREAD_ALL
-#define ACAV_SWEEP_REREAD_ALL 1
-#endif
 #ifndef ACAV_TPW_FIRST_SLEEP
 #define ACAV_TPW_FIRST_SLEEP 0
-#endif
-#ifndef ACAV_TPW_PASS_SLEEP
-#define ACAV_TPW_PASS_SLEEP 0
 #endif
 
 #if defined(ACAV_WIDE_NO_MFMA) && !defined(ACAV_EXPERIMENT_BUILD)
@@ -570,15 +564,16 @@ struct TrainCtl {
     unsigned err;          // 1 = a bounded spin gave up
     unsigned pad[3];
     unsigned long long prof[8];  // shader-clock cycles per phase, summed over the steps of workgroup (1,0)
-    unsigned long long prof_wg[256][8];  // the same per workgroup (ACAV_PROFILE_STEPS diagnostics)
+    union {
+        unsigned long long prof_wg[256][8];  // the same per workgroup (ACAV_PROFILE_STEPS diagnostics of k_train_persistent)
+        unsigned long long wide_up[8];       // -DACAV_WIDE_PROF writes prof_wg[0]: the update's four phases, then wave 0's inside the exchange
+        unsigned long long split_half0[8];   // the split kernel's timers of column half 0 (half 1 reports into prof)
+    };
     // granules[ring][centre group][batch row]: {tag:16 | local centre:16 | orderable distance:32}, each
     // written by exactly one workgroup per synced step with ONE 8-byte device-scope store
     unsigned long long gran[TP_RING][TP_MAXCG * 2 * TP_LSTRIDE];
 };
 
-#ifndef ACAV_SWEEP_LEAN
-#define ACAV_SWEEP_LEAN 1
-#endif
 #ifndef ACAV_LEAN_PASS_SLEEP
 #define ACAV_LEAN_PASS_SLEEP 0
 #endif
@@ -958,8 +953,6 @@ __global__ __launch_bounds__(256) void k_train_persistent(
                     if (kk < nck && ii < nrv) key = pack_key(tq, k);
                 }
                 key = tp_min_xor32(tp_min_xor16(tp_min_xor8(key)));  // (the minimum over the 8 centres kk of row ii: lanes ^ 8, ^ 16, ^ 32)
-                unsigned long long o;
-                (void)o;
                 // publish: one tagged granule per (my centre group, my row), a single 8-byte device-scope store
                 const unsigned long long tag = (unsigned long long)((nsync % 65535u) + 1u) << 48;
                 unsigned long long *ring = ctl->gran[nsync % TP_RING];
@@ -968,8 +961,10 @@ __global__ __launch_bounds__(256) void k_train_persistent(
                     __hip_atomic_store(&ring[tp_gran_index(blockIdx.x, rbase + lane)], tag | (local << 32) | (key >> 32), __ATOMIC_RELAXED,
                                        __HIP_MEMORY_SCOPE_AGENT);
                 }
-#if ACAV_SWEEP_LEAN
-                {  // gather: tp_sweep_lean (above); the pause before the first pass as tuned in round 2 (comment in the #else branch)
+                {  // gather: tp_sweep_lean (above).  The first sweep leaves ~0.9 us after the publish: sent at once it nearly always comes back
+                    // incomplete (the other workgroups' stores are still on their way) and every pass costs a full round trip of ~1.7 us -- 2.5 passes
+                    // per step without the pause, 1.7 with it (round 2, K = 256 / d = 1024; the tuning table: docs/measured_and_rejected.md).  With few
+                    // centre groups the first pass is more often complete and the pause costs more than it saves (K = 64: 7.34 -> 7.43 us per step)
                     if (ncg >= 16) __builtin_amdgcn_s_sleep(TP_FIRST_SWEEP_PAUSE);
                     const unsigned tag16 = (nsync % 65535u) + 1u;
                     const int nu = (ncg + 1) >> 1;
@@ -982,63 +977,6 @@ __global__ __launch_bounds__(256) void k_train_persistent(
                     if (lane < b) sBest[lane] = bl;
                     if (!ok && lane == 0) sDead = 1;
                 }
-#else
-                // gather: lane (row = l & 31, half = l >> 5) sweeps the granules of its row from half of the
-                // centre groups until every tag is this step's; then the lexicographic minimum
-                const int srow = lane & 31, half = lane >> 5;
-                unsigned long long bestkey = ~0ull;
-                unsigned ok = 1;
-                constexpr int TP_SW = 16;  // granules per lane: centre groups half, half+2, ... (ncg <= 32 per sweep set)
-                unsigned long long g[TP_SW];
-                unsigned need = 0;  // bit u: granule u of this lane not yet seen with this step's tag
-#pragma unroll
-                for (int u = 0; u < TP_SW; ++u)
-                    if (srow < b && half + 2 * u < ncg) need |= 1u << u;
-                // the first sweep leaves ~0.9 us after the publish: sent at once it nearly always comes back incomplete (the
-                // other workgroups' stores are still on their way) and every pass costs a full round trip of ~1.7 us --
-                // 2.5 passes per step without the pause, 1.7 with it (7.20 -> 7.00 us per step at K = 256, d = 1024; 24 / 28 /
-                // 32 / 36 / 40 / 48 x 64 clocks: 7.08 / 7.01 / 7.00 / 7.02 / 7.08 / 7.24).  With few centre groups the first
-                // pass is more often complete and the pause costs more than it saves (K = 64: 7.34 -> 7.43)
-                if (ncg >= 16) __builtin_amdgcn_s_sleep(TP_FIRST_SWEEP_PAUSE);
-                for (unsigned spins = 0;; ++spins) {
-                    // round 6: EVERY pass re-reads every granule of the existing centre groups (a wave-uniform condition).  Re-reading
-                    // only the lanes' missing granules -- rounds 1-5 -- put an exec-mask save / branch / restore around each of the
-                    // loads and sent nearly as many (sparse) memory instructions: tools/exp/exchange_bench.hip, 128 workgroups,
-                    // 3 500 cycles of work per round: 4.85-5.05 us per round against 3.75-3.85 with full re-reads; in this kernel
-                    // K = 256 / d = 1024 5.98 -> 5.87 us per step, K = 64 / d = 512 6.58 -> 6.34
-#pragma unroll
-                    for (int u = 0; u < TP_SW; ++u)
-                        if (ACAV_SWEEP_REREAD_ALL ? 2 * u < ncg : (int)((need >> u) & 1u))
-                            g[u] = __hip_atomic_load(&ring[tp_gran_index(half + 2 * u, srow)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-                    for (int u = 0; u < TP_SW; ++u)
-                        if (((need >> u) & 1u) && (g[u] >> 48) == (tag >> 48)) need &= ~(1u << u);
-                    if (PROF) pr[7] += 1;  // sweep passes (diagnostics)
-                    if (__all(need == 0)) break;
-                    if (spins > TP_SPIN_LIMIT || (spins & 1023) == 1023) {
-                        if (spins > TP_SPIN_LIMIT || __hip_atomic_load(&ctl->err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                            if (lane == 0) __hip_atomic_store(&ctl->err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            ok = 0;
-                            break;
-                        }
-                    }
-                }
-                bestkey = ~0ull;
-#pragma unroll
-                for (int u = 0; u < TP_SW; ++u) {
-                    const int cg = half + 2 * u;
-                    if (srow < b && cg < ncg && ok) {
-                        const unsigned loc = (unsigned)(g[u] >> 32) & 0xFFFFu;
-                        const unsigned long long cand =
-                            loc == 0xFFFFu ? ~0ull : (((g[u] & 0xffffffffull) << 32) | (unsigned)(cg * TP_NC + loc));
-                        bestkey = cand < bestkey ? cand : bestkey;
-                    }
-                }
-                o = __shfl_xor(bestkey, 32);
-                bestkey = o < bestkey ? o : bestkey;
-                if (lane < b) sBest[lane] = (int)(bestkey & 0xffffffffull);
-                if (!ok && lane == 0) sDead = 1;
-#endif
             }
             ++nsync;
             __syncthreads();
@@ -1157,7 +1095,7 @@ __global__ __launch_bounds__(256) void k_train_persistent(
 // the passes, and the sweep reads up to 64 centre groups (32 granules per lane).  The update walks the passes; a step
 // touches ~b / (K / (8 NCP)) centres of a workgroup, almost always none or one.  Same exchange, same arithmetic, same
 // bit-exact result as k_train_persistent -- which stays the kernel of every shape it can hold (K d <= 256 x 1024).
-constexpr int TPW_SW = 32;  // granules per lane in the sweep: up to 64 centre groups
+// (TPW_SW = 32 granules per lane in the sweep, up to 64 centre groups: acav_kmeans_form.h)
 
 template <bool RAGGED>
 __device__ __forceinline__ void tpw_dma_block(float *lds, const float *__restrict__ src, int first_row, int nrows_valid, int d,
@@ -1415,7 +1353,6 @@ __global__ __launch_bounds__(256) void k_train_persistent_wide(
             if (ONE_X && t + 1 < T) dma_rows(t + 1);  // the one row buffer is free: the next step's rows land under the exchange
             if (wave == 0) {
                 unsigned long long keys[NRP];
-                unsigned long long o;
                 unsigned long long key;
                 if constexpr (MF) {  // lane l: centres 4 (l >> 4) + e of batch row l & 15
                     const int i15 = lane & 15, kq = lane >> 4;
@@ -1451,7 +1388,6 @@ __global__ __launch_bounds__(256) void k_train_persistent_wide(
                         key = kc < key ? kc : key;
                     }
                     key = tp_min_xor32(tp_min_xor16(key));  // lane l < 16 holds the key of row l
-                    (void)o;
                     (void)keys;
                 } else {
 #pragma unroll
@@ -1469,7 +1405,6 @@ __global__ __launch_bounds__(256) void k_train_persistent_wide(
                         }
                     }
                     key = tp_min_xor32(tp_min_xor16(tp_min_xor8(key)));
-                    (void)o;
                     keys[rp] = key;
                 }
                 // lane l < 8 NRP holds the key of row l: its ii is l & 7 and every lane of an ii column holds that row's minimum
@@ -1486,8 +1421,7 @@ __global__ __launch_bounds__(256) void k_train_persistent_wide(
                     __hip_atomic_store(&ring[tp_gran_index(blockIdx.x, rbase + lane)], tag | (local << 32) | (key >> 32), __ATOMIC_RELAXED,
                                        __HIP_MEMORY_SCOPE_AGENT);
                 }
-#if ACAV_SWEEP_LEAN
-                {  // (the per-lane form of rounds 1-5 below: -DACAV_SWEEP_LEAN=0)
+                {  // gather: tp_sweep_lean (the per-lane form of rounds 1-5 and what it measured: docs/measured_and_rejected.md)
 #if ACAV_TPW_FIRST_SLEEP > 0
                     __builtin_amdgcn_s_sleep(ACAV_TPW_FIRST_SLEEP);
 #endif
@@ -1505,77 +1439,6 @@ __global__ __launch_bounds__(256) void k_train_persistent_wide(
                     if (lane < b) sBest[lane] = bl;
                     if (!okl && lane == 0) sDead = 1;
                 }
-#else
-                {
-                const int srow = lane & 31, half = lane >> 5;
-                unsigned long long bestkey = ~0ull;
-                unsigned ok = 1;
-                unsigned long long g[TPW_SW];
-                unsigned needm = 0;  // bit u: granule u of this lane not yet seen with this step's tag
-                const bool reread_all = gridDim.x * gridDim.y <= 128u;
-#pragma unroll
-                for (int u = 0; u < TPW_SW; ++u)
-                    if (srow < b && half + 2 * u < ncg) needm |= 1u << u;
-#if ACAV_TPW_FIRST_SLEEP > 0
-                __builtin_amdgcn_s_sleep(ACAV_TPW_FIRST_SLEEP);  // experiment knob: x 64 clocks between the publish and the first sweep
-#endif
-                for (unsigned spins = 0;; ++spins) {
-#if ACAV_TPW_PASS_SLEEP > 0
-                    if (spins) __builtin_amdgcn_s_sleep(ACAV_TPW_PASS_SLEEP);  // experiment knob: pause before a repeated pass
-#endif
-#ifdef ACAV_WIDE_PROF
-                    wpr[7] += 1;  // sweep passes
-                    const long long wpass0 = TPW_CLK();
-#endif
-                    // up to 128 workgroups (the 16 x 16 form at K = 1024): every pass re-reads everything under a wave-uniform
-                    // condition (k_train_persistent); more pollers than that (16 x 8 forms: 256) and the volume of full re-reads costs
-                    // more than the per-lane conditions -- d = 128 / K = 1024 on 256 workgroups 9.05 vs 8.38 us per step
-                    if (ACAV_SWEEP_REREAD_ALL && reread_all) {
-#pragma unroll
-                        for (int u = 0; u < TPW_SW; ++u)
-                            if (2 * u < ncg)
-                                g[u] = __hip_atomic_load(&ring[tp_gran_index(half + 2 * u, srow)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    } else {
-#pragma unroll
-                        for (int u = 0; u < TPW_SW; ++u)
-                            if ((needm >> u) & 1u)
-                                g[u] = __hip_atomic_load(&ring[tp_gran_index(half + 2 * u, srow)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-#pragma unroll
-                    for (int u = 0; u < TPW_SW; ++u)
-                        if (((needm >> u) & 1u) && (g[u] >> 48) == (tag >> 48)) needm &= ~(1u << u);
-#ifdef ACAV_WIDE_PROF
-                    if (t >= need && spins == 0) wsw[2] += TPW_CLK() - wpass0;
-#endif
-                    if (__all(needm == 0)) break;
-                    if (spins > TP_SPIN_LIMIT || (spins & 1023) == 1023) {
-                        if (spins > TP_SPIN_LIMIT || __hip_atomic_load(&ctl->err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                            if (lane == 0) __hip_atomic_store(&ctl->err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            ok = 0;
-                            break;
-                        }
-                    }
-                }
-#ifdef ACAV_WIDE_PROF
-                wsw_end = TPW_CLK();
-                if (t >= need) wsw[1] += wsw_end - wsw0;
-#endif
-#pragma unroll
-                for (int u = 0; u < TPW_SW; ++u) {
-                    const int cg = half + 2 * u;
-                    if (srow < b && cg < ncg && ok) {
-                        const unsigned loc = (unsigned)(g[u] >> 32) & 0xFFFFu;
-                        const unsigned long long cand =
-                            loc == 0xFFFFu ? ~0ull : (((g[u] & 0xffffffffull) << 32) | (unsigned)(cg * NCW + loc));
-                        bestkey = cand < bestkey ? cand : bestkey;
-                    }
-                }
-                o = __shfl_xor(bestkey, 32);
-                bestkey = o < bestkey ? o : bestkey;
-                if (lane < b) sBest[lane] = (int)(bestkey & 0xffffffffull);
-                if (!ok && lane == 0) sDead = 1;
-                }
-#endif
             }
             ++nsync;
             __syncthreads();
@@ -1749,10 +1612,7 @@ __global__ __launch_bounds__(256) void k_train_persistent_wide(
 // Hand-off slots are single (no ring): ch = 0 cannot reach its next publish before it has seen the label granules of the
 // step, which its partner only writes after consuming the slot.  Tags are the step number + 1 (the rings are zeroed
 // before every launch).  Bounded spins + error flag + re-run on the per-step path, as k_train_persistent.
-constexpr int TS_NC = 16;      // centres per workgroup
-constexpr int TS_NR = 16;      // batch rows per workgroup
-constexpr int TS_COLS = 1024;  // columns per workgroup (= TP_DS: the LDS row stride of tp_dma_block / dot_blocks)
-constexpr size_t TS_SMEM = sizeof(float) * (size_t)(2 * 16 * TS_COLS + 2 * TS_NC + 4 * 4 * 64 + 32) + 8 * 64 + 64;
+// (TS_NC = 16 centres x TS_NR = 16 rows x TS_COLS = 1024 columns per workgroup, TS_SMEM bytes of LDS: acav_kmeans_form.h)
 
 __device__ __forceinline__ unsigned long long ts_granule(float v, unsigned tag)
 {
@@ -2023,7 +1883,6 @@ __global__ __launch_bounds__(256) void k_train_persistent_split(
                     __hip_atomic_store(&ring[tp_gran_index(cg, rbase + lane)], tag16 | (local << 32) | (key >> 32), __ATOMIC_RELAXED,
                                        __HIP_MEMORY_SCOPE_AGENT);
                 }
-#if ACAV_SWEEP_LEAN
                 {
                     const int nu = (ncg + 1) >> 1;
                     int bl = -1;
@@ -2033,47 +1892,6 @@ __global__ __launch_bounds__(256) void k_train_persistent_split(
                     if (lane < b) sBest[lane] = bl;
                     if (!okl && lane == 0) sDead = 1;
                 }
-#else
-                const int srow = lane & 31, half = lane >> 5;
-                unsigned long long bestkey = ~0ull;
-                unsigned okw = 1;
-                unsigned long long g[TPW_SW];
-                unsigned needm = 0;  // bit u: granule u of this lane not yet seen with this step's tag
-#pragma unroll
-                for (int u = 0; u < TPW_SW; ++u)
-                    if (srow < b && half + 2 * u < ncg) needm |= 1u << u;
-                for (unsigned spins = 0;; ++spins) {
-#pragma unroll
-                    for (int u = 0; u < TPW_SW; ++u)
-                        if ((needm >> u) & 1u)  // (256 workgroups: only the missing granules -- full re-reads measured 10.68 vs 10.50 us per step)
-                            g[u] = __hip_atomic_load(&ring[tp_gran_index(half + 2 * u, srow)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-                    for (int u = 0; u < TPW_SW; ++u)
-                        if (((needm >> u) & 1u) && (g[u] >> 48) == (tag16 >> 48)) needm &= ~(1u << u);
-                    if (__all(needm == 0)) break;
-                    if (spins > TP_SPIN_LIMIT || (spins & 1023) == 1023) {
-                        if (spins > TP_SPIN_LIMIT || __hip_atomic_load(&ctl->err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                            if (lane == 0) __hip_atomic_store(&ctl->err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            okw = 0;
-                            break;
-                        }
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < TPW_SW; ++u) {
-                    const int cgu = half + 2 * u;
-                    if (srow < b && cgu < ncg && okw) {
-                        const unsigned loc = (unsigned)(g[u] >> 32) & 0xFFFFu;
-                        const unsigned long long cand =
-                            loc == 0xFFFFu ? ~0ull : (((g[u] & 0xffffffffull) << 32) | (unsigned)(cgu * TS_NC + loc));
-                        bestkey = cand < bestkey ? cand : bestkey;
-                    }
-                }
-                const unsigned long long o = __shfl_xor(bestkey, 32);
-                bestkey = o < bestkey ? o : bestkey;
-                if (lane < b) sBest[lane] = (int)(bestkey & 0xffffffffull);
-                if (!okw && lane == 0) sDead = 1;
-#endif
             }
             ++nsync;
             __syncthreads();
@@ -2457,12 +2275,74 @@ struct TrainCall {
     const float *fx = nullptr;
     const int64_t *dw = nullptr;
     const void *x_user = nullptr, *w_user = nullptr;
-    int nwg = 0;
-    bool launched = false, prof = false, split_prof = false, active = false;
-    bool is_split = false;  // the column-split kernel: one 130 KB workgroup on every CU, 256 registers per lane
-    bool shared = false;    // launched BESIDE such a kernel, in the LDS it leaves (books no CUs of the budget)
+    TrainForm form;  // the kernel of the launch, its grid and LDS (acav_kmeans_form.h)
+    bool launched = false, prof = false, active = false;
     std::vector<float> thr;  // staging of the per-step thresholds: alive until the launch has been waited for
 };
+
+// the experiment switches of the form choice, read from the environment in this one place
+static TrainSwitches train_switches()
+{
+    auto starts = [](const char *name, char c) {
+        const char *v = getenv(name);
+        return v && v[0] == c;
+    };
+    TrainSwitches sw;
+    sw.no_persistent = starts("ACAV_NO_PERSISTENT", '1');
+    sw.force_wide = starts("ACAV_FORCE_WIDE", '1');
+    sw.tall = !starts("ACAV_TALL", '0');
+    if (const char *v = getenv("ACAV_WIDE_NCP")) sw.wide_ncp = atoi(v) > 0 ? atoi(v) : 0;
+    sw.wide_nrp = starts("ACAV_WIDE_NRP", '2') ? 2 : starts("ACAV_WIDE_NRP", '1') ? 1 : 0;
+    if (const char *v = getenv("ACAV_SPLIT_MINK")) sw.split_mink = atoi(v);
+    return sw;
+}
+
+ACAV_EXPORT int acav_kmeans_train_form(int d, int k, int64_t b, int aligned, int cus, int occ_narrow, int occ_split, int has_budget,
+                                       int room, int share_lds, int *out)
+{
+    ACAV_REQUIRE(out, ACAV_EINVAL, "NULL argument");
+    ACAV_REQUIRE(d > 0 && k > 0 && b > 0 && cus >= 0 && occ_narrow >= 0 && occ_split >= 0, ACAV_EINVAL, "bad sizes");
+    const TrainForm f = train_pick_form({d, k, b, aligned != 0}, {cus, occ_narrow, occ_split, has_budget != 0, room, share_lds}, train_switches());
+    const int v[8] = {f.kind, f.ncp, f.nrp, f.one_x, f.gx, f.gy, f.gz, f.smem};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return ACAV_OK;
+}
+
+using NarrowKernel = decltype(&k_train_persistent<false, false>);
+using WideKernel = decltype(&k_train_persistent_wide<false, 2>);
+using SplitKernel = decltype(&k_train_persistent_split<false>);
+static NarrowKernel train_narrow_kernel(bool ragged, bool prof)
+{
+    return ragged ? (prof ? k_train_persistent<true, true> : k_train_persistent<true, false>)
+                  : (prof ? k_train_persistent<false, true> : k_train_persistent<false, false>);
+}
+static SplitKernel train_split_kernel(bool prof) { return prof ? k_train_persistent_split<true> : k_train_persistent_split<false>; }
+// the fourteen instantiations of the wide kernel: NCP 1 (tall rows only), 2, 4, 8; one row buffer at NCP <= 2; two row passes at 16 x 16
+template <bool RAGGED>
+static WideKernel train_wide_kernel(const TrainForm &f)
+{
+    if (f.nrp == 2) return k_train_persistent_wide<RAGGED, 2, true, 2>;
+    switch (f.ncp) {
+        case 1: return f.one_x ? k_train_persistent_wide<RAGGED, 1, true> : k_train_persistent_wide<RAGGED, 1, false>;
+        case 2: return f.one_x ? k_train_persistent_wide<RAGGED, 2, true> : k_train_persistent_wide<RAGGED, 2, false>;
+        case 4: return k_train_persistent_wide<RAGGED, 4>;
+        default: return k_train_persistent_wide<RAGGED, 8>;
+    }
+}
+
+// centres, norms, counts and scalars as they are before a persistent launch: saved, and restored if the launch gave up
+static int train_state_copy(acav_kmeans *km, bool restore)
+{
+    const size_t cbytes = sizeof(float) * (size_t)km->K * km->d, kbytes = sizeof(float) * (size_t)km->K;
+    if (!restore) ACAV_TRY(km->backup.ensure(cbytes + 2 * kbytes + sizeof(StepScalars)));
+    char *bk = km->backup.as<char>();
+    const struct { void *p; size_t bytes; } parts[4] = {{km->centers.p, cbytes}, {km->cn.p, kbytes}, {km->counts.p, kbytes}, {km->scalars.p, sizeof(StepScalars)}};
+    for (const auto &q : parts) {
+        ACAV_HIP_TRY(hipMemcpyAsync(restore ? q.p : bk, restore ? bk : q.p, q.bytes, hipMemcpyDeviceToDevice, km->ctx.stream));
+        bk += q.bytes;
+    }
+    return ACAV_OK;
+}
 
 static int train_launch(acav_kmeans *km, TrainCall &tc, const float *x, int64_t n, int64_t b, double lr,
                         const int64_t *warm_best, int64_t n_warm, int *budget, int share_lds = 0)
@@ -2506,130 +2386,31 @@ static int train_launch(acav_kmeans *km, TrainCall &tc, const float *x, int64_t 
                            km->xn.as<float>());
         ACAV_HIP_TRY(hipGetLastError());
     }
-    // persistent path: the whole call in one launch, centres resident in LDS (k_train_persistent)
-    const int nwg = ((km->K + TP_NC - 1) / TP_NC) * (int)((b + TP_NR - 1) / TP_NR);
-    tc.nwg = nwg;
-    const char *nop = getenv("ACAV_NO_PERSISTENT");
+    // persistent path: the whole call in one launch, centres resident in LDS.  Every workgroup of the launch must be resident at
+    // once: the occupancy queries give the workgroups one CU can hold (1: 97 KB of LDS each), times the CUs of the device, minus what
+    // other launches of this call already hold (the budget).  Other streams may still hold CUs: the kernels' spins are bounded and a
+    // launch that gave up is re-run by train_finish() on the per-step path from the saved state.
     const bool prof = getenv("ACAV_PROFILE_STEPS") != nullptr;
-    tc.prof = prof;
-    const bool ragged = (km->d & 255) != 0;
-    auto tkern = ragged ? (prof ? k_train_persistent<true, true> : k_train_persistent<true, false>)
-                        : (prof ? k_train_persistent<false, true> : k_train_persistent<false, false>);
-    // every workgroup of the launch must be resident at once: the occupancy query gives the workgroups one CU can
-    // hold (1: 97 KB of LDS each), times the CUs of the device, minus what other launches of this call already hold.
-    // Other streams may still hold CUs: the kernel's spins are bounded and a launch that gave up is re-run by
-    // train_finish() on the per-step path from the saved state.
     if (km->num_cus == 0) {
         hipDeviceProp_t prop;
         ACAV_HIP_TRY(hipGetDeviceProperties(&prop, km->ctx.device));
         km->num_cus = prop.multiProcessorCount;
     }
-    int occ = 0;
-    ACAV_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void *>(tkern), 256, 0));
-    const int room = budget ? *budget : occ * km->num_cus;
-    const bool shape_ok = steps > 0 && !(nop && nop[0] == '1') && (km->d % 4) == 0 && km->d <= TP_DS && b <= TP_MAXB &&
-                          ((uintptr_t)fx & 15) == 0;
-    // the exchange sweep of k_train_persistent reads 2 x TP_SW = 32 centre groups per row: K <= 256; more groups go to the
-    // wide kernel (64 groups of NCP x 8 centres)
-    // (ACAV_FORCE_WIDE=1: experiments -- the 16-centre forms for shapes the narrow kernel would take)
-    const char *vfw = getenv("ACAV_FORCE_WIDE");
-    const bool narrow_ok = (km->K + TP_NC - 1) / TP_NC <= 32 && !(vfw && vfw[0] == '1');
-    bool persistent = shape_ok && narrow_ok && nwg <= room && nwg <= occ * km->num_cus;
-    // more 8-centre groups than CUs (K = 1024): NCP x 8 centres per workgroup (k_train_persistent_wide) -- the smallest
-    // NCP whose grid fits 3/4 of the device, else the whole device, within the LDS of a CU
-    int ncp = 1, nrp = 1, ds = 0, wide_wg = 0;
-    size_t wide_smem = 0;
-    bool wide = false, one_x = false;
-    // rows wider than 1024 columns (round 4: the real SlowFast widths 1408 / 2304, and d = 2048 below K = 1024): the wide kernel
-    // with ONE centre pass per workgroup (or two), its waves looping over the 256-column blocks, one batch-row buffer when two do
-    // not fit -- no column split, no hand-off between workgroups.  ACAV_TALL=0 switches it off (A/B against the split kernel /
-    // the per-step launches).
-    const char *vtall = getenv("ACAV_TALL");
-    if (!persistent && steps > 0 && !(nop && nop[0] == '1') && !(vtall && vtall[0] == '0') && (km->d % 4) == 0 && km->d > TP_DS &&
-        b <= TP_MAXB && ((uintptr_t)fx & 15) == 0) {
-        ds = ((km->d + 255) / 256) * 256;
-        const int nblk_t = ds / 256, rgroups = (int)((b + TP_NR - 1) / TP_NR);
-        for (int c : {1, 2}) {
-            for (int xrows : {16, 8}) {
-                const int groups = (km->K + 8 * c - 1) / (8 * c);
-                const size_t smem = sizeof(float) * ((size_t)(8 * c + xrows) * ds + 2 * 8 * c + 64 * (c == 2 ? 4 : c) * nblk_t + 32);  // (16 centres: matrix-core tile sums, 4 per lane and block)
-                if (!wide && groups <= 64 && smem <= 160 * 1024 - 1024 && groups * rgroups <= km->num_cus && groups * rgroups <= room) {
-                    ncp = c, wide_wg = groups * rgroups, wide_smem = smem, one_x = xrows == 8;
-                    wide = persistent = true;
-                }
-            }
-        }
-    }
-    if (shape_ok && !persistent && (nwg > occ * km->num_cus || !narrow_ok)) {
-        ds = ((km->d + 255) / 256) * 256;
-        const int rgroups = (int)((b + TP_NR - 1) / TP_NR);
-        int best_ncp = 0;
-        const char *fncp = getenv("ACAV_WIDE_NCP");  // experiments: force the centres per workgroup (2, 4, 8)
-        // a call for one clustering takes the smallest NCP that fits the device (K = 1024, d = 128: 9.8 us per step on 256
-        // workgroups, 11.4 on 128); with several clusterings in one call (budget) the grids stay within 3/4 of it first,
-        // so that two of them run side by side
-        for (int pass = (fncp || !budget) ? 1 : 0; pass < 2 && !best_ncp; ++pass)
-            for (int c : {2, 4, 8}) {
-                if (fncp && atoi(fncp) != c) continue;
-                const int groups = (km->K + 8 * c - 1) / (8 * c);
-                const size_t smem = sizeof(float) * ((size_t)(8 * c + 16) * ds + 2 * 8 * c + 256 * (c == 2 ? 4 : c) + 32);
-                const int lim = pass == 0 ? (3 * km->num_cus) / 4 : km->num_cus;
-                if (groups <= 64 && smem <= 160 * 1024 - 1024 && groups * rgroups <= lim && groups * rgroups <= room) {
-                    best_ncp = c, wide_wg = groups * rgroups, wide_smem = smem;
-                    break;
-                }
-            }
-        // K = 1024 at 768 < d <= 1024 (cfg5): NCP = 2 needs the whole device (64 centre groups x 4 row groups) and more centres
-        // per workgroup do not fit next to two row buffers -- with SEVERAL clusterings in the call the two-row-pass form
-        // (16 centres x 16 rows, one row buffer, 64 x 2 = 128 workgroups) lets two of them run side by side: 14.x us per step of
-        // the PAIR instead of 2 x 13.1.  ACAV_WIDE_NRP=2 forces it for a single clustering, =1 switches it off (A/B).
-        const char *fnrp = getenv("ACAV_WIDE_NRP");
-        const bool nrp_forced = fnrp && fnrp[0] == '2', nrp_off = fnrp && fnrp[0] == '1';
-        if (ds == TS_COLS && !nrp_off && !fncp && (nrp_forced || !best_ncp || wide_wg > (3 * km->num_cus) / 4)) {
-            // (round 6: also for a LONE clustering -- with the tile on the matrix core the 16 x 16 form costs no more FMA time than 16 x 8 and
-            // has half the workgroups in the exchange: K = d = 1024 alone 8.6 vs 9.2 us per step)
-            const int groups = (km->K + 15) / 16, rg2 = (int)((b + 15) / 16);
-            const size_t smem = sizeof(float) * ((size_t)(16 + 16) * ds + 2 * 16 + 4 * 64 * (ds / 256) + 32);
-            if (groups <= 64 && smem <= 160 * 1024 - 1024 && groups * rg2 <= (3 * km->num_cus) / 4 && groups * rg2 <= room) {
-                best_ncp = 2, nrp = 2, one_x = true, wide_wg = groups * rg2, wide_smem = smem;
-            }
-        }
-        // Round 6 (ACAV_TRAIN_SHARE_CU=0 switches it off): no CUs left, but the ONE launch in flight is the column-split kernel (a 130 KB workgroup
-        // on every CU, 252 + 4 registers per lane since the exchange rewrite) -- a 16-centre form with one row buffer fits the LDS it
-        // leaves (26 KB at ds = 256) and the register file beside it (231-243 + 4: profiles/r06_train_regs.txt), one workgroup per CU:
-        // cfg4's 2048-d and 128-d views train side by side instead of one after the other.
-        if (!best_ncp && share_lds > 0 && ds <= 512) {
-            const int groups = (km->K + 15) / 16;
-            const size_t smem = sizeof(float) * ((size_t)(16 + 8) * ds + 2 * 16 + 4 * 64 * (size_t)(ds / 256) + 32);  // (tile sums: 4 x 64 per column block)
-            if (groups <= 64 && (int)smem + 512 <= share_lds && groups * rgroups <= km->num_cus) {
-                best_ncp = 2, nrp = 1, one_x = true, wide_wg = groups * rgroups, wide_smem = smem;
-                tc.shared = true;
-                if (getenv("ACAV_TRAIN_SHARE_DEBUG")) fprintf(stderr, "[acav] shared launch: d = %d, K = %d, %d workgroups of %zu B beside the split kernel (%d B free per CU)\n", km->d, km->K, wide_wg, smem, share_lds);
-            }
-        }
-        if (best_ncp) ncp = best_ncp, persistent = wide = true;
-    }
-    // 1024 < d <= 2048 (cfg4's visual view): the columns are split over pairs of workgroups (k_train_persistent_split)
-    bool split = false;
-    int split_wg = 0;
-    const int s_ncg = (km->K + TS_NC - 1) / TS_NC, s_nrg = (int)((b + TS_NR - 1) / TS_NR);
-    // (worth it from K = 512 on: below that the per-step launches are as fast -- 14.5 us at K = 256 -- because the two
-    // dependent hand-offs of a split step cost more than the launches they replace; ACAV_SPLIT_MINK overrides)
-    const char *smk = getenv("ACAV_SPLIT_MINK");
-    const int split_mink = smk ? atoi(smk) : 512;
-    if (!persistent && steps > 0 && !(nop && nop[0] == '1') && km->d > TP_DS && km->d <= 2 * TP_DS && (km->d & 255) == 0 &&
-        b <= TP_MAXB && ((uintptr_t)fx & 15) == 0 && s_ncg <= 2 * TPW_SW && km->K >= split_mink) {
-        auto sk = prof ? k_train_persistent_split<true> : k_train_persistent_split<false>;
+    const NarrowKernel nk = train_narrow_kernel((km->d & 255) != 0, prof);
+    const SplitKernel sk = train_split_kernel(prof);
+    int occ = 0, occ_split = 0;
+    ACAV_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void *>(nk), 256, 0));
+    if (km->d > TP_DS && km->d <= 2 * TS_COLS) {  // (the only widths the split kernel takes)
         ACAV_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(sk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TS_SMEM));
-        int occ2 = 0;
-        ACAV_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ2, reinterpret_cast<const void *>(sk), 256, TS_SMEM));
-        split_wg = s_ncg * s_nrg * 2;
-        if (occ2 >= 1 && split_wg <= occ2 * km->num_cus && split_wg <= (budget ? *budget : occ2 * km->num_cus)) split = persistent = true;
+        ACAV_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_split, reinterpret_cast<const void *>(sk), 256, TS_SMEM));
     }
-    if (!persistent) return ACAV_OK;
-    tc.nwg = split ? split_wg : wide ? wide_wg : nwg;
-    tc.is_split = split;
-    if (budget && !tc.shared) *budget -= tc.nwg;
+    const TrainForm f = train_pick_form({km->d, km->K, b, ((uintptr_t)fx & 15) == 0},
+                                        {km->num_cus, occ, occ_split, budget != nullptr, budget ? *budget : 0, share_lds}, train_switches());
+    tc.form = f;
+    tc.prof = prof;
+    if (f.kind == TRAIN_NONE) return ACAV_OK;
+    if (f.shared && getenv("ACAV_TRAIN_SHARE_DEBUG")) fprintf(stderr, "[acav] shared launch: d = %d, K = %d, %d workgroups of %zu B beside the split kernel (%d B free per CU)\n", km->d, km->K, f.nwg(), (size_t)f.smem, share_lds);
+    if (budget && !f.shared) *budget -= f.nwg();
     tc.thr.resize((size_t)steps);
     for (int64_t t = 0; t < steps; ++t)
         tc.thr[(size_t)t] = (float)pow((double)(km->count + t * b) / (double)km->K, km->reinit_p);
@@ -2638,48 +2419,26 @@ static int train_launch(acav_kmeans *km, TrainCall &tc, const float *x, int64_t 
     ACAV_TRY(km->ctl.ensure(sizeof(TrainCtl)));
     ACAV_HIP_TRY(hipMemsetAsync(km->ctl.p, 0, sizeof(TrainCtl), st));  // err = 0, every granule tag = 0 (never a live tag)
     // the state as it is now, in case the launch gives up (1 MB at K=256, d=1024: a few microseconds)
-    const size_t cbytes = sizeof(float) * (size_t)km->K * km->d, kbytes = sizeof(float) * (size_t)km->K;
-    ACAV_TRY(km->backup.ensure(cbytes + 2 * kbytes + sizeof(StepScalars)));
-    char *bk = km->backup.as<char>();
-    ACAV_HIP_TRY(hipMemcpyAsync(bk, km->centers.p, cbytes, hipMemcpyDeviceToDevice, st));
-    ACAV_HIP_TRY(hipMemcpyAsync(bk + cbytes, km->cn.p, kbytes, hipMemcpyDeviceToDevice, st));
-    ACAV_HIP_TRY(hipMemcpyAsync(bk + cbytes + kbytes, km->counts.p, kbytes, hipMemcpyDeviceToDevice, st));
-    ACAV_HIP_TRY(hipMemcpyAsync(bk + cbytes + 2 * kbytes, km->scalars.p, sizeof(StepScalars), hipMemcpyDeviceToDevice, st));
-    if (split) {
-        tc.prof = false;
-        tc.split_prof = prof;
-        const size_t t0b = sizeof(unsigned long long) * (size_t)s_ncg * s_nrg * 256, nrb = sizeof(unsigned long long) * (size_t)s_ncg * s_nrg * TS_NC * 32;
+    ACAV_TRY(train_state_copy(km, false));
+    const dim3 grid((unsigned)f.gx, (unsigned)f.gy, (unsigned)f.gz);
+    if (f.kind == TRAIN_SPLIT) {
+        const size_t t0b = sizeof(unsigned long long) * (size_t)f.gx * f.gy * 256, nrb = sizeof(unsigned long long) * (size_t)f.gx * f.gy * TS_NC * 32;
         ACAV_TRY(km->split_rings.ensure(t0b + nrb));
         ACAV_HIP_TRY(hipMemsetAsync(km->split_rings.p, 0, t0b + nrb, st));  // every hand-off tag = 0 (never a live tag)
         unsigned long long *t0r = km->split_rings.as<unsigned long long>();
-        hipLaunchKernelGGL((prof ? k_train_persistent_split<true> : k_train_persistent_split<false>), dim3((unsigned)s_ncg, (unsigned)s_nrg, 2), dim3(256), TS_SMEM, st, fx,
-                           km->xn.as<float>(), (int)b, km->d, km->K, km->centers.as<float>(), km->cn.as<float>(),
-                           km->counts.as<float>(), km->thr.as<float>(), lr, (float)km->reinit_r, tc.dw, (int)need, (int)steps,
-                           km->ctl.as<TrainCtl>(), km->scalars.as<StepScalars>(), t0r, t0r + t0b / sizeof(unsigned long long));
-    } else if (!wide) {
-        hipLaunchKernelGGL(tkern, dim3((km->K + TP_NC - 1) / TP_NC, (unsigned)((b + TP_NR - 1) / TP_NR)),
-                           dim3(256), 0, st, fx, km->xn.as<float>(), (int)b, km->d, km->K, km->centers.as<float>(),
-                           km->cn.as<float>(), km->counts.as<float>(), km->thr.as<float>(), lr, (float)km->reinit_r,
-                           tc.dw, (int)need, (int)steps, km->ctl.as<TrainCtl>(), km->scalars.as<StepScalars>(), nwg);
-    } else {
-        tc.prof = false;  // the wide kernel carries no phase timers
-        using WideKernel = void (*)(const float *, const float *, int, int, int, int, float *, float *, float *, const float *,
-                                    double, float, const int64_t *, int, int, TrainCtl *, StepScalars *);
-        WideKernel wk = nullptr;
-        if (km->d > TP_DS) {  // the tall forms: one or two centre passes, one or two row buffers
-            if (ragged) wk = ncp == 1 ? (one_x ? k_train_persistent_wide<true, 1, true> : k_train_persistent_wide<true, 1, false>)
-                                      : (one_x ? k_train_persistent_wide<true, 2, true> : k_train_persistent_wide<true, 2, false>);
-            else wk = ncp == 1 ? (one_x ? k_train_persistent_wide<false, 1, true> : k_train_persistent_wide<false, 1, false>)
-                               : (one_x ? k_train_persistent_wide<false, 2, true> : k_train_persistent_wide<false, 2, false>);
-        } else if (nrp == 2) wk = ragged ? k_train_persistent_wide<true, 2, true, 2> : k_train_persistent_wide<false, 2, true, 2>;
-        else if (one_x && ncp == 2) wk = ragged ? k_train_persistent_wide<true, 2, true> : k_train_persistent_wide<false, 2, true>;  // (beside the split kernel)
-        else if (ragged) wk = ncp == 2 ? k_train_persistent_wide<true, 2> : ncp == 4 ? k_train_persistent_wide<true, 4> : k_train_persistent_wide<true, 8>;
-        else wk = ncp == 2 ? k_train_persistent_wide<false, 2> : ncp == 4 ? k_train_persistent_wide<false, 4> : k_train_persistent_wide<false, 8>;
-        ACAV_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(wk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wide_smem));
-        hipLaunchKernelGGL(wk, dim3((km->K + 8 * ncp - 1) / (8 * ncp), (unsigned)((b + 8 * nrp - 1) / (8 * nrp))), dim3(256), wide_smem, st,
-                           fx, km->xn.as<float>(), (int)b, km->d, ds, km->K, km->centers.as<float>(), km->cn.as<float>(),
-                           km->counts.as<float>(), km->thr.as<float>(), lr, (float)km->reinit_r, tc.dw, (int)need, (int)steps,
-                           km->ctl.as<TrainCtl>(), km->scalars.as<StepScalars>());
+        hipLaunchKernelGGL(sk, grid, dim3(256), f.smem, st, fx, km->xn.as<float>(), (int)b, km->d, km->K, km->centers.as<float>(),
+                           km->cn.as<float>(), km->counts.as<float>(), km->thr.as<float>(), lr, (float)km->reinit_r, tc.dw, (int)need,
+                           (int)steps, km->ctl.as<TrainCtl>(), km->scalars.as<StepScalars>(), t0r, t0r + t0b / sizeof(unsigned long long));
+    } else if (f.kind == TRAIN_NARROW) {
+        hipLaunchKernelGGL(nk, grid, dim3(256), 0, st, fx, km->xn.as<float>(), (int)b, km->d, km->K, km->centers.as<float>(),
+                           km->cn.as<float>(), km->counts.as<float>(), km->thr.as<float>(), lr, (float)km->reinit_r, tc.dw, (int)need,
+                           (int)steps, km->ctl.as<TrainCtl>(), km->scalars.as<StepScalars>(), f.nwg());
+    } else {  // (the wide kernel carries no ACAV_PROFILE_STEPS timers)
+        const WideKernel wk = f.ragged ? train_wide_kernel<true>(f) : train_wide_kernel<false>(f);
+        ACAV_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(wk), hipFuncAttributeMaxDynamicSharedMemorySize, f.smem));
+        hipLaunchKernelGGL(wk, grid, dim3(256), f.smem, st, fx, km->xn.as<float>(), (int)b, km->d, f.ds, km->K, km->centers.as<float>(),
+                           km->cn.as<float>(), km->counts.as<float>(), km->thr.as<float>(), lr, (float)km->reinit_r, tc.dw, (int)need,
+                           (int)steps, km->ctl.as<TrainCtl>(), km->scalars.as<StepScalars>());
     }
     ACAV_HIP_TRY(hipGetLastError());
     tc.launched = true;
@@ -2693,19 +2452,23 @@ static int train_finish(acav_kmeans *km, TrainCall &tc)
     hipStream_t st = km->ctx.stream;
     const int64_t steps = tc.steps, need = tc.need, b = tc.b;
     if (tc.launched) {
-        const bool prof = tc.prof;
-        const int nwg = tc.nwg;
-        struct { unsigned err, pad[3]; unsigned long long prof[8]; unsigned long long prof_wg[256][8]; } head{};
-        ACAV_HIP_TRY(hipMemcpyAsync(&head, km->ctl.p, prof ? sizeof(head) : 16, hipMemcpyDeviceToHost, st));
+        // the head of the control block: the error flag, and the timers in front of the granules when a diagnostic asked for them
+        bool timers = tc.prof && tc.form.kind != TRAIN_WIDE;
+#ifdef ACAV_WIDE_PROF
+        timers = true;
+#endif
+        const std::unique_ptr<TrainCtl> headp(new TrainCtl);
+        const TrainCtl &head = *headp;
+        ACAV_HIP_TRY(hipMemcpyAsync(headp.get(), km->ctl.p, timers ? offsetof(TrainCtl, gran) : offsetof(TrainCtl, prof), hipMemcpyDeviceToHost, st));
         ACAV_HIP_TRY(hipStreamSynchronize(st));  // also covers the thr staging vector
-        if (prof) {
-            const double den = (double)(steps > need ? steps - need : 1);
+        const double den = (double)(steps > need ? steps - need : 1);
+        if (tc.prof && tc.form.kind == TRAIN_NARROW) {
             fprintf(stderr, "[acav] persistent epoch: %lld steps; cycles/step: wait+dma-issue %.0f, fma %.0f, exchange %.0f, "
                             "update %.0f (fma chain alone %.0f, rows+apply %.0f), total %.0f\n", (long long)steps, head.prof[0] / den,
                     head.prof[1] / den, head.prof[2] / den, head.prof[3] / den, head.prof[5] / den, head.prof[6] / den,
                     head.prof[4] / den);
             double mx[4] = {0, 0, 0, 0}, mn[4] = {1e30, 1e30, 1e30, 1e30};
-            for (int w = 0; w < nwg && w < 256; ++w)
+            for (int w = 0; w < tc.form.nwg() && w < 256; ++w)
                 for (int q = 0; q < 4; ++q) {
                     const double v = head.prof_wg[w][q] / den;
                     mx[q] = v > mx[q] ? v : mx[q];
@@ -2715,34 +2478,27 @@ static int train_finish(acav_kmeans *km, TrainCall &tc)
                     mx[0], mn[1], mx[1], mn[2], mx[2], mn[3], mx[3], head.prof[7] / den);
         }
 #ifdef ACAV_WIDE_PROF
-        {
-            struct { unsigned err, pad[3]; unsigned long long prof[8]; unsigned long long up[8]; } hw{};
-            ACAV_HIP_TRY(hipMemcpy(&hw, km->ctl.p, sizeof(hw), hipMemcpyDeviceToHost));
-            const double den = (double)(hw.prof[5] ? hw.prof[5] : 1);
-            if (hw.prof[5])
-                fprintf(stderr, "[acav] wide epoch (%d workgroups): cycles/step of workgroup (1, 0): row wait %.0f, fma %.0f, keys + exchange %.0f, update %.0f, "
-                                "total %.0f; sweep passes/step %.2f; steps with an update of mine %.3f\n", tc.nwg, hw.prof[0] / den, hw.prof[1] / den,
-                        hw.prof[2] / den, hw.prof[3] / den, hw.prof[4] / den, hw.prof[7] / den, hw.prof[6] / den);
-            if (hw.prof[5])
-                fprintf(stderr, "[acav]   wave 0 inside keys + exchange: keys epilogue %.0f, publish + sweep %.0f (first pass %.0f), sweep end -> past the barrier %.0f\n",
-                        hw.up[4] / den, hw.up[5] / den, hw.up[6] / den, hw.up[7] / den);
-            if (hw.prof[6]) {
-                const double dt = (double)hw.prof[6];
+        if (head.prof[5]) {
+            const unsigned long long *up = head.wide_up;
+            const double den = (double)head.prof[5];
+            fprintf(stderr, "[acav] wide epoch (%d workgroups): cycles/step of workgroup (1, 0): row wait %.0f, fma %.0f, keys + exchange %.0f, update %.0f, "
+                            "total %.0f; sweep passes/step %.2f; steps with an update of mine %.3f\n", tc.form.nwg(), head.prof[0] / den, head.prof[1] / den,
+                    head.prof[2] / den, head.prof[3] / den, head.prof[4] / den, head.prof[7] / den, head.prof[6] / den);
+            fprintf(stderr, "[acav]   wave 0 inside keys + exchange: keys epilogue %.0f, publish + sweep %.0f (first pass %.0f), sweep end -> past the barrier %.0f\n",
+                    up[4] / den, up[5] / den, up[6] / den, up[7] / den);
+            if (head.prof[6]) {
+                const double dt = (double)head.prof[6];
                 fprintf(stderr, "[acav]   per step WITH an update of mine: lr / labels %.0f, row loads issued -> landed %.0f, ballots + accumulate + centre rows "
-                                "rewritten %.0f, closing barrier %.0f\n", hw.up[0] / dt, hw.up[1] / dt, hw.up[2] / dt, hw.up[3] / dt);
+                                "rewritten %.0f, closing barrier %.0f\n", up[0] / dt, up[1] / dt, up[2] / dt, up[3] / dt);
             }
         }
 #endif
-        if (tc.split_prof) {
-            struct { unsigned err, pad[3]; unsigned long long prof[8]; unsigned long long wg0[8]; } hs{};
-            ACAV_HIP_TRY(hipMemcpy(&hs, km->ctl.p, sizeof(hs), hipMemcpyDeviceToHost));
-            const double den = (double)(steps > need ? steps - need : 1);
+        if (tc.prof && tc.form.kind == TRAIN_SPLIT)
             for (int h2 = 1; h2 >= 0; --h2) {
-                const unsigned long long *v = h2 ? hs.prof : hs.wg0;
+                const unsigned long long *v = h2 ? head.prof : head.split_half0;
                 fprintf(stderr, "[acav] split epoch, column half %d: cycles/step: row wait %.0f, fma+norms %.0f, hand-off+keys %.0f, sweep %.0f, "
                                 "update %.0f, total %.0f\n", h2, v[0] / den, v[1] / den, v[2] / den, v[3] / den, v[4] / den, v[5] / den);
             }
-        }
         if (head.err == 0) {
             km->count += steps * b;
             km->cb16_valid = false;
@@ -2754,12 +2510,7 @@ static int train_finish(acav_kmeans *km, TrainCall &tc)
         // the launch gave up at an exchange (not all workgroups resident: the GPU is shared): restore the state it
         // started from and take the per-step launch path for this call
         km->n_persistent_fallbacks += 1;
-        const size_t cbytes = sizeof(float) * (size_t)km->K * km->d, kbytes = sizeof(float) * (size_t)km->K;
-        char *bk = km->backup.as<char>();
-        ACAV_HIP_TRY(hipMemcpyAsync(km->centers.p, bk, cbytes, hipMemcpyDeviceToDevice, st));
-        ACAV_HIP_TRY(hipMemcpyAsync(km->cn.p, bk + cbytes, kbytes, hipMemcpyDeviceToDevice, st));
-        ACAV_HIP_TRY(hipMemcpyAsync(km->counts.p, bk + cbytes + kbytes, kbytes, hipMemcpyDeviceToDevice, st));
-        ACAV_HIP_TRY(hipMemcpyAsync(km->scalars.p, bk + cbytes + 2 * kbytes, sizeof(StepScalars), hipMemcpyDeviceToDevice, st));
+        ACAV_TRY(train_state_copy(km, true));
     }
     for (int64_t t = 0; t < steps; ++t) {
         const int64_t *f = t < need ? tc.dw + t * b : nullptr;
@@ -2820,13 +2571,13 @@ ACAV_EXPORT int acav_kmeans_train_multi(acav_kmeans *const *kms, int count, cons
                 int *bp = (inflight.empty() && pending.size() == 1) ? nullptr : &budget;
                 // LDS a second launch may use on every CU: only beside ONE in-flight column-split kernel
                 int share_lds = 0;
-                if (share_cu && bp != nullptr && inflight.size() == 1 && calls[(size_t)inflight[0]].is_split && !calls[(size_t)inflight[0]].shared)
-                    share_lds = 160 * 1024 - (int)TS_SMEM - 512;  // (LDS is handed out in 512-byte units; both kernels' static __shared__ is a few bytes)
+                if (share_cu && bp != nullptr && inflight.size() == 1 && calls[(size_t)inflight[0]].form.kind == TRAIN_SPLIT && !calls[(size_t)inflight[0]].form.shared)
+                    share_lds = TRAIN_LDS_PER_CU - (int)TS_SMEM - 512;  // (LDS is handed out in 512-byte units; both kernels' static __shared__ is a few bytes)
                 ACAV_TRY(train_launch(kms[i], tc, xs[i], ns[i], b, lr, warm_best ? warm_best[i] : nullptr, n_warm[i], bp, share_lds));
                 if (tc.active && !tc.launched && inflight.empty() && bp != nullptr && budget == cus) {
                     // does not fit beside others even on an empty device: as a call for one clustering (whole-device forms)
                     ACAV_TRY(train_launch(kms[i], tc, xs[i], ns[i], b, lr, warm_best ? warm_best[i] : nullptr, n_warm[i], nullptr));
-                    if (tc.launched) budget -= tc.nwg < budget ? tc.nwg : budget;  // (train_launch only books a budget it was given)
+                    if (tc.launched) budget -= tc.form.nwg() < budget ? tc.form.nwg() : budget;  // (train_launch only books a budget it was given)
                 }
                 if (!tc.active) {  // not even one batch: nothing to do
                     pending.erase(pending.begin() + (long)q);
@@ -2860,7 +2611,7 @@ ACAV_EXPORT int acav_kmeans_train_multi(acav_kmeans *const *kms, int count, cons
         (void)hipGetLastError();  // a hipErrorNotReady of this sweep must not surface in the next launch's error check
         const int i = inflight[done];
         inflight.erase(inflight.begin() + (long)done);
-        const int gave = calls[(size_t)i].shared ? 0 : calls[(size_t)i].nwg;  // (a shared launch booked no CUs)
+        const int gave = calls[(size_t)i].form.shared ? 0 : calls[(size_t)i].form.nwg();  // (a shared launch booked no CUs)
         ACAV_TRY(train_finish(kms[i], calls[(size_t)i]));  // a launch that gave up is re-run on the per-step path in here
         ACAV_TRY(kms[i]->prepare_filter());
         budget = budget + gave > cus ? cus : budget + gave;
