@@ -7,13 +7,13 @@
 #include <set>
 #include <tuple>
 
+#include "acav_kmeans_form.h"  // the tile constants (AS_*, FB_ROWS, FD_*, CAND_MAX) and assign_pick_plan()
 #include "acav_kmeans_shared.h"
 
 namespace {
 
 // --------------------------------------------------------------------------- k_assign_f32
 constexpr int AS_CG = 256;    // centres per group: 8 MFMA tiles, 2 per wave
-constexpr int AS_BK = 32;     // feature columns per LDS stage (= the 32 canonical sumsq classes)
 constexpr int AS_LD = 36;     // padded LDS row (floats): 144 B = 9 x 16 B -> conflict-free ds_read_b128
 
 // LDS image of one staged row: within each group of 8 columns the even columns come first
@@ -310,9 +310,6 @@ __global__ __launch_bounds__(256, GUARD ? 1 : 2) void k_assign_f32(const float *
 typedef _Float16 fl16;
 typedef _Float16 bf16x8 __attribute__((ext_vector_type(8)));  // (8 operand elements of one lane: the historical name stays)
 
-constexpr int FB_ROWS = 128;  // rows per workgroup (4 MFMA row tiles)
-constexpr int FILTER_NW_DEFAULT = 4, FILTER_SCHED_DEFAULT = 0;  // K <= 256 defaults of k_assign_f16_rw (see acav_kmeans_assign)
-
 struct CentersAux {
     unsigned cmax_bits;   // bits of max_k ||c_k||^2 (non-negative floats order like unsigned)
     unsigned cmaxc_bits;  // bits of (an upper bound of) max_k ||c'_k||^2 of the copy the filter multiplies by
@@ -518,11 +515,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 //   * canonical ||x||^2: wave w accumulates the 16 classes per lane of row tile w (both k-steps).
 //   * the epilogue scratch aliases the row ring; it multiplies by 1/r where the exact path divides by r (inside
 //     the e2 term of the acceptance bound).
-constexpr int FD_BK = 32;
-constexpr int FD_DX = 3;  // row ring depth (2 stages = 32 KB in flight per workgroup, two workgroups per CU)
-constexpr int FD_DC = 2;  // centre ring depth (1 stage in flight: an L2 round trip is shorter than a stage)
-constexpr int FD_SLOT = 16384;  // bytes per ring slot: 128 rows x 32 fp32 == 256 centres x 32 bf16
-constexpr int FD_SMEM = (FD_DX + FD_DC) * FD_SLOT;  // 80 KB: two workgroups fill the CU's 160 KB
+// (FD_BK = 32 columns per stage, rings of FD_DX = 3 row and FD_DC = 2 centre slots of FD_SLOT = 16 KB: acav_kmeans_form.h)
 
 // LDS byte address of a __shared__ pointer (wave-uniform) and a 16-byte-per-lane LDS-DMA issued from inline asm:
 // lane l's 16 bytes at gbase + voff(l) land at lds + 16 l.  The compiler does not see the pending LDS write, so the
@@ -768,7 +761,6 @@ __device__ __forceinline__ float cand_threshold(float d1, float E)
     const float u = d1 + W;
     return u + 3.2e-5f * fabsf(u) + 1.6e-6f * (fabsf(d1) + W);
 }
-constexpr unsigned CAND_MAX = 16;  // candidates per row beyond which the row takes the full exact sweep
 __device__ __forceinline__ AssignCtl *ctl_of_f32_count(const unsigned *f32_count)
 {
     return reinterpret_cast<AssignCtl *>(reinterpret_cast<char *>(const_cast<unsigned *>(f32_count)) - offsetof(AssignCtl, f32_count));
@@ -1611,16 +1603,21 @@ int acav_kmeans::prepare_filter()
         ACAV_HIP_TRY(hipStreamSynchronize(st));
         filter_rows_scaled = sx_host != 1.0f;
     }
-    cb16_valid = true;
-    // the sweep's one-time objects, so that the first sweep of a handle does not create them inside its own timing
-    if (!ev_f0) {
-        ACAV_HIP_TRY(hipEventCreate(&ev_f0));
-        ACAV_HIP_TRY(hipEventCreate(&ev_f1));
+    // the sweep's one-time objects, so that no sweep creates them inside its own timing: the CU count its grids are sized by, the
+    // events around the filter launch, and the control block -- zero when a sweep starts: zeroed here once, and by the last kernel
+    // of every sweep
+    if (num_cus == 0) {
+        hipDeviceProp_t prop;
+        ACAV_HIP_TRY(hipGetDeviceProperties(&prop, ctx.device));
+        num_cus = prop.multiProcessorCount;
     }
+    if (!ev_f0) ACAV_HIP_TRY(hipEventCreate(&ev_f0));
+    if (!ev_f1) ACAV_HIP_TRY(hipEventCreate(&ev_f1));
     if (!cand_ctl.p) {
         ACAV_TRY(cand_ctl.ensure(sizeof(AssignCtl)));
         ACAV_HIP_TRY(hipMemsetAsync(cand_ctl.p, 0, sizeof(AssignCtl), st));
     }
+    cb16_valid = true;  // last: a valid copy implies everything above exists
     return ACAV_OK;
 }
 
@@ -1681,6 +1678,62 @@ ACAV_EXPORT int acav_kmeans_filter_time(acav_kmeans *km, float *ms)
     return ACAV_OK;
 }
 
+// the experiment switches of the plan, read from the environment in this one place (first character only)
+static AssignSwitches assign_switches()
+{
+    auto first = [](const char *name) {
+        const char *v = getenv(name);
+        return v ? v[0] : '\0';
+    };
+    AssignSwitches sw;
+    sw.exact_only = first("ACAV_ASSIGN_EXACT_ONLY") == '1';
+    sw.pad = first("ACAV_FILTER_PAD") != '0';
+    sw.cand = first("ACAV_ASSIGN_CAND") != '0';
+    sw.emit = first("ACAV_ASSIGN_EMIT") == '0' ? 0 : first("ACAV_ASSIGN_EMIT") == '1' ? 1 : 2;
+    if (const char *v = getenv("ACAV_CAND_PAIR_CAP")) sw.pair_cap = atol(v);
+    sw.nt = first("ACAV_FILTER_NT") != '0';
+    sw.gs = first("ACAV_FILTER_GS") != '0';
+    sw.nw = first("ACAV_FILTER_NW") == '8' ? 8 : first("ACAV_FILTER_NW") == '4' ? 4 : 0;
+    if (getenv("ACAV_FILTER_SCHED")) sw.sched = first("ACAV_FILTER_SCHED") == '2' ? 2 : 0;
+    return sw;
+}
+
+// The instantiation of k_assign_f16_rw a plan launches: its filter (emit = the plan's 0 or 2) or its emission pass (emit = 1).
+// Every instantiation the library holds appears here once; nullptr for any other combination.
+using FilterKern = decltype(&k_assign_f16_rw<true, 4, false>);
+static FilterKern assign_filter_kernel(const AssignPlan &p, int emit)
+{
+    switch (emit == 1 ? p.emit_kernel() : p.filter_kernel()) {
+#define ACAV_FILTER_KERNEL(NT, NW, GS, DCR, SCHED, EMIT, XS) \
+    case assign_kernel_id(NT, NW, GS, DCR, SCHED, EMIT, XS): return k_assign_f16_rw<NT, NW, GS, DCR, SCHED, EMIT, XS>;
+    // non-temporal rows / the default cache policy / scaled rows, for: 8-wave pairs, the 8-wave tile, 4-wave pairs,
+        ACAV_FILTER_KERNEL(true, 8, true, 3, 2, 0, false) ACAV_FILTER_KERNEL(false, 8, true, 3, 2, 0, false) ACAV_FILTER_KERNEL(true, 8, true, 3, 2, 0, true)
+        ACAV_FILTER_KERNEL(true, 8, false, 3, 2, 0, false) ACAV_FILTER_KERNEL(false, 8, false, 3, 2, 0, false) ACAV_FILTER_KERNEL(true, 8, false, 3, 2, 0, true)
+        ACAV_FILTER_KERNEL(true, 4, true, 2, 0, 0, false) ACAV_FILTER_KERNEL(false, 4, true, 2, 0, 0, false) ACAV_FILTER_KERNEL(true, 4, true, 2, 0, 0, true)
+    // the 4-wave tile with schedule 2, with the emission in place, lean, and the emission pass
+        ACAV_FILTER_KERNEL(true, 4, false, 2, 2, 0, false) ACAV_FILTER_KERNEL(false, 4, false, 2, 2, 0, false) ACAV_FILTER_KERNEL(true, 4, false, 2, 2, 0, true)
+        ACAV_FILTER_KERNEL(true, 4, false, 2, 0, 2, false) ACAV_FILTER_KERNEL(false, 4, false, 2, 0, 2, false) ACAV_FILTER_KERNEL(true, 4, false, 2, 0, 2, true)
+        ACAV_FILTER_KERNEL(true, 4, false, 2, 0, 0, false) ACAV_FILTER_KERNEL(false, 4, false, 2, 0, 0, false) ACAV_FILTER_KERNEL(true, 4, false, 2, 0, 0, true)
+        ACAV_FILTER_KERNEL(true, 4, false, 2, 0, 1, false) ACAV_FILTER_KERNEL(false, 4, false, 2, 0, 1, false) ACAV_FILTER_KERNEL(true, 4, false, 2, 0, 1, true)
+#undef ACAV_FILTER_KERNEL
+    default: return nullptr;
+    }
+}
+static decltype(&k_assign_f32<false>) assign_exact_kernel(bool guard) { return !guard ? k_assign_f32<false> : k_assign_f32<true>; }
+
+ACAV_EXPORT int acav_kmeans_assign_plan(int d, int k, int64_t n, int aligned, int need_mean, int rows_scaled, int cus, int *out)
+{
+    ACAV_REQUIRE(out, ACAV_EINVAL, "NULL argument");
+    ACAV_REQUIRE(d > 0 && d <= 16384 && k > 0 && (int64_t)k * d <= ((int64_t)1 << 30) && n > 0 && cus > 0, ACAV_EINVAL, "bad sizes");
+    const AssignPlan p = assign_pick_plan({d, k, n, aligned != 0, need_mean != 0, rows_scaled != 0}, {cus}, assign_switches());
+    auto clamp = [](int64_t v) { return (int)std::min<int64_t>(v, 0x7fffffff); };
+    const int v[ACAV_ASSIGN_PLAN_LEN] = {p.error, p.path, clamp(p.grid), p.fd, p.ragged, p.ngroups, p.gs, p.nw, p.nt, p.xs, p.sched, p.dcr,
+                                         p.emit, p.emit_pass, p.cand, p.und_list, (int)p.pair_cap, p.filter_kernel(), p.emit_kernel(),
+                                         clamp(p.fgrid), p.fblock, p.fsmem, clamp(p.egrid), p.eblock, p.esmem, clamp(p.rgrid), p.cgrid};
+    for (int i = 0; i < ACAV_ASSIGN_PLAN_LEN; ++i) out[i] = p.error ? (i == 0 ? p.error : 0) : v[i];
+    return ACAV_OK;
+}
+
 ACAV_EXPORT int acav_kmeans_assign(acav_kmeans *km, const float *x, int64_t n, int64_t *labels, float *mean_dist)
 {
     ACAV_REQUIRE(km, ACAV_EINVAL, "handle is NULL");
@@ -1703,191 +1756,104 @@ ACAV_EXPORT int acav_kmeans_assign(acav_kmeans *km, const float *x, int64_t n, i
         ACAV_TRY(km->stage_lab.ensure(sizeof(int64_t) * (size_t)n));
         dlab = km->stage_lab.as<int64_t>();
     }
-    const int64_t grid = (n + AS_ROWS - 1) / AS_ROWS;
-    ACAV_REQUIRE(grid <= 0x7fffffff, ACAV_EINVAL, "n too large for one launch");
-    ACAV_TRY(km->wg_sum.ensure(sizeof(double) * (size_t)grid));
-    const bool fast = (km->d % AS_BK) == 0 && ((uintptr_t)dx & 15) == 0;
-    // bf16 filter + exact re-check (bit-identical labels, HBM-bound when the clusters are separated): taken when
-    // the caller does not need the mean distance (the filter's distances are approximate)
-    const char *noflt = getenv("ACAV_ASSIGN_EXACT_ONLY");
-    // d % 32 != 0 (88-wide SlowFast layer): the filter sweep runs on zero-padded copies of the rows and the centres (k_pad_rows;
-    // ACAV_FILTER_PAD=0: the guarded exact sweep as before)
-    const char *vpad = getenv("ACAV_FILTER_PAD");
-    const bool ragged = (km->d % FD_BK) != 0;
-    const bool filter = !mean_dist && (ragged ? !(vpad && vpad[0] == '0') : fast) && km->K >= 2 && n >= FB_ROWS &&
-                        !(noflt && noflt[0] == '1') && n < 0x7fffffff;
-    if (filter) {
+
+    // ---- the plan.  The filter is taken when the caller does not need the mean distance (the filter's distances are approximate);
+    // its plan needs the centre copy first, which says whether the rows are scaled (and brings the CU count)
+    AssignShape shape = {km->d, km->K, n, ((uintptr_t)dx & 15) == 0, mean_dist != nullptr, false};
+    const AssignSwitches sw = assign_switches();
+    if (assign_wants_filter(shape, sw)) {
         ACAV_TRY(km->prepare_filter());
-        const int fd = km->filter_d();  // the width the sweep runs at
-        const float *fc = km->centers.as<float>();
-        if (ragged) {
-            ACAV_TRY(km->xpad.ensure(sizeof(float) * (size_t)n * fd));
-            hipLaunchKernelGGL(k_pad_rows, dim3((unsigned)std::min<int64_t>((n * fd + 255) / 256, 65536)), dim3(256), 0, st,
-                               static_cast<const float *>(dx), km->xpad.as<float>(), n, km->d, fd);
-            dx = km->xpad.p;
+        shape.rows_scaled = km->filter_rows_scaled;
+    }
+    const AssignPlan p = assign_pick_plan(shape, {km->num_cus}, sw);
+    ACAV_REQUIRE(p.error == ASSIGN_PLAN_OK, ACAV_EINVAL, "n too large for one launch");
+
+    // ---- buffers, kernels and their LDS attributes
+    ACAV_TRY(km->wg_sum.ensure(sizeof(double) * (size_t)p.grid));
+    FilterKern fk = nullptr, ek = nullptr;
+    if (p.path == ASSIGN_FILTER) {
+        if (p.ragged) ACAV_TRY(km->xpad.ensure(sizeof(float) * (size_t)n * p.fd));
+        ACAV_TRY(km->recheck_list.ensure(sizeof(int) * (size_t)n * 2));  // [undecided rows | rows for the full exact sweep]
+        if (p.cand) {
+            ACAV_TRY(km->cand_rows.ensure(sizeof(CandRow) * (size_t)n));
+            ACAV_TRY(km->cand_pairs.ensure(sizeof(CandPair) * (size_t)p.pair_cap));
+            if (p.ngroups > 1) ACAV_TRY(km->cand_T.ensure(sizeof(float) * (size_t)n));
+        }
+        if (p.gs) ACAV_TRY(km->grec.ensure(sizeof(Top2Rec) * (size_t)p.ngroups * (size_t)n));
+        fk = assign_filter_kernel(p, p.emit);
+        ek = p.emit_pass ? assign_filter_kernel(p, 1) : nullptr;
+        ACAV_REQUIRE(fk && (ek || !p.emit_pass), ACAV_ESTATE, "internal: no k_assign_f16_rw instantiation for plan %d / %d",
+                     p.filter_kernel(), p.emit_kernel());
+        ACAV_TRY(dyn_lds_once(reinterpret_cast<const void *>(fk), km->ctx.device, p.fsmem));
+        if (ek) ACAV_TRY(dyn_lds_once(reinterpret_cast<const void *>(ek), km->ctx.device, p.esmem));
+    }
+
+    // ---- launches
+    const float *fx = static_cast<const float *>(dx), *fc = km->centers.as<float>();
+    const float *cn = km->cn.as<float>(), *counts = km->counts.as<float>();
+    const float thr = km->threshold(), r = (float)km->reinit_r;
+    // the exact sweep: over all rows (list == NULL), or the rows of a list whose length only the device knows
+    auto exact_launch = [&](bool guard, int64_t grid, int width, const int *list, const unsigned *count) {
+        hipLaunchKernelGGL(assign_exact_kernel(guard), dim3((unsigned)grid), dim3(256), 0, st, fx, n, width, fc, cn, counts, km->K, thr, r,
+                           dlab, (float *)nullptr, km->wg_sum.as<double>(), list, count);
+    };
+    if (p.path == ASSIGN_FILTER) {
+        if (p.ragged) {  // the sweep (and its exact re-check) run on zero-padded copies of the rows and the centres
+            hipLaunchKernelGGL(k_pad_rows, dim3((unsigned)std::min<int64_t>((n * p.fd + 255) / 256, 65536)), dim3(256), 0, st, fx,
+                               km->xpad.as<float>(), n, km->d, p.fd);
+            fx = km->xpad.as<float>();
             fc = km->cpad.as<float>();
         }
-        ACAV_TRY(km->recheck_list.ensure(sizeof(int) * (size_t)n * 2));  // [undecided rows | rows for the full exact sweep]
-        // control block of the sweep: zero when a sweep starts -- zeroed here once, and by the last kernel of every sweep
-        if (!km->cand_ctl.p) {
-            ACAV_TRY(km->cand_ctl.ensure(sizeof(AssignCtl)));
-            ACAV_HIP_TRY(hipMemsetAsync(km->cand_ctl.p, 0, sizeof(AssignCtl), st));
-        }
         AssignCtl *ctl = km->cand_ctl.as<AssignCtl>();
-        unsigned *f32_count = &ctl->f32_count;
-        // candidate-restricted exact re-check (K <= 256: the filter's epilogue emits the candidates); ACAV_ASSIGN_CAND=0
-        // sends every undecided row to the full exact sweep as in round 3
-        const char *vcand = getenv("ACAV_ASSIGN_CAND");
-        // (K > 256: through the emission pass over the rows k_assign_merge lists.  n < 2^27: slots and pairs -- at most 16 per row --
-        // share one 64-bit allocator word, 32 bits each)
-        const bool cand = !(vcand && vcand[0] == '0') && n < ((int64_t)1 << 27);
-        // ACAV_ASSIGN_EMIT=0: experiment -- the lean filter kernel (no emission code) even with the candidate path on
-        // ACAV_ASSIGN_EMIT: 0 = no emission at all (undecided rows -> full exact sweep), 1 = lean filter + emission pass over the
-        // undecided rows, 2 (default) = emission in place in the filter's own epilogue (one pass)
-        const char *vemit = getenv("ACAV_ASSIGN_EMIT");
-        const bool emit_allowed = !(vemit && vemit[0] == '0');
-        const bool emit_inplace = !(vemit && vemit[0] == '1');
-        const uint64_t pair_cap64 = std::min<uint64_t>(std::max<uint64_t>(4ull * (uint64_t)n, 65536ull), 0x7fffffffull);
-        unsigned pair_cap = (unsigned)pair_cap64;
-        if (const char *vcap = getenv("ACAV_CAND_PAIR_CAP")) {  // tests: force the pool-overflow path
-            const long v = atol(vcap);
-            if (v > 0 && (uint64_t)v < pair_cap64) pair_cap = (unsigned)v;
-        }
-        if (cand) {
-            ACAV_TRY(km->cand_rows.ensure(sizeof(CandRow) * (size_t)n));
-            ACAV_TRY(km->cand_pairs.ensure(sizeof(CandPair) * (size_t)pair_cap));
-            if (km->K > 256) ACAV_TRY(km->cand_T.ensure(sizeof(float) * (size_t)n));
-        }
-        CandRow *crow = cand ? km->cand_rows.as<CandRow>() : (CandRow *)nullptr;
-        CandPair *cpair = cand ? km->cand_pairs.as<CandPair>() : (CandPair *)nullptr;
         int *und_list = km->recheck_list.as<int>(), *f32_list = und_list + n;
-        const CandOut cout = {crow, cpair, f32_list, cand && km->K > 256 ? km->cand_T.as<float>() : (float *)nullptr, pair_cap};
-        const double acc = 1.01 * (double)fd * ldexp(1.0, -24);  // accumulation error of one fp32 dot, relative
+        int *list = p.und_list ? und_list : f32_list;
+        unsigned *count = p.und_list ? &ctl->und_count : &ctl->f32_count;
+        CandRow *crow = p.cand ? km->cand_rows.as<CandRow>() : (CandRow *)nullptr;
+        CandPair *cpair = p.cand ? km->cand_pairs.as<CandPair>() : (CandPair *)nullptr;
+        const CandOut cout = {crow, cpair, f32_list, p.cand && p.ngroups > 1 ? km->cand_T.as<float>() : (float *)nullptr, p.pair_cap};
+        Top2Rec *grec = p.gs ? km->grec.as<Top2Rec>() : (Top2Rec *)nullptr;
+        const CentersAux *aux = km->caux.as<CentersAux>();
+        const double acc = 1.01 * (double)p.fd * ldexp(1.0, -24);  // accumulation error of one fp32 dot, relative
         const float e1c = (float)(2.02 * (ldexp(1.0, -10) * 1.002 + acc) * 1.001);  // x ||c'|| ||x||: half roundings (2^-11 per operand) + filter dot
         const float e1r = (float)(2.02 * (acc + ldexp(1.0, -24)) * 1.001);           // x ||c|| ||x||: canonical dot, c - mu
-        // rows are read exactly once: non-temporal DMA policy (ACAV_FILTER_NT=0 restores the default policy)
-        const char *vnt = getenv("ACAV_FILTER_NT");
-        const bool nt = !(vnt && vnt[0] == '0');
-        constexpr bool rw = true;  // (round 1's wave layout, ACAV_FILTER_V1, went with the move to half-precision operands)
         const float e2 = (float)ldexp(1.0, -20);  // epilogue roundings only, the tag is charged separately
-        // Tile shape and DMA schedule of k_assign_f16_rw (template parameters there).  K > 256: one workgroup per (row tile,
-        // centre group) pair, the pairs of a tile side by side on one XCD, 256-row tiles (8 waves), centre ring of 3, DMA
-        // pieces spread between the MFMAs -- rows from HBM once.  Knobs for A/B runs: ACAV_FILTER_GS=0 (loop over the groups
-        // inside one workgroup), ACAV_FILTER_NW=4|8, ACAV_FILTER_SCHED=0|2.
-        const int ngroups = (km->K + 255) / 256;
-        const char *vgs = getenv("ACAV_FILTER_GS"), *vnw = getenv("ACAV_FILTER_NW"), *vsc = getenv("ACAV_FILTER_SCHED");
-        const bool gs = rw && ngroups > 1 && !(vgs && vgs[0] == '0');
-        // (narrow views, d <= 256: a pair is only 4-8 stages long and its ring fill and epilogue weigh as much as its stage loop
-        // -- two 128-row workgroups per CU hide them under each other: d = 128, K = 1024: 0.59 vs 0.72 ms per 1.25M rows)
-        const int nw = !rw ? 4 : (vnw && vnw[0] == '8') ? 8 : (vnw && vnw[0] == '4') ? 4 : (gs ? (fd <= 256 ? 4 : 8) : FILTER_NW_DEFAULT);
-        const bool nt_eff = gs ? !(vnt && vnt[0] == '0') : nt;  // nt rows are still found in L2 by the tile's other groups (PMC)
-        const int dcr = nw == 8 ? 3 : 2;  // centre ring depth (3 only fits the one-workgroup-per-CU tile)
-        const int sched = nw == 8 ? 2 : (vsc ? (vsc[0] == '2' ? 2 : 0) : FILTER_SCHED_DEFAULT);
-        typedef void (*FilterKern)(const float *, int64_t, int, const fl16 *, const float *, const float *, int, float, float,
-                                   const CentersAux *, float, float, float, int64_t *, int *, unsigned *, AssignCtl *, Top2Rec *,
-                                   CandOut);
-        FilterKern rwk = nullptr;
-        // K <= 256: the filter emits in place (or, ACAV_ASSIGN_EMIT=1, lists for the emission pass); K > 256: the (tile, group) pairs
-        // cannot know a row's minimum over all groups -- k_assign_merge lists the undecided rows with their thresholds and the
-        // emission pass runs the filter's main loop once more over those rows, all groups in one workgroup
-        const bool emit_gs = cand && emit_allowed && rw && gs;
-        const bool emit = cand && emit_allowed && rw && ((!gs && ngroups == 1 && nw == 4 && sched == 0) || emit_gs);
-        if (rw) {
-            // (rows scaled before the conversion: the XS instantiations, non-temporal rows only)
-            const bool xs = km->filter_rows_scaled;
-            if (nw == 8) rwk = gs ? (xs ? k_assign_f16_rw<true, 8, true, 3, 2, 0, true> : nt_eff ? k_assign_f16_rw<true, 8, true, 3, 2> : k_assign_f16_rw<false, 8, true, 3, 2>)
-                                  : (xs ? k_assign_f16_rw<true, 8, false, 3, 2, 0, true> : nt_eff ? k_assign_f16_rw<true, 8, false, 3, 2> : k_assign_f16_rw<false, 8, false, 3, 2>);
-            else if (gs) rwk = xs ? k_assign_f16_rw<true, 4, true, 2, 0, 0, true> : nt_eff ? k_assign_f16_rw<true, 4, true, 2, 0> : k_assign_f16_rw<false, 4, true, 2, 0>;
-            else if (sched == 2) rwk = xs ? k_assign_f16_rw<true, 4, false, 2, 2, 0, true> : nt_eff ? k_assign_f16_rw<true, 4, false, 2, 2> : k_assign_f16_rw<false, 4, false, 2, 2>;
-            else if (emit && emit_inplace && !emit_gs)
-                rwk = xs ? k_assign_f16_rw<true, 4, false, 2, 0, 2, true> : nt_eff ? k_assign_f16_rw<true, 4, false, 2, 0, 2> : k_assign_f16_rw<false, 4, false, 2, 0, 2>;
-            else rwk = xs ? k_assign_f16_rw<true, 4, false, 2, 0, 0, true> : nt_eff ? k_assign_f16_rw<true, 4, false, 2, 0> : k_assign_f16_rw<false, 4, false, 2, 0>;
-        }
-        const int fsmem = FD_DX * nw * 4096 + dcr * FD_SLOT;
-        const int64_t tile_rows = (int64_t)nw * 32, ntiles = (n + tile_rows - 1) / tile_rows;
-        const int64_t fgrid = gs ? (ntiles + 7) / 8 * 8 * ngroups : ntiles;
-        ACAV_REQUIRE(fgrid <= 0x7fffffff, ACAV_EINVAL, "n too large for one launch");
-        if (gs) ACAV_TRY(km->grec.ensure(sizeof(Top2Rec) * (size_t)ngroups * (size_t)n));
-        if (!km->ev_f0) {
-            ACAV_HIP_TRY(hipEventCreate(&km->ev_f0));
-            ACAV_HIP_TRY(hipEventCreate(&km->ev_f1));
-        }
-        if (rw) {
-            ACAV_TRY(dyn_lds_once(reinterpret_cast<const void *>(rwk), km->ctx.device, fsmem));
-            ACAV_HIP_TRY(hipEventRecord(km->ev_f0, st));
-            hipLaunchKernelGGL(rwk, dim3((unsigned)fgrid), dim3(nw * 64), fsmem, st, static_cast<const float *>(dx), n, fd,
-                               km->cb16.as<fl16>(), km->cn.as<float>(), km->counts.as<float>(), km->K, km->threshold(),
-                               (float)km->reinit_r, km->caux.as<CentersAux>(), e1c, e1r, e2, dlab, emit ? und_list : f32_list,
-                               emit ? &ctl->und_count : f32_count, ctl, gs ? km->grec.as<Top2Rec>() : (Top2Rec *)nullptr, cout);
-            if (gs)
-                hipLaunchKernelGGL(k_assign_merge, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, km->grec.as<Top2Rec>(),
-                                   ngroups, n, km->caux.as<CentersAux>(), e1c, e1r, e2, dlab, emit_gs ? und_list : f32_list,
-                                   emit_gs ? &ctl->und_count : f32_count, emit_gs ? cout.und_T : (float *)nullptr);
-        }
+        auto filter_launch = [&](FilterKern k, int64_t grid, int block, int smem, int *rows, unsigned *nrows, Top2Rec *rec) {
+            hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(block), smem, st, fx, n, p.fd, km->cb16.as<fl16>(), cn, counts, km->K, thr, r,
+                               aux, e1c, e1r, e2, dlab, rows, nrows, ctl, rec, cout);
+        };
+        ACAV_HIP_TRY(hipEventRecord(km->ev_f0, st));
+        filter_launch(fk, p.fgrid, p.fblock, p.fsmem, list, count, grec);
+        if (p.gs)
+            hipLaunchKernelGGL(k_assign_merge, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, grec, p.ngroups, n, aux, e1c, e1r, e2,
+                               dlab, list, count, p.und_list ? cout.und_T : (float *)nullptr);
         ACAV_HIP_TRY(hipGetLastError());
         ACAV_HIP_TRY(hipEventRecord(km->ev_f1, st));
-        // exact pass over the listed rows (no host round trip): a fixed grid of 2 workgroups per CU strides over
-        // however many row tiles the list turns out to hold
-        if (km->num_cus == 0) {
-            hipDeviceProp_t prop;
-            ACAV_HIP_TRY(hipGetDeviceProperties(&prop, km->ctx.device));
-            km->num_cus = prop.multiProcessorCount;
-        }
-        const int64_t rgrid = grid < 2 * (int64_t)km->num_cus ? grid : 2 * (int64_t)km->num_cus;
-        if (emit) {
-            // emission pass: the filter's main loop once more over the undecided rows only (a fixed grid strides over the tiles
-            // of the list), the epilogue emits each row's candidate centres; then the exact canonical chains of those (row,
-            // centre) pairs and the labels of those rows
-            if (!emit_inplace || emit_gs) {
-                // one workgroup per CU (rings + lists do not fit twice), 4 waves / 128 rows
-                // (round 6: the 8-wave emission instantiations are gone -- they kept 156-172 B of scratch and no run ever selected them
-                // outside A/B tests; the emission pass always runs 128-row tiles)
-                constexpr int enw = 4;
-                const bool xs = km->filter_rows_scaled;
-                FilterKern ek = xs ? k_assign_f16_rw<true, 4, false, 2, 0, 1, true> : nt ? k_assign_f16_rw<true, 4, false, 2, 0, 1> : k_assign_f16_rw<false, 4, false, 2, 0, 1>;
-                const int esmem = FD_DX * enw * 4096 + 2 * FD_SLOT + enw * 32 * (4 + 2 * (int)CAND_MAX);  // rings + lists
-                ACAV_TRY(dyn_lds_once(reinterpret_cast<const void *>(ek), km->ctx.device, esmem));
-                const int64_t erows = (int64_t)enw * 32;
-                const int64_t egrid = std::min<int64_t>((n + erows - 1) / erows, (int64_t)km->num_cus);
-                hipLaunchKernelGGL(ek, dim3((unsigned)egrid), dim3(enw * 64), esmem, st, static_cast<const float *>(dx), n, fd,
-                                   km->cb16.as<fl16>(), km->cn.as<float>(), km->counts.as<float>(), km->K, km->threshold(),
-                                   (float)km->reinit_r, km->caux.as<CentersAux>(), e1c, e1r, e2, dlab, und_list, &ctl->und_count, ctl,
-                                   (Top2Rec *)nullptr, cout);
-            }
-            // (3 workgroups of 4 waves per CU: the kernel is bound by the L2 -> L1 path -- 1, 2, 3, 4, 6 per CU all measure the same)
-            hipLaunchKernelGGL(k_assign_cand, dim3((unsigned)(3 * km->num_cus)), dim3(256), 0, st, static_cast<const float *>(dx),
-                               fd, fc, km->cn.as<float>(), km->counts.as<float>(), km->threshold(),
-                               (float)km->reinit_r, ctl, crow, cpair, pair_cap, dlab);
-        }
-        // full exact sweep of the rows on the f32 list (more than CAND_MAX candidates, pool overflow, K > 256); also the
+        // emission pass: the filter's main loop once more over the undecided rows only (a fixed grid strides over the tiles of the
+        // list), the epilogue emits each row's candidate centres; then the exact canonical chains of those (row, centre) pairs
+        if (p.emit_pass) filter_launch(ek, p.egrid, p.eblock, p.esmem, und_list, &ctl->und_count, (Top2Rec *)nullptr);
+        if (p.und_list)
+            hipLaunchKernelGGL(k_assign_cand, dim3((unsigned)p.cgrid), dim3(256), 0, st, fx, p.fd, fc, cn, counts, thr, r, ctl, crow, cpair,
+                               p.pair_cap, dlab);
+        // full exact sweep of the rows on the f32 list (more than CAND_MAX candidates, pool overflow, no candidate path); also the
         // sweep's last kernel: its last workgroup resets the control block
-        hipLaunchKernelGGL(k_assign_f32<false>, dim3((unsigned)rgrid), dim3(256), 0, st, static_cast<const float *>(dx), n,
-                           fd, fc, km->cn.as<float>(), km->counts.as<float>(), km->K,
-                           km->threshold(), (float)km->reinit_r, dlab, (float *)nullptr, km->wg_sum.as<double>(),
-                           f32_list, f32_count);
+        exact_launch(false, p.rgrid, p.fd, f32_list, &ctl->f32_count);
         km->n_filter_launches += 1;
         km->last_rows = (uint64_t)n;
-    } else if (fast)
-        hipLaunchKernelGGL(k_assign_f32<false>, dim3((unsigned)grid), dim3(256), 0, st, static_cast<const float *>(dx), n,
-                           km->d, km->centers.as<float>(), km->cn.as<float>(), km->counts.as<float>(), km->K,
-                           km->threshold(), (float)km->reinit_r, dlab, (float *)nullptr, km->wg_sum.as<double>(),
-                           (const int *)nullptr, (const unsigned *)nullptr);
-    else
-        hipLaunchKernelGGL(k_assign_f32<true>, dim3((unsigned)grid), dim3(256), 0, st, static_cast<const float *>(dx), n,
-                           km->d, km->centers.as<float>(), km->cn.as<float>(), km->counts.as<float>(), km->K,
-                           km->threshold(), (float)km->reinit_r, dlab, (float *)nullptr, km->wg_sum.as<double>(),
-                           (const int *)nullptr, (const unsigned *)nullptr);
+    } else
+        exact_launch(p.path == ASSIGN_EXACT_GUARDED, p.grid, km->d, (const int *)nullptr, (const unsigned *)nullptr);
     ACAV_HIP_TRY(hipGetLastError());
     km->n_assign_launches += 1;
+
+    // ---- copy back
     if (!lab_dev) ACAV_HIP_TRY(hipMemcpyAsync(labels, dlab, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, st));
     if (mean_dist) {
-        std::vector<double> part((size_t)grid);
-        ACAV_HIP_TRY(hipMemcpyAsync(part.data(), km->wg_sum.p, sizeof(double) * (size_t)grid, hipMemcpyDeviceToHost, st));
+        std::vector<double> part((size_t)p.grid);
+        ACAV_HIP_TRY(hipMemcpyAsync(part.data(), km->wg_sum.p, sizeof(double) * (size_t)p.grid, hipMemcpyDeviceToHost, st));
         ACAV_HIP_TRY(hipStreamSynchronize(st));
         double s = 0.0;
         for (double v : part) s += v;
         *mean_dist = (float)(s / (double)n);
-    } else if (!lab_dev || dx != x) {
+    } else if (!lab_dev || fx != x) {  // staged labels or rows (a padded copy included): the call returns when they are free
         ACAV_HIP_TRY(hipStreamSynchronize(st));
     }
     return ACAV_OK;

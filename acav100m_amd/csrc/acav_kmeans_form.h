@@ -1,7 +1,9 @@
-// Which persistent kernel an epoch of acav_kmeans_train runs on, how many workgroups that takes and how much LDS each
-// gets -- as ONE pure function of the shape, the device's limits and the experiment switches.  Plain C++: no HIP type, no
-// getenv, no handle; acav_kmeans.hip fills the three structs and turns the TrainForm into a launch,
-// acav_kmeans_train_form() exposes the choice to a machine without a GPU (tests/test_train_form.py).
+// The kernel choices of the k-means path, each ONE pure function of the shape, the device's limits and the experiment switches.
+// Plain C++: no HIP type, no getenv, no handle.  train_pick_form() below, assign_pick_plan() at the end of the file.
+//
+// Which persistent kernel an epoch of acav_kmeans_train runs on, how many workgroups that takes and how much LDS each gets:
+// acav_kmeans.hip fills the three structs and turns the TrainForm into a launch, acav_kmeans_train_form() exposes the choice to
+// a machine without a GPU (tests/test_train_form.py).
 //
 //   d <= 1024   K <= 256 and the grid fits          narrow   8 centres x 8 rows per workgroup (k_train_persistent)
 //               else, in this order                 wide     NCP x 8 centres x 8 rows, two row buffers: the smallest NCP of 2, 4, 8
@@ -136,4 +138,162 @@ inline TrainForm train_pick_form(const TrainShape &s, const TrainLimits &l, cons
         gx * gy * 2 <= l.occ_split * l.cus && gx * gy * 2 <= (l.has_budget ? l.room : l.occ_split * l.cus))
         f.kind = TRAIN_SPLIT, f.gx = gx, f.gy = gy, f.gz = 2, f.smem = (int)TS_SMEM;
     return f;
+}
+
+// ================================================================================================ the assign sweep
+// Which kernels one sweep of acav_kmeans_assign launches, on which grids and with how much LDS.  acav_kmeans_assign.hip fills the
+// three structs (assign_switches() reads the environment), maps the plan to an instantiation of k_assign_f16_rw
+// (assign_filter_kernel) and launches; acav_kmeans_assign_plan() exposes the plan to a machine without a GPU
+// (tests/test_assign_plan.py).
+//
+//   the mean distance is wanted, K < 2, n < 128 or n >= 2^31 - 1,      exact    k_assign_f32 over all rows: the fast form when d % 32 = 0
+//     ACAV_ASSIGN_EXACT_ONLY=1, d % 32 = 0 but unaligned rows,                  and the rows are 16-byte aligned, else the guarded one
+//     d % 32 != 0 with ACAV_FILTER_PAD=0
+//   otherwise                                                          filter   k_assign_f16_rw at fd = d rounded up to 32 columns (zero-
+//                                                                               padded copies when d % 32 != 0), then the exact re-check
+//     K <= 256                                4 waves, 128-row tiles, schedule 0, centre ring of 2; the epilogue emits the candidates
+//                                             of an undecided row in place (EMIT = 2) -> k_assign_cand -> k_assign_f32 over the rest
+//     K > 256, fd <= 256                      4 waves, one workgroup per (tile, group) pair (GS) -> k_assign_merge -> emission pass
+//     K > 256, fd > 256                       8 waves, 256-row tiles, pairs (GS)               (EMIT = 1) -> k_assign_cand -> k_assign_f32
+//     ACAV_ASSIGN_EMIT=1 at K <= 256          the lean filter (EMIT = 0) -> emission pass -> k_assign_cand -> k_assign_f32
+//     no candidate path (below)               the lean filter (-> k_assign_merge) -> k_assign_f32 over every undecided row
+//
+// What the arms of the old nested choice only implied:
+//   * the centre ring depth follows the tile: dcr = 3 with 8 waves (one workgroup per CU), 2 with 4 (two per CU);
+//   * 8 waves always run schedule 2 (DMA pieces between the MFMAs), 4-wave pairs always schedule 0: ACAV_FILTER_SCHED only
+//     reaches the 4-wave tile of K <= 256;
+//   * scaled rows (xs) are always read non-temporally: xs => nt, whatever ACAV_FILTER_NT says;
+//   * candidates are emitted in place only by ONE group on the 4-wave tile with schedule 0.  The (tile, group) pairs emit through
+//     the emission pass.  Every other form has NO candidate path -- ACAV_FILTER_NW=8 or ACAV_FILTER_SCHED=2 at K <= 256,
+//     ACAV_FILTER_GS=0 at K > 256, as well as ACAV_ASSIGN_EMIT=0, ACAV_ASSIGN_CAND=0 and n >= 2^27 (slots and pairs share one
+//     64-bit allocator word): its undecided rows all go to the f32 list and take the full exact sweep;
+//   * the emission pass always runs 128-row tiles (4 waves, no pairs, ring of 2, schedule 0), one workgroup per CU.
+constexpr int AS_ROWS = 64;   // rows per workgroup of the exact sweep: 2 MFMA row tiles
+constexpr int AS_BK = 32;     // feature columns per LDS stage (= the 32 canonical sumsq classes)
+constexpr int FB_ROWS = 128;  // rows per workgroup (4 MFMA row tiles)
+constexpr int FILTER_NW_DEFAULT = 4, FILTER_SCHED_DEFAULT = 0;  // K <= 256 defaults of k_assign_f16_rw
+constexpr int FD_BK = 32;
+constexpr int FD_DX = 3;  // row ring depth (2 stages = 32 KB in flight per workgroup, two workgroups per CU)
+constexpr int FD_DC = 2;  // centre ring depth (1 stage in flight: an L2 round trip is shorter than a stage)
+constexpr int FD_SLOT = 16384;  // bytes per ring slot: 128 rows x 32 fp32 == 256 centres x 32 bf16
+constexpr unsigned CAND_MAX = 16;  // candidates per row beyond which the row takes the full exact sweep
+
+struct AssignShape {
+    int d, K;
+    int64_t n;
+    bool aligned;      // the row pointer is 16-byte aligned
+    bool need_mean;    // the caller wants the mean distance: the filter's distances are approximate
+    bool rows_scaled;  // the filter's copy of the centres asks for scaled rows (k_centers_scale): the XS instantiations
+};
+struct AssignLimits { int cus; };
+struct AssignSwitches {        // the environment, read once by the caller (assign_switches() in acav_kmeans_assign.hip)
+    bool exact_only = false;   // ACAV_ASSIGN_EXACT_ONLY=1
+    bool pad = true;           // ACAV_FILTER_PAD=0: d % 32 != 0 takes the guarded exact sweep instead of padded copies
+    bool cand = true;          // ACAV_ASSIGN_CAND=0: every undecided row to the full exact sweep
+    int emit = 2;              // ACAV_ASSIGN_EMIT: 0 no emission at all, 1 lean filter + emission pass, else 2: in place
+    long pair_cap = 0;         // ACAV_CAND_PAIR_CAP: a smaller candidate-pair pool (tests: the overflow path); 0 < v < default counts
+    bool nt = true;            // ACAV_FILTER_NT=0: the default cache policy on the row DMA instead of the non-temporal one
+    bool gs = true;            // ACAV_FILTER_GS=0: K > 256 loops over the groups inside one workgroup
+    int nw = 0;                // ACAV_FILTER_NW=4|8: waves per workgroup; 0 = by shape
+    int sched = FILTER_SCHED_DEFAULT;  // ACAV_FILTER_SCHED=2, any other value 0
+};
+
+enum AssignPath { ASSIGN_EXACT_GUARDED = 0, ASSIGN_EXACT_FAST = 1, ASSIGN_FILTER = 2 };
+enum AssignError { ASSIGN_PLAN_OK = 0, ASSIGN_N_TOO_LARGE = 1 };  // a grid beyond 2^31 - 1 workgroups
+
+// the template arguments of one k_assign_f16_rw instantiation as decimal digits, e.g. <true, 8, true, 3, 2, 0, false> = 1813200
+constexpr int assign_kernel_id(bool nt, int nw, bool gs, int dcr, int sched, int emit, bool xs)
+{
+    return (((((nt * 10 + nw) * 10 + gs) * 10 + dcr) * 10 + sched) * 10 + emit) * 10 + xs;
+}
+
+struct AssignPlan {
+    int error = ASSIGN_PLAN_OK, path = ASSIGN_EXACT_GUARDED;
+    int64_t grid = 0;        // workgroups of the exact sweep over all rows (= partial sums of the mean distance)
+    // ---- the filter path; all zero on the exact ones
+    int fd = 0;              // the width the sweep runs at
+    bool ragged = false;     // fd != d: the sweep runs on zero-padded copies of the rows and the centres
+    int ngroups = 0;         // groups of 256 centres
+    bool gs = false;         // one workgroup per (tile, group) pair; k_assign_merge folds the groups' records
+    int nw = 0, sched = 0, dcr = 0;
+    bool nt = false, xs = false;
+    int emit = 0;            // EMIT of the filter launch: 2 = candidates in place, 0 = the lean kernel
+    bool emit_pass = false;  // the emission pass (EMIT = 1) runs over the undecided list
+    bool cand = false;       // the candidate buffers exist (and the K > 256 thresholds)
+    bool und_list = false;   // filter and merge write the undecided list and its counter, k_assign_cand settles it; else the f32 list
+    unsigned pair_cap = 0;
+    int64_t fgrid = 0, egrid = 0;  // workgroups, threads and dynamic LDS bytes of the filter launch (f) and the emission pass (e)
+    int fblock = 0, fsmem = 0, eblock = 0, esmem = 0;
+    int64_t rgrid = 0;       // k_assign_f32 over the f32 list: a fixed grid strides over however many row tiles the list holds
+    int cgrid = 0;           // k_assign_cand
+    int filter_kernel() const { return path == ASSIGN_FILTER ? assign_kernel_id(nt, nw, gs, dcr, sched, emit, xs) : -1; }
+    int emit_kernel() const { return emit_pass ? assign_kernel_id(nt, FB_ROWS / 32, false, FD_DC, 0, 1, xs) : -1; }
+};
+
+// bf16 filter + exact re-check (bit-identical labels, HBM-bound when the clusters are separated)?  Asked before the plan: the
+// filter's plan needs the centre copy prepared (rows_scaled comes from it), the exact sweeps must not pay for one
+inline bool assign_wants_filter(const AssignShape &s, const AssignSwitches &sw)
+{
+    const bool fast = s.d % AS_BK == 0 && s.aligned;
+    return !s.need_mean && (s.d % FD_BK != 0 ? sw.pad : fast) && s.K >= 2 && s.n >= FB_ROWS && !sw.exact_only && s.n < 0x7fffffff;
+}
+
+inline AssignPlan assign_pick_plan(const AssignShape &s, const AssignLimits &l, const AssignSwitches &sw)
+{
+    AssignPlan p;
+    p.grid = (s.n + AS_ROWS - 1) / AS_ROWS;
+    if (p.grid > 0x7fffffff) {
+        p.error = ASSIGN_N_TOO_LARGE;
+        return p;
+    }
+    if (!assign_wants_filter(s, sw)) {
+        p.path = s.d % AS_BK == 0 && s.aligned ? ASSIGN_EXACT_FAST : ASSIGN_EXACT_GUARDED;
+        return p;
+    }
+    p.path = ASSIGN_FILTER;
+    p.fd = (s.d + FD_BK - 1) / FD_BK * FD_BK;
+    p.ragged = p.fd != s.d;
+    // K > 256: one workgroup per (row tile, centre group) pair, the pairs of a tile side by side on one XCD, 256-row tiles (8
+    // waves), centre ring of 3, DMA pieces spread between the MFMAs -- rows from HBM once.
+    // (narrow views, fd <= 256: a pair is only 4-8 stages long and its ring fill and epilogue weigh as much as its stage loop
+    // -- two 128-row workgroups per CU hide them under each other: d = 128, K = 1024: 0.59 vs 0.72 ms per 1.25M rows)
+    p.ngroups = (s.K + 255) / 256;
+    p.gs = p.ngroups > 1 && sw.gs;
+    p.nw = sw.nw ? sw.nw : p.gs ? (p.fd <= 256 ? 4 : 8) : FILTER_NW_DEFAULT;
+    p.dcr = p.nw == 8 ? 3 : FD_DC;  // 3 only fits the one-workgroup-per-CU tile
+    p.sched = p.nw == 8 ? 2 : p.gs ? 0 : sw.sched;
+    p.xs = s.rows_scaled;
+    p.nt = sw.nt || p.xs;  // (nt rows are still found in L2 by the tile's other groups: PMC)
+    // candidate-restricted exact re-check.  n < 2^27: slots and pairs -- at most 16 per row -- share one 64-bit allocator word
+    p.cand = sw.cand && s.n < ((int64_t)1 << 27);
+    const uint64_t cap = 4 * (uint64_t)s.n < 65536 ? 65536 : 4 * (uint64_t)s.n > 0x7fffffff ? 0x7fffffff : 4 * (uint64_t)s.n;
+    p.pair_cap = (unsigned)(sw.pair_cap > 0 && (uint64_t)sw.pair_cap < cap ? (uint64_t)sw.pair_cap : cap);
+    // K <= 256: the filter emits in place (or, ACAV_ASSIGN_EMIT=1, lists for the emission pass); K > 256: the (tile, group) pairs
+    // cannot know a row's minimum over all groups -- k_assign_merge lists the undecided rows with their thresholds and the
+    // emission pass runs the filter's main loop once more over those rows, all groups in one workgroup
+    const bool in_place = p.ngroups == 1 && p.nw == 4 && p.sched == 0;
+    p.und_list = p.cand && sw.emit != 0 && (in_place || p.gs);
+    p.emit = p.und_list && in_place && sw.emit == 2 ? 2 : 0;
+    p.emit_pass = p.und_list && p.emit == 0;
+    const int64_t tile_rows = p.nw * 32, ntiles = (s.n + tile_rows - 1) / tile_rows;
+    p.fgrid = p.gs ? (ntiles + 7) / 8 * 8 * p.ngroups : ntiles;  // pairs: whole rounds of the 8 XCDs per group
+    if (p.fgrid > 0x7fffffff) {
+        p.error = ASSIGN_N_TOO_LARGE;
+        return p;
+    }
+    p.fblock = p.nw * 64;
+    p.fsmem = FD_DX * p.nw * 4096 + p.dcr * FD_SLOT;
+    if (p.emit_pass) {
+        // one workgroup per CU (rings + lists do not fit twice), 4 waves / 128 rows: the 8-wave emission instantiations kept
+        // 156-172 B of scratch and no run ever selected them outside A/B tests
+        constexpr int enw = FB_ROWS / 32;
+        const int64_t etiles = (s.n + FB_ROWS - 1) / FB_ROWS;
+        p.egrid = etiles < l.cus ? etiles : l.cus;
+        p.eblock = enw * 64;
+        p.esmem = FD_DX * enw * 4096 + FD_DC * FD_SLOT + enw * 32 * (4 + 2 * (int)CAND_MAX);  // rings + lists
+    }
+    p.rgrid = p.grid < 2 * (int64_t)l.cus ? p.grid : 2 * (int64_t)l.cus;
+    // (3 workgroups of 4 waves per CU: k_assign_cand is bound by the L2 -> L1 path -- 1, 2, 3, 4, 6 per CU all measure the same)
+    p.cgrid = p.und_list ? 3 * l.cus : 0;
+    return p;
 }

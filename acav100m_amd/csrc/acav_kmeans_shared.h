@@ -52,8 +52,6 @@ __device__ __forceinline__ float dist_epilogue(float dot, float xn, float cn, bo
     return t;
 }
 
-constexpr int AS_ROWS = 64;   // rows per workgroup of the exact sweep: 2 MFMA row tiles
-
 }  // namespace
 
 // =============================================================================== handle
@@ -68,13 +66,12 @@ struct acav_kmeans {
     DevBuf cb16, caux, cmu, recheck_list, backup, grec, split_rings;
     DevBuf cand_ctl, cand_rows, cand_pairs, cand_T;
     DevBuf cpad, xpad;  // zero-padded centres / rows of the assign filter when d % 32 != 0 (acav_kmeans_assign.hip)
-    unsigned ctl_pair_cap = 0;  // candidate-restricted re-check of the assign sweep (acav_kmeans_assign.hip)
     hipEvent_t ev_f0 = nullptr, ev_f1 = nullptr;  // around the last filter launch (acav_kmeans_filter_time)
     bool cb16_valid = false;  // the filter's half-precision copy of the centres matches `centers`
     bool filter_rows_scaled = false;  // ... and its sweeps multiply the rows by aux->sx before the conversion (XS instantiations)
     bool rg_attr_set = false; // dynamic-LDS attribute of the large-batch distance kernels set
     int64_t n_filter_launches = 0;
-    uint64_t last_recheck = 0, last_rows = 0;
+    uint64_t last_rows = 0;
     int64_t n_persistent_launches = 0, n_persistent_fallbacks = 0;
     int num_cus = 0;  // multiProcessorCount of the handle's device (queried on first use)
     int key_phase = 0;  // which half of `keys` the next step's distance kernel folds into

@@ -534,6 +534,87 @@ def test_filter_scaled_rows_every_instantiation(env, d, K, switch, scale, monkey
     assert np.array_equal(km.calc_best(xt)[0].cpu().numpy(), want)
 
 
+_INSTANTIATION_DATA = {}
+
+
+def _instantiation_data(O, d, K, n=1000):
+    """The overlapping mixture of test_filter_scaled_rows_every_instantiation at unit scale, and the oracle's labels: once per (d, K)."""
+    if (d, K) not in _INSTANTIATION_DATA:
+        rs = np.random.RandomState(5)
+        cen0 = rs.randn(K, d).astype(np.float32)
+        x = (cen0[rs.randint(0, K, n)] + rs.randn(n, d).astype(np.float32)).astype(np.float32)
+        centers = (rs.randn(K, d).astype(np.float32)[rs.randint(0, K, K)] + rs.randn(K, d).astype(np.float32)).astype(np.float32)
+        counts = np.full(K, 500, np.float32)
+        ref = O.KMeans(d, K, O.Rng(0), centers=centers)
+        ref.set_state(None, counts, 10 * K + int(counts.sum()))
+        _INSTANTIATION_DATA[d, K] = x, centers, counts, ref.calc_best(x)[0]
+    return _INSTANTIATION_DATA[d, K]
+
+
+# name -> d, K, switches, <NT, NW, GS, DCR, SCHED, EMIT, XS> of the filter launch and of the emission pass (None: no pass)
+_INSTANTIATIONS = {
+    # families no other test launches
+    "sched2_4_waves": (128, 200, {"ACAV_FILTER_SCHED": "2"}, 1402200, None),
+    "lean_no_emission_k200": (128, 200, {"ACAV_ASSIGN_EMIT": "0"}, 1402000, None),
+    "lean_no_emission_k300": (128, 300, {"ACAV_ASSIGN_EMIT": "0"}, 1412000, None),
+    "default_policy_8_wave_pairs": (128, 300, {"ACAV_FILTER_NT": "0", "ACAV_FILTER_NW": "8"}, 813200, 402010),
+    "default_policy_8_wave_tile": (128, 200, {"ACAV_FILTER_NT": "0", "ACAV_FILTER_NW": "8"}, 803200, None),
+    "default_policy_4_wave_pairs": (128, 300, {"ACAV_FILTER_NT": "0"}, 412000, 402010),
+    "default_policy_sched2": (128, 200, {"ACAV_FILTER_NT": "0", "ACAV_FILTER_SCHED": "2"}, 402200, None),
+    "default_policy_emission_pass": (128, 200, {"ACAV_FILTER_NT": "0", "ACAV_ASSIGN_EMIT": "1"}, 402000, 402010),
+    # one of every family other tests launch
+    "in_place": (128, 200, {}, 1402020, None),
+    "default_policy_in_place": (128, 200, {"ACAV_FILTER_NT": "0"}, 402020, None),
+    "emission_pass_k200": (128, 200, {"ACAV_ASSIGN_EMIT": "1"}, 1402000, 1402010),
+    "8_wave_tile": (128, 200, {"ACAV_FILTER_NW": "8"}, 1803200, None),
+    "8_wave_pairs": (128, 300, {"ACAV_FILTER_NW": "8"}, 1813200, 1402010),
+    "4_wave_pairs": (128, 300, {}, 1412000, 1402010),
+    "4_wave_pairs_d96": (96, 300, {}, 1412000, 1402010),
+}
+
+
+@pytest.mark.parametrize("case", list(_INSTANTIATIONS))
+def test_every_filter_instantiation_launches(env, case, monkeypatch):
+    """Every unscaled-row instantiation of k_assign_f16_rw on the smallest shapes at which it can still go wrong: n = 1000 (7 full
+    128-row tiles and a tail of 104, or 3 full 256-row tiles and a tail of 232), d = 128 (4 stages: one more than the deepest ring,
+    every ring wraps) and once d = 96, K = 200 (one group, partly filled) and K = 300 (two groups, the second partly filled); 8 waves
+    forced by ACAV_FILTER_NW=8.  acav_kmeans_assign_plan names the instantiation the sweep launches; the labels must equal the
+    oracle's and the exact sweep's, with some rows undecided so that the re-check behind the instantiation runs too.
+    Unit-scale data leaves the rows unscaled: k_centers_scale keeps sx = 1 while the largest raw centre element lies in
+    [2^-5, 2^6] (here about 6), so these are the XS = false instantiations; the scaled-row ones stay with
+    test_filter_scaled_rows_every_instantiation."""
+    import ctypes as C
+    torch, acav, O = env
+    from acav100m_amd.clustering import KMeans
+    d, K, switches, filter_id, emit_id = _INSTANTIATIONS[case]
+    for name in ("ACAV_ASSIGN_EXACT_ONLY", "ACAV_FILTER_PAD", "ACAV_ASSIGN_CAND", "ACAV_ASSIGN_EMIT", "ACAV_CAND_PAIR_CAP", "ACAV_FILTER_NT",
+                 "ACAV_FILTER_GS", "ACAV_FILTER_NW", "ACAV_FILTER_SCHED"):
+        monkeypatch.delenv(name, raising=False)
+    for name, value in switches.items():
+        monkeypatch.setenv(name, value)
+    x, centers, counts, want = _instantiation_data(O, d, K)
+    n = len(x)
+    plan = (C.c_int * 27)()
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    assert acav.load_library().acav_kmeans_assign_plan(d, K, n, 1, 0, 0, cus, plan) == 0
+    assert (plan[0], plan[1]) == (0, 2) and plan[17] == filter_id and plan[18] == (emit_id if emit_id else -1)
+    km = KMeans(None, d, K)
+    km.centers, km.counts, km.count = centers, counts, 10 * K + int(counts.sum())
+    km.to("cuda:0")
+    xt = torch.from_numpy(x).cuda()
+    for rep in range(2):
+        lab, _ = km.calc_best(xt, need_mean=False)
+        launches, rows, rechecked = km.filter_stats()
+        cand_rows, cand_pairs, full_rows = km.recheck_stats()
+        print(f"{case}: undecided {rechecked}/{n}: {cand_rows} rows by {cand_pairs} candidate pairs, {full_rows} by the full sweep")
+        assert launches == rep + 1, "the filter did not run"
+        assert rechecked >= 1, "no row undecided: the case exercises no re-check"
+        assert rechecked == cand_rows + full_rows
+        bad = int((lab.cpu().numpy() != want).sum())
+        assert bad == 0, f"{bad} of {n} labels differ from the oracle"
+    assert np.array_equal(km.calc_best(xt)[0].cpu().numpy(), want)
+
+
 @pytest.mark.parametrize("spread", [0.02, 0.006, 0.0004])
 def test_filter_underflow_unit_and_row_headroom(env, spread, monkeypatch):
     """The half-precision filter's bound charges 2^-25 per operand element below half's normal range when the device keeps half
@@ -628,8 +709,8 @@ def test_candidate_restricted_recheck(env, mode, monkeypatch):
 @pytest.mark.parametrize("switch", [("ACAV_FILTER_NT", "0"), ("ACAV_ASSIGN_EXACT_ONLY", "1"),
                                     ("ACAV_NO_PERSISTENT", "1")])
 def test_diagnostic_switches_keep_the_results(env, switch, monkeypatch):
-    """The A/B switches select other kernels, never other results: the round-1 wave layout of the filter, the default
-    cache policy on its row DMA, the exact sweep alone, and per-step launches instead of the persistent epoch kernel."""
+    """The A/B switches select other kernels, never other results: the default cache policy on the filter's row DMA, the
+    exact sweep alone, and per-step launches instead of the persistent epoch kernel."""
     torch, acav, O = env
     from acav100m_amd.clustering import KMeans
     monkeypatch.setenv(*switch)
