@@ -84,6 +84,7 @@ SIGNATURES = {
                            C.POINTER(i64), vp, vp, vp, vp, i64],
     "acav_mi_run_greedy_multi": [vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp],
     "acav_mi_run_exact": [vp, vp, i64, i32, i64, vp, vp, C.POINTER(i64), vp, vp, vp],
+    "acav_mi_run_exact_multi": [vp, i32, vp, vp, vp, vp, vp, vp, vp],
     "acav_mi_run_celf": [vp, vp, i64, i32, i64, f64, vp, vp, vp, C.POINTER(i64), i64, vp, vp, vp],
     "acav_mi_set_measure": [vp, i32],
     "acav_mi_set_average_method": [vp, i32],

@@ -12,6 +12,7 @@
 //        (k_mi_select), float64, formula in oracle/acav_oracle.c "canon".
 //   calc_ids top-k, update_cache, update_candidates (batch.py:143-171)  k_mi_select.
 // The whole loop is enqueued without host synchronisation: L shrinks deterministically.
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <type_traits>
@@ -753,8 +754,22 @@ __device__ __forceinline__ bool exact_better(double s, int p, double so, int po)
 // PAIR: the pair-counting scores (measures 4-6) in an instantiation of their own, so that the code of measures 0-3 is what
 // it was before they existed.  W (measure 0 only): the weighted pair mean sum_p(s_p w_p) / P with the handle's fp32 pair
 // weights pw (acav_mi_set_pair_weights), in an instantiation of its own for the same reason
-template <bool PAIR, bool W = false>
-__global__ __launch_bounds__(256) void k_mi_exact_iter(
+// One pick of one candidate list, the whole of it (scoring, reduction, commit), as the device function that both kernels
+// are made of.  G says which of the list's workgroups this one is: the launch's own grid for k_mi_exact_iter (ExactGridOwn:
+// the kernel compiles to what it was before the function existed), a slice of the launch's grid for k_mi_exact_iter_multi
+// (ExactGridSlice).  A chunk's picks therefore cannot depend on which of the two ran it.
+struct ExactGridOwn {
+    __device__ __forceinline__ unsigned blk() const { return blockIdx.x; }
+    __device__ __forceinline__ unsigned nblk() const { return gridDim.x; }
+};
+struct ExactGridSlice {
+    unsigned b, n;
+    __device__ __forceinline__ unsigned blk() const { return b; }
+    __device__ __forceinline__ unsigned nblk() const { return n; }
+};
+template <bool PAIR, bool W, class G>
+__device__ __forceinline__ void exact_iter(
+    const G grid,
     const int *__restrict__ asg, int D, int C, int P, const int *__restrict__ pairs, const int *__restrict__ A, int L,
     unsigned char *__restrict__ removed, int *__restrict__ Nc, int *__restrict__ ac, int *__restrict__ bc,
     double *__restrict__ SN, double *__restrict__ Sa, double *__restrict__ Sb, const double *__restrict__ phi,
@@ -787,7 +802,7 @@ __global__ __launch_bounds__(256) void k_mi_exact_iter(
     __shared__ int sP[4];
     __shared__ int sLast;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int w = blockIdx.x * 256 + tid;
+    const int w = grid.blk() * 256 + tid;
     const long long nc = sc->nc;
     double s = -INFINITY;
     int pos = 0x7fffffff;
@@ -810,17 +825,17 @@ __global__ __launch_bounds__(256) void k_mi_exact_iter(
     if (tid == 0) {
         for (int q = 1; q < 4; ++q)
             if (exact_better<PAIR>(s, pos, sS[q], sP[q])) s = sS[q], pos = sP[q];
-        blockbest[blockIdx.x].s = s;
-        blockbest[blockIdx.x].pos = pos;
+        blockbest[grid.blk()].s = s;
+        blockbest[grid.blk()].pos = pos;
         __threadfence();  // the result is visible device-wide before the ticket is taken
         const unsigned t = atomicAdd(ticket, 1u);
-        sLast = (t == gridDim.x - 1) ? 1 : 0;
+        sLast = (t == grid.nblk() - 1) ? 1 : 0;
     }
     __syncthreads();
     if (!sLast) return;  // uniform
     __threadfence();
     s = -INFINITY, pos = 0x7fffffff;
-    for (int q = tid; q < (int)gridDim.x; q += 256) {
+    for (int q = tid; q < (int)grid.nblk(); q += 256) {
         const double so = __hip_atomic_load(&blockbest[q].s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const int po = __hip_atomic_load(&blockbest[q].pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (exact_better<PAIR>(s, pos, so, po)) s = so, pos = po;
@@ -873,6 +888,58 @@ __global__ __launch_bounds__(256) void k_mi_exact_iter(
             ps[p] = st;
         }
     }
+}
+
+template <bool PAIR, bool W = false>
+__global__ __launch_bounds__(256) void k_mi_exact_iter(
+    const int *__restrict__ asg, int D, int C, int P, const int *__restrict__ pairs, const int *__restrict__ A, int L,
+    unsigned char *__restrict__ removed, int *__restrict__ Nc, int *__restrict__ ac, int *__restrict__ bc,
+    double *__restrict__ SN, double *__restrict__ Sa, double *__restrict__ Sb, const double *__restrict__ phi,
+    MiScalars *__restrict__ sc, ExactBest *__restrict__ blockbest, unsigned *__restrict__ ticket,
+    long long *__restrict__ S_out, double *__restrict__ G_out, const int *__restrict__ forced,
+    double *__restrict__ trace_scores, int *__restrict__ trace_argmax, int measure, const double *__restrict__ lnk,
+    const double *__restrict__ lf, int avg, PairStat *__restrict__ ps, const float *__restrict__ pw)
+{
+    exact_iter<PAIR, W>(ExactGridOwn(), asg, D, C, P, pairs, A, L, removed, Nc, ac, bc, SN, Sa, Sb, phi, sc,
+                        blockbest, ticket, S_out, G_out, forced, trace_scores, trace_argmax, measure, lnk, lf, avg, ps, pw);
+}
+
+// ------------------------------------------------------------------- exact greedy, several chunks in lockstep
+// acav_mi_run_exact_multi: ONE launch serves one pick of every chunk that still has picks to make.  A workgroup belongs to one
+// chunk: block_chunk[blockIdx.x] names its descriptor, and block0 of the descriptor makes it the (blockIdx.x - block0)-th of
+// the chunk's nblk workgroups.  Everything after that is exact_iter on the chunk's own pointers, blockbest slice and ticket:
+// nothing crosses chunks on the device.  The host orders the descriptors by their number of picks, descending, so the chunks
+// alive at pick `it` are a prefix and the grid of that launch is the prefix's block count -- a finished chunk has no
+// workgroup.  The descriptor and the table entry are read through uniform addresses (scalar loads); the per-candidate path
+// is the single-chunk kernel's.  No forced positions and no traces here.
+struct ExactChunk {
+    const int *asg;
+    const int *pairs;
+    const int *A;
+    unsigned char *removed;
+    int *Nc, *ac, *bc;
+    double *SN, *Sa, *Sb;
+    const double *phi;
+    MiScalars *sc;
+    ExactBest *blockbest;
+    unsigned *ticket;
+    long long *S_out;
+    double *G_out;
+    const double *lnk, *lf;
+    PairStat *ps;
+    const float *pw;
+    int D, C, P, L;
+    int block0, nblk;
+};
+
+template <bool PAIR, bool W = false>
+__global__ __launch_bounds__(256) void k_mi_exact_iter_multi(const ExactChunk *__restrict__ cd, const int *__restrict__ block_chunk,
+                                                             int it, int measure, int avg)
+{
+    const ExactChunk d = cd[block_chunk[blockIdx.x]];
+    exact_iter<PAIR, W>(ExactGridSlice{blockIdx.x - (unsigned)d.block0, (unsigned)d.nblk}, d.asg, d.D, d.C, d.P, d.pairs, d.A, d.L, d.removed, d.Nc, d.ac, d.bc,
+                        d.SN, d.Sa, d.Sb, d.phi, d.sc, d.blockbest, d.ticket, d.S_out + it, d.G_out + it, nullptr, nullptr,
+                        nullptr, measure, d.lnk, d.lf, avg, d.ps, d.pw);
 }
 
 // ------------------------------------------------------------------- CELF lazy greedy (acav_mi_run_celf)
@@ -2126,6 +2193,7 @@ struct acav_mi {
     DevBuf celf_val, celf_stamp, celf_bv, celf_bst, celf_bp, celf_state, celf_lk, celf_qout;  // CELF queue (acav_mi_run_celf)
     DevBuf celf_fresh, celf_ks, celf_ks2, celf_kv, celf_kv2, celf_i0, celf_i1, celf_i2, celf_d, celf_pm, celf_dn, celf_tmp;  // its dense pick
     DevBuf chunk_desc;                         // descriptor array of a multi-chunk run (lead handle)
+    DevBuf chunk_blocks;                       // workgroup -> descriptor table of acav_mi_run_exact_multi (lead handle)
     DevBuf lane_states, ring, polys;           // MT19937 lanes of the single-chunk greedy (MtStream)
     DevBuf lnk, lf;   // ln k and ln k! tables of the `ami` score (acav_mi_set_measure)
     int measure = 0;  // exact greedy: 0 = calc_MI, 1 = calc_AMI, 2 = calc_NMI, 3 = constant, 4 = FM, 5 = Rand, 6 = ARI
@@ -3046,12 +3114,13 @@ ACAV_EXPORT int acav_mi_set_pair_weights(acav_mi *mi, const float *weights, int 
 }
 
 // T_ab / T_a / T_b of the current tables into mi->pst, residues 0 (on the handle's stream), unless pst is still current: the
-// reference resets its residues only in add_samples, so consecutive exact-greedy calls carry them on
-static int pair_stats_init(acav_mi *mi)
+// reference resets its residues only in add_samples, so consecutive exact-greedy calls carry them on.  `on`: the stream to
+// order it on (default: the handle's own)
+static int pair_stats_init(acav_mi *mi, hipStream_t on = nullptr)
 {
     if (mi->pst_valid) return ACAV_OK;
     ACAV_TRY(mi->pst.ensure(sizeof(PairStat) * (size_t)mi->P));
-    hipLaunchKernelGGL(k_pair_stats_init, dim3(mi->P), dim3(256), 0, mi->ctx.stream, mi->C, mi->Nc.as<int>(), mi->ac.as<int>(),
+    hipLaunchKernelGGL(k_pair_stats_init, dim3(mi->P), dim3(256), 0, on ? on : mi->ctx.stream, mi->C, mi->Nc.as<int>(), mi->ac.as<int>(),
                        mi->bc.as<int>(), mi->pst.as<PairStat>());
     ACAV_HIP_TRY(hipGetLastError());
     mi->pst_valid = true;
@@ -3159,6 +3228,133 @@ ACAV_EXPORT int acav_mi_run_exact(acav_mi *mi, const int64_t *candidates, int64_
     ACAV_HIP_TRY(hipStreamSynchronize(st));
     if (trace_argmax)
         for (int64_t i = 0; i < iters; ++i) trace_argmax[i] = am[(size_t)i];
+    return ACAV_OK;
+}
+
+// acav_mi_run_exact for several chunks at once: one launch of k_mi_exact_iter_multi per pick serves every chunk that still has
+// picks to make.  Chunk c yields, bit for bit, what acav_mi_run_exact(mis[c], candidates[c], L[c], ns[c], subset[c], S_out[c],
+// GAIN_out[c], &n_selected[c], NULL, NULL, NULL) yields, and its handle is left as that call leaves it (tables, scalars, pair
+// sums).  Every argument of every chunk is checked before anything is touched.  The launches go on the first handle's stream;
+// what the other handles were doing on their own streams is over before the first one (as in run_greedy_tiled).  No forced
+// positions, no traces, no CELF: those stay with the single-chunk calls.
+constexpr int EXACT_MULTI_MAX = 64;
+ACAV_EXPORT int acav_mi_run_exact_multi(acav_mi **mis, int nchunks, const int64_t *const *candidates, const int64_t *L,
+                                        const int *ns, const int64_t *subset, int64_t *const *S_out, double *const *GAIN_out,
+                                        int64_t *n_selected)
+{
+    ACAV_REQUIRE(mis && candidates && L && ns && subset && S_out && GAIN_out && n_selected, ACAV_EINVAL, "NULL argument");
+    ACAV_REQUIRE(nchunks >= 1 && nchunks <= EXACT_MULTI_MAX, ACAV_EINVAL, "%d chunks: one call takes 1 to %d", nchunks,
+                 EXACT_MULTI_MAX);
+    acav_mi *lead = mis[0];
+    ACAV_REQUIRE(lead, ACAV_EINVAL, "chunk 0: NULL argument");
+    std::vector<int64_t> iters((size_t)nchunks);
+    int64_t total_blocks = 0;
+    for (int c = 0; c < nchunks; ++c) {
+        const acav_mi *mi = mis[c];
+        ACAV_REQUIRE(mi && candidates[c] && S_out[c] && GAIN_out[c], ACAV_EINVAL, "chunk %d: NULL argument", c);
+        ACAV_REQUIRE(L[c] > 0 && L[c] < 0x7fffffff && ns[c] >= 0, ACAV_EINVAL, "chunk %d: bad candidate count %lld", c,
+                     (long long)L[c]);
+        ACAV_REQUIRE(mi->ctx.device == lead->ctx.device, ACAV_EINVAL, "chunk %d lives on another device", c);
+        for (int e = 0; e < c; ++e) ACAV_REQUIRE(mis[e] != mi, ACAV_EINVAL, "chunks %d and %d share a handle", e, c);
+        ACAV_REQUIRE(mi->measure == lead->measure, ACAV_EINVAL, "chunks 0 and %d differ in their measure (%d, %d)", c,
+                     lead->measure, mi->measure);
+        ACAV_REQUIRE(mi->avg == lead->avg, ACAV_EINVAL, "chunks 0 and %d differ in their average method (%d, %d)", c, lead->avg,
+                     mi->avg);
+        ACAV_REQUIRE(mi->weighted == lead->weighted, ACAV_EINVAL, "chunks 0 and %d differ: one has pair weights, the other has none",
+                     c);
+        int64_t itc = subset[c] - 1 - ns[c];  // range(len(start_indices), subset_size - 1)   (mi.py:161)
+        itc = itc < 0 ? 0 : itc > L[c] ? L[c] : itc;
+        iters[(size_t)c] = itc;
+        if (itc == 0) continue;  // as the single-chunk call: nothing selected, nothing looked at
+        for (int64_t i = 0; i < L[c]; ++i)
+            ACAV_REQUIRE(candidates[c][i] >= 0 && candidates[c][i] < mi->V, ACAV_EINVAL,
+                         "chunk %d: candidate id %lld outside [0, %lld)", c, (long long)candidates[c][i], (long long)mi->V);
+        total_blocks += (L[c] + 255) / 256;
+    }
+    ACAV_REQUIRE(total_blocks < (1 << 23), ACAV_EINVAL, "%lld candidates in all: too many for one lockstep call",
+                 (long long)total_blocks * 256);
+    // the chunks with picks to make, by their number of picks, descending (chunk order among equals): those alive at pick `it` are a prefix
+    std::vector<int> order;
+    for (int c = 0; c < nchunks; ++c)
+        if (iters[(size_t)c] > 0) order.push_back(c);
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return iters[(size_t)x] > iters[(size_t)y]; });
+    const int nlive = (int)order.size();
+    ACAV_HIP_TRY(hipSetDevice(lead->ctx.device));
+    const int measure = lead->measure;
+    const bool pair = measure >= 4;
+    const bool wt = lead->weighted && measure == 0;  // the reference weights calc_MI only
+    // whatever a handle was doing on its own stream is over; fm / rand: its tables hold a sample (read, nothing written yet)
+    std::vector<MiScalars> sc0((size_t)nchunks);
+    for (int c = 0; c < nchunks; ++c) {
+        if (iters[(size_t)c] == 0) continue;
+        if (pair && measure != 6)
+            ACAV_HIP_TRY(hipMemcpyAsync(&sc0[(size_t)c], mis[c]->scalars.p, sizeof(MiScalars), hipMemcpyDeviceToHost, mis[c]->ctx.stream));
+        ACAV_HIP_TRY(hipStreamSynchronize(mis[c]->ctx.stream));
+    }
+    if (pair && measure != 6)
+        for (int c = 0; c < nchunks; ++c)
+            ACAV_REQUIRE(iters[(size_t)c] == 0 || sc0[(size_t)c].nc >= 1, ACAV_EINVAL, "chunk %d: fm / rand: the tables hold no sample -- "
+                         "add the start clips first (the reference's pair-count check fails on an empty start)", c);
+    for (int c = 0; c < nchunks; ++c) n_selected[c] = iters[(size_t)c];
+    if (nlive == 0) return ACAV_OK;
+    hipStream_t st = lead->ctx.stream;
+    std::vector<ExactChunk> desc((size_t)nlive);
+    std::vector<int> block_chunk((size_t)total_blocks);
+    std::vector<unsigned> grid_of((size_t)nlive);  // blocks of the first q + 1 descriptors
+    int block0 = 0;
+    for (int q = 0; q < nlive; ++q) {
+        const int c = order[(size_t)q];
+        acav_mi *mi = mis[c];
+        const int64_t itc = iters[(size_t)c];
+        const int nblk = (int)((L[c] + 255) / 256);
+        if (nchunks > 1) mi->lockstep_member = true;
+        ACAV_TRY(mi->A0.ensure(sizeof(int) * (size_t)L[c]));
+        ACAV_TRY(ids_to_device32(mi, candidates[c], L[c], mi->stage, mi->A0, st));
+        ACAV_TRY(mi->removed.ensure((size_t)L[c]));
+        ACAV_TRY(mi->blockbest.ensure(sizeof(ExactBest) * (size_t)nblk));
+        ACAV_TRY(mi->ticket.ensure(sizeof(unsigned)));
+        ACAV_TRY(mi->S.ensure(sizeof(long long) * (size_t)itc));
+        ACAV_TRY(mi->G.ensure(sizeof(double) * (size_t)itc));
+        ACAV_HIP_TRY(hipMemsetAsync(mi->removed.p, 0, (size_t)L[c], st));
+        ACAV_HIP_TRY(hipMemsetAsync(mi->ticket.p, 0, sizeof(unsigned), st));
+        if (pair) ACAV_TRY(pair_stats_init(mi, st));  // their sums start from the tables as they are (init_pair_stats)
+        else mi->pst_valid = false;                   // the commits below do not maintain pst
+        ExactChunk &d = desc[(size_t)q];
+        d.asg = mi->asg.as<int>(), d.pairs = mi->pairs.as<int>(), d.A = mi->A0.as<int>();
+        d.removed = mi->removed.as<unsigned char>();
+        d.Nc = mi->Nc.as<int>(), d.ac = mi->ac.as<int>(), d.bc = mi->bc.as<int>();
+        d.SN = mi->SN.as<double>(), d.Sa = mi->Sa.as<double>(), d.Sb = mi->Sb.as<double>();
+        d.phi = mi->phi.as<double>(), d.sc = mi->scalars.as<MiScalars>();
+        d.blockbest = mi->blockbest.as<ExactBest>(), d.ticket = mi->ticket.as<unsigned>();
+        d.S_out = mi->S.as<long long>(), d.G_out = mi->G.as<double>();
+        d.lnk = mi->lnk.as<double>(), d.lf = mi->lf.as<double>();
+        d.ps = mi->pst.as<PairStat>(), d.pw = wt ? mi_weights(mi) : nullptr;
+        d.D = mi->D, d.C = mi->C, d.P = mi->P, d.L = (int)L[c];
+        d.block0 = block0, d.nblk = nblk;
+        for (int b = 0; b < nblk; ++b) block_chunk[(size_t)(block0 + b)] = q;
+        block0 += nblk;
+        grid_of[(size_t)q] = (unsigned)block0;
+    }
+    ACAV_TRY(lead->chunk_desc.ensure(sizeof(ExactChunk) * (size_t)nlive));
+    ACAV_TRY(lead->chunk_blocks.ensure(sizeof(int) * block_chunk.size()));
+    ACAV_HIP_TRY(hipMemcpyAsync(lead->chunk_desc.p, desc.data(), sizeof(ExactChunk) * (size_t)nlive, hipMemcpyHostToDevice, st));
+    ACAV_HIP_TRY(hipMemcpyAsync(lead->chunk_blocks.p, block_chunk.data(), sizeof(int) * block_chunk.size(), hipMemcpyHostToDevice, st));
+    const auto kernel = pair ? k_mi_exact_iter_multi<true> : wt ? k_mi_exact_iter_multi<false, true> : k_mi_exact_iter_multi<false>;
+    const int64_t iters_max = iters[(size_t)order[0]];
+    int alive = nlive;
+    for (int64_t it = 0; it < iters_max; ++it) {
+        while (iters[(size_t)order[(size_t)(alive - 1)]] <= it) --alive;  // order[0] lasts until iters_max
+        hipLaunchKernelGGL(kernel, dim3(grid_of[(size_t)(alive - 1)]), dim3(256), 0, st, lead->chunk_desc.as<ExactChunk>(),
+                           lead->chunk_blocks.as<int>(), (int)it, measure, lead->avg);
+    }
+    ACAV_HIP_TRY(hipGetLastError());
+    for (int q = 0; q < nlive; ++q) {
+        const int c = order[(size_t)q];
+        const size_t itc = (size_t)iters[(size_t)c];
+        ACAV_HIP_TRY(hipMemcpyAsync(S_out[c], mis[c]->S.p, sizeof(long long) * itc, hipMemcpyDeviceToHost, st));
+        ACAV_HIP_TRY(hipMemcpyAsync(GAIN_out[c], mis[c]->G.p, sizeof(double) * itc, hipMemcpyDeviceToHost, st));
+    }
+    ACAV_HIP_TRY(hipStreamSynchronize(st));
     return ACAV_OK;
 }
 

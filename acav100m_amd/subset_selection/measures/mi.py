@@ -123,6 +123,64 @@ class EfficientMI(EfficientBatchMI):
             print("Time Consumed: {} seconds".format(elapsed))
         return (start + S, GAIN, [elapsed / max(n, 1)] * n, [0] * n)
 
+    # ------------------------------------------------------------ several chunks in lockstep
+    @staticmethod
+    def _check_lockstep(measures, subset_sizes, start_indices_list):
+        """what run_greedy_multi requires of its arguments; ValueError before any device call"""
+        n = len(measures)
+        if n == 0 or len(subset_sizes) != n or len(start_indices_list) != n:
+            raise ValueError("run_greedy_multi needs one subset size and one start list per measure, and at least one measure")
+        m0 = measures[0]
+        for i, m in enumerate(measures):
+            if type(m) is not type(m0):
+                raise ValueError("chunks run in lockstep must share their measure: chunk 0 is {}, chunk {} is {}"
+                                 .format(type(m0).__name__, i, type(m).__name__))
+            if m.average_method != m0.average_method:
+                raise ValueError("chunks run in lockstep must share their average_method: chunk 0 has {!r}, chunk {} has {!r}"
+                                 .format(m0.average_method, i, m.average_method))
+        if len({id(m) for m in measures}) != n:
+            raise ValueError("the same measure object appears twice: every chunk needs its own")
+
+    @staticmethod
+    def run_greedy_multi(measures, subset_sizes, start_indices_list, verbose=False):
+        """run_greedy for several independent exact-greedy measures (one per chunk) with ONE kernel launch per pick
+        (acav_mi_run_exact_multi).  Element i of the result is, bit for bit, what
+        measures[i].run_greedy(subset_sizes[i], start_indices_list[i]) returns (the timelapse holds equal shares of the
+        call's wall time), and every measure's candidate list shrinks by its picks.  All measures are of one class with one
+        average_method (ValueError otherwise, before any device call); at most 64 per call.  No CELF, no forced positions
+        and no traces: those stay with run_greedy."""
+        EfficientMI._check_lockstep(measures, subset_sizes, start_indices_list)
+        n = len(measures)
+        cands = [m.candidate_ids for m in measures]
+        starts = [list(s) for s in start_indices_list]
+        niters = [max(0, min(int(sub) - 1 - len(s), len(c))) for sub, s, c in zip(subset_sizes, starts, cands)]
+        S = [np.empty(it + 1, np.int64) for it in niters]
+        G = [np.empty(it + 1, np.float64) for it in niters]
+
+        def parr(ptrs):
+            return (C.c_void_p * n)(*[p.value if isinstance(p, C.c_void_p) else p for p in ptrs])
+
+        L = np.array([len(c) for c in cands], np.int64)
+        ns = np.array([len(s) for s in starts], np.int32)
+        sub = np.array([int(s) for s in subset_sizes], np.int64)
+        nsel = np.zeros(n, np.int64)
+        t0 = time.time()
+        _lib.check(_lib._lib.acav_mi_run_exact_multi(parr([m._h for m in measures]), n, parr([_lib.ptr(c) for c in cands]),
+                                                     _lib.ptr(L), _lib.ptr(ns), _lib.ptr(sub), parr([_lib.ptr(a) for a in S]),
+                                                     parr([_lib.ptr(a) for a in G]), _lib.ptr(nsel)))
+        elapsed = time.time() - t0
+        if verbose:
+            print("Time Consumed: {} seconds for {} chunks in lockstep".format(elapsed, n))
+        out = []
+        for i, m in enumerate(measures):
+            k = int(nsel[i])
+            picks = S[i][:k].tolist()
+            picked = set(picks)
+            if picked:  # the candidate list shrinks as in _run
+                m.candidate_ids = np.ascontiguousarray([c for c in cands[i].tolist() if c not in picked], np.int64)
+            out.append((starts[i] + picks, G[i][:k].tolist(), [elapsed / max(k, 1)] * k, [0] * k))
+        return out
+
 
 class EfficientMemMI(EfficientMI):
     """mi.py:284-412: the memory-lean formulation of the same greedy; identical here."""

@@ -58,6 +58,16 @@ class _PairCountingMeasure(EfficientMI):
                                   log_times=log_times, node_rank=node_rank, pid=pid, record_trace=record_trace,
                                   forced_pos=forced_pos, celf_ratio=celf_ratio)
 
+    @staticmethod
+    def run_greedy_multi(measures, subset_sizes, start_indices_list, verbose=False):
+        """run_greedy for several chunks in lockstep: every chunk's start clips join its tables first, as in run_greedy, then
+        EfficientMI.run_greedy_multi.  The arguments are checked before the first table changes."""
+        EfficientMI._check_lockstep(measures, subset_sizes, start_indices_list)
+        starts = [[int(i) for i in s] for s in start_indices_list]
+        for m, s in zip(measures, starts):
+            m.add_samples(s)
+        return EfficientMI.run_greedy_multi(measures, subset_sizes, starts, verbose=verbose)
+
 
 class FowlkesMallowsScore(_PairCountingMeasure):
     """efficient_pair.py:22-105 ('fm', 'efficient_fm'): the Fowlkes-Mallows index of the selection, mean over the pairs."""

@@ -15,6 +15,7 @@ import numpy as np
 
 from .. import shards as io
 from ..parallel import world
+from .measures import get_measure
 from .run_greedy import _prepare, run_greedy
 
 
@@ -80,6 +81,19 @@ def run_single(args):
     return out_path, counts
 
 
+def lockstep_supported(measure_name, celf_ratio=0):
+    """computation.concurrent_chunks > 1: can this configuration run its chunks in lockstep?  Returns None, or raises
+    ValueError with the reason.  Every measure of the registry can, except `contrastive` (it trains a model: there is no
+    greedy loop to share); a non-zero celf_ratio cannot yet (the lazy greedy has no lockstep form)."""
+    name = str(measure_name).lower()
+    if not hasattr(get_measure(name), 'run_greedy_multi'):
+        raise ValueError("computation.concurrent_chunks: the measure {!r} has no lockstep form; run its chunks one after "
+                         "another (concurrent_chunks=1)".format(measure_name))
+    if celf_ratio:
+        raise ValueError("computation.concurrent_chunks: celf_ratio={!r} cannot run in lockstep yet (no CELF there); use "
+                         "concurrent_chunks=1 or celf_ratio=0".format(celf_ratio))
+
+
 def run_chunks(args):
     """chunk.py:21-53 + run_chunks_node :115-131 for THIS process's rank (one process per GPU)."""
     args.parent_pid = str(args.parent_pid or os.environ.get('ACAV_PARENT_PID') or os.getpid())  # chunk.py:22
@@ -97,6 +111,7 @@ def run_chunks(args):
     chunk_args.node_rank = rank
     width = int(chunk_args.computation.concurrent_chunks or 1)
     if width > 1:
+        lockstep_supported(chunk_args.measure_name, chunk_args.get('celf_ratio', 0))  # before any shard is read
         return _run_chunks_lockstep(args, chunk_args, mine, rank, width)
     written = []
     # computation.load_async (chunk.py:119-120,197-226): the next chunk's shards are read and parsed by a host
@@ -191,13 +206,14 @@ def compare_measures(args):
 
 def _run_chunks_lockstep(args, chunk_args, mine, rank, width):
     """computation.concurrent_chunks = width > 1: `width` chunks at a time share ONE set of kernel launches per
-    greedy iteration (acav_mi_run_greedy_multi) -- the loop of a single chunk is a chain of small dependent kernels
-    and leaves most of the GPU idle.  The reference runs a process's chunks one after the other on one RNG
-    stream (chunk.py:115-131); chunks in flight together need a stream each: chunk number `num` draws from
-    Generator(computation.random_seed + 1 + num), whichever rank or group it lands in."""
+    greedy iteration (the measure class's run_greedy_multi: acav_mi_run_greedy_multi for batch_mi,
+    acav_mi_run_exact_multi for the exact-greedy and pair-counting measures) -- the loop of a single chunk is a chain of
+    small dependent kernels and leaves most of the GPU idle.  The reference runs a process's chunks one after the other on
+    one RNG stream (chunk.py:115-131); chunks in flight together need a stream each: chunk number `num` draws from
+    Generator(computation.random_seed + 1 + num), whichever rank or group it lands in.  (The exact measures draw nothing from
+    it: for them lockstep and sequential chunk mode select the same clips.)"""
     from ..rng import Generator
-    from .measures.batch import EfficientBatchMI
-    assert chunk_args.measure_name == 'batch_mi', "lockstep chunks are implemented for the batch_mi measure"
+    run_greedy_multi = get_measure(chunk_args.measure_name).run_greedy_multi
     from concurrent.futures import ThreadPoolExecutor
     base_seed = int(chunk_args.computation.random_seed or 0)
     written = []
@@ -231,8 +247,8 @@ def _run_chunks_lockstep(args, chunk_args, mine, rank, width):
         nxt = pool.submit(prepare_group, groups[gi + 1]) if gi + 1 < len(groups) else None
         live = [p for p in prepared if p is not None]
         print("running chunks {} in lockstep".format([num for num, _ in group]))
-        results = EfficientBatchMI.run_greedy_multi([p[0] for p in live], [p[2] for p in live], [p[1] for p in live],
-                                                    verbose=chunk_args.verbose) if live else []
+        results = run_greedy_multi([p[0] for p in live], [p[2] for p in live], [p[1] for p in live],
+                                   verbose=chunk_args.verbose) if live else []
         ri = 0
         for j, (num, chunk) in enumerate(group):
             i = g0 + j

@@ -1,0 +1,63 @@
+"""GPU: the chunked CLI run (`--chunk_size`) of the exact-greedy measures with computation.concurrent_chunks > 1.  The exact
+measures draw nothing from the per-chunk generators, so lockstep and sequential chunk mode are the same function: the two
+merged output.csv files must be byte-identical."""
+import json
+import os
+import random
+import types
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def workdir(tmp_path_factory):
+    """four assignment shards written with the product's own helpers, in the layout of test_gpu_cli's workdir
+    (root/clusters/shard-00000i.pkl + root/videos/shard-00000i.json): two chunks of two shards.  (test_gpu_cli's own
+    fixture is module-scoped: its clustering outputs cannot be seen from here.)"""
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from acav100m_amd import shards
+    root = str(tmp_path_factory.mktemp("acav_exact_lockstep_cli"))
+    rows, layers, nshards = 130, 2, 4
+    rs = np.random.RandomState(33)
+    comp = rs.randint(0, 6, size=nshards * rows)
+    os.makedirs(os.path.join(root, "videos"), exist_ok=True)
+    for s in range(nshards):
+        name = "shard-%06d" % s
+        fns = ["clip_%06d_%04d.mp4" % (s, r) for r in range(rows)]
+        table = types.SimpleNamespace(filename=fns, shard_size=[rows] * rows, shard_name=[name] * rows,
+                                      tags={("audio", "vggish"): ("VGGishExtractor", "audioset"),
+                                            ("video", "slowfast"): ("SlowFastExtractor", "kinetics")})
+        labels = {}
+        for kind, mk in (("audio", "vggish"), ("video", "slowfast")):
+            for layer in range(layers):
+                col = np.where(rs.rand(rows) < 0.6, comp[s * rows:(s + 1) * rows], rs.randint(0, 6, size=rows))
+                labels[(kind, mk, "layer_%d" % layer)] = col.astype(np.int64)
+        shards.dump_pickle(shards.assignment_rows(table, labels, range(rows)), os.path.join(root, "clusters", name + ".pkl"))
+        with open(os.path.join(root, "videos", name + ".json"), "w") as f:
+            json.dump([{"filename": fn, "id": "vid%09d" % (s * rows + r), "segment": [10, 20]} for r, fn in enumerate(fns)], f)
+    return root, os.path.join(root, "clusters", "shard-{000000..000003}.pkl")
+
+
+@pytest.mark.parametrize("measure", ["mem_mi", "ami", "arand"])
+def test_lockstep_chunks_equal_sequential_chunks(workdir, measure):
+    from acav100m_amd.subset_selection.cli import Cli
+    root, glob = workdir
+    assert os.path.isfile(os.path.join(root, "clusters", "shard-000003.pkl"))
+    outs = {}
+    for width in (2, 1):
+        out_csv = os.path.join(root, "{}_w{}".format(measure, width), "output.csv")
+        os.makedirs(os.path.dirname(out_csv), exist_ok=True)
+        random.seed(1)
+        Cli().run(shards_path=glob, meta_path=os.path.join(root, "videos"), out_path=out_csv, chunk_size=2,
+                  measure_name=measure, **{"computation.concurrent_chunks": width, "computation.random_seed": 7,
+                                           "subset.size": 80})
+        Cli().reduce_csvs(out_path=out_csv)
+        outs[width] = open(out_csv, "rb").read()
+    assert outs[2] == outs[1]
+    # 40 per chunk: the start clip + 38 picks each (range(len(start), subset_size - 1))
+    assert len(outs[2].splitlines()) == 2 * 39
