@@ -2009,6 +2009,60 @@ __device__ __forceinline__ const unsigned *chunk_draw_ptr(const TileChunk &c, in
     return r0 < c.head ? c.ring - (c.head - r0) : c.ring + (r0 - c.head) % c.ring_words;
 }
 
+// XCD-affine grids of k_fy_tile_multi and k_fy_resolve_multi.  The workgroup with linear id b lands on XCD b % 8 (observed, not
+// promised: the bucket shards rely on it too), the eight L2s are not coherent, and both kernels touch a table at random -- the
+// scattered src stores of the tile kernel, the g chain reads of the resolve kernel.  On the 3-D grid (x fastest) the workgroups of
+// one (chunk, iteration) ITEM are dealt over all eight XCDs: every L2 writes back its own partial lines of the item's src and
+// fetches the item's whole g.  On the 1-D grid below all workgroups of an item share b % 8, so one L2 merges the stores and
+// fetches the table once.  Item m = y + ny z goes to class m % 8 (per-class counts differ by at most one) and is the (m / 8)-th of
+// its class; within a class the items follow one another, nx workgroups each, so an XCD works on one item's tables at a time.
+// The grid is padded to 8 nx ceil(items / 8) workgroups; a padding workgroup has no work.  With fewer than 8 items whole XCDs
+// would idle: the 1-D grid then runs in the old x-fastest order.  Nothing crosses workgroups in the two kernels, so a wrong
+// placement guess costs speed only.  Plain C++ on both sides: acav_fy_block_map() exposes it to the tests without a device.
+constexpr int FY_XCDS = 8;
+struct FyGrid {
+    unsigned nx, ny, gz;  // the 3-D grid that the 1-D launch stands for; nx == 0: the launch IS that 3-D grid (ACAV_FY_XCD_AFFINE=0)
+};
+struct FyBlock {
+    int x, y, z;
+    bool work;
+};
+__host__ __device__ inline long long fy_affine_blocks(unsigned nx, unsigned ny, unsigned gz)
+{
+    const unsigned items = ny * gz;
+    return items < (unsigned)FY_XCDS ? (long long)nx * items : (long long)FY_XCDS * nx * ((items + FY_XCDS - 1) / FY_XCDS);
+}
+__host__ __device__ inline FyBlock fy_block_map(unsigned b, unsigned nx, unsigned ny, unsigned gz)
+{
+    const unsigned items = ny * gz;
+    unsigned x, m;
+    if (items < (unsigned)FY_XCDS) {
+        x = b % nx, m = b / nx;
+    } else {
+        const unsigned s = b / FY_XCDS;  // the class's s-th workgroup
+        x = s % nx, m = b % FY_XCDS + FY_XCDS * (s / nx);
+    }
+    if (m >= items) return {0, 0, 0, false};
+    return {(int)x, (int)(m % ny), (int)(m / ny), true};
+}
+// the workgroup's place in the 3-D grid, from either launch form
+__device__ __forceinline__ FyBlock fy_this_block(const FyGrid &gr)
+{
+    if (gr.nx == 0) return {(int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, true};
+    return fy_block_map(blockIdx.x, gr.nx, gr.ny, gr.gz);
+}
+// the launch grid of one of the two kernels: 1-D when `affine` and the 1-D grid fits a launch of `threads`-wide workgroups
+static dim3 fy_launch_grid(bool affine, unsigned nx, unsigned ny, unsigned gz, unsigned threads, FyGrid *gr)
+{
+    const long long nb = fy_affine_blocks(nx, ny, gz);
+    if (affine && nx > 0 && nb > 0 && nb <= 0x7fffffffll && nb * threads < (1ll << 32)) {
+        *gr = {nx, ny, gz};
+        return dim3((unsigned)nb);
+    }
+    *gr = {0u, ny, gz};
+    return dim3(nx, ny, gz);
+}
+
 template <bool STAGED, bool PACK>
 __global__ __launch_bounds__(FYA_THREADS) void k_fy_part_multi(const TileChunk *__restrict__ cd, int it0, int dl)
 {
@@ -2028,30 +2082,34 @@ __global__ __launch_bounds__(FYA_THREADS) void k_fy_part_multi(const TileChunk *
 }
 
 template <bool PACK>
-__global__ __launch_bounds__(FYT_THREADS) void k_fy_tile_multi(const TileChunk *__restrict__ cd, int it0, int dl)
+__global__ __launch_bounds__(FYT_THREADS) void k_fy_tile_multi(const TileChunk *__restrict__ cd, int it0, int dl, FyGrid gr)
 {
     ACAV_MI_EMPTY_RETURN
-    const TileChunk &c = cd[blockIdx.y];
-    const int z = (int)blockIdx.z, it = it0 + z;
-    if (it >= c.iters || (int)blockIdx.x >= c.NT) return;
+    const FyBlock blk = fy_this_block(gr);
+    if (!blk.work) return;
+    const TileChunk &c = cd[blk.y];
+    const int z = blk.z, it = it0 + z;
+    if (it >= c.iters || blk.x >= c.NT) return;
     const size_t bofs = (size_t)z * c.NT * FY_SHARDS * c.capg;
     fy_tile_body<PACK>(c.L0 - it * dl, c.ebound, c.capg, c.ecap, c.wcap,
                  PACK ? reinterpret_cast<int2 *>(reinterpret_cast<unsigned *>(c.bucket) + bofs) : c.bucket + bofs,
-                 c.gcount + (size_t)z * c.NT * FY_SHARDS, c.src[z], c.g[z], c.err, (int)blockIdx.x);
+                 c.gcount + (size_t)z * c.NT * FY_SHARDS, c.src[z], c.g[z], c.err, blk.x);
 }
 
 // perm[i] = the position (before the iteration) whose content output position i receives: the E-ref chains are walked
 // here, beside the content path -- the gather that waits for the previous selection is then one indexed copy
 template <bool WIDE>
-__global__ __launch_bounds__(256) void k_fy_resolve_multi(const TileChunk *__restrict__ cd, int it0, int dl, int nreq)
+__global__ __launch_bounds__(256) void k_fy_resolve_multi(const TileChunk *__restrict__ cd, int it0, int dl, int nreq, FyGrid gr)
 {
     ACAV_MI_EMPTY_RETURN
     // one element per thread: a wave waits for the longest of its chains, and four elements per thread (256 chains per
     // wave) made the kernel 1.5x slower
-    const TileChunk &c = cd[blockIdx.y];
-    const int z = (int)blockIdx.z, it = it0 + z;
+    const FyBlock blk = fy_this_block(gr);
+    if (!blk.work) return;
+    const TileChunk &c = cd[blk.y];
+    const int z = blk.z, it = it0 + z;
     const int L = c.L0 - it * dl;
-    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    const int i = (int)((unsigned)blk.x * 256 + threadIdx.x);
     if (it >= c.iters || i >= L) return;
     const unsigned s = c.src[z][i];
     int a = (int)(s & 0x7fffffffu);
@@ -2810,6 +2868,9 @@ static int run_greedy_tiled(acav_mi **mis, int nchunks, const int64_t *const *ca
     for (int c = 0; c < nchunks; ++c) lmax = L[c] > lmax ? L[c] : lmax;
     const char *vpack = getenv("ACAV_FY_PACK");  // =0: the 8-byte bucket entries (A/B)
     const bool pack = lmax <= FY_PACK_MAX && !(vpack && vpack[0] == '0');
+    // =0: the 3-D grids of the tile and resolve kernels, every item's workgroups dealt over all XCDs (A/B; see fy_block_map)
+    const char *vaff = getenv("ACAV_FY_XCD_AFFINE");
+    const bool xcd_affine = !(vaff && vaff[0] == '0');
     int pmax = 1, dmax = 1, ntmax = 1;
     bool weighted = false;  // some chunk has pair weights: the weighted selection for the whole launch
     size_t part_smem = 0, part_smem_staged = 0, tile_smem = 0;
@@ -2934,6 +2995,7 @@ static int run_greedy_tiled(acav_mi **mis, int nchunks, const int64_t *const *ca
         ACAV_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(gs_kernel),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)sel_smem));
     const auto t_loop0 = std::chrono::steady_clock::now();
+    long long groups_1d = 0, groups_3d = 0;  // launch form of the tile / resolve grids, per group (diagnostics: ACAV_MI_TIMING prints it)
     for (int64_t g0 = 0; g0 < iters_max; g0 += FY_GROUP) {
         const int64_t g1 = g0 + FY_GROUP < iters_max ? g0 + FY_GROUP : iters_max;
         const unsigned gz = (unsigned)(g1 - g0);
@@ -2956,10 +3018,12 @@ static int run_greedy_tiled(acav_mi **mis, int nchunks, const int64_t *const *ca
                            (int)g0, (int)dl);
         for (int c = 0; c < nchunks; ++c)
             if (g0 < iters[(size_t)c]) ACAV_TRY(streams[(size_t)c].release(r0[(size_t)c]));  // k_fy_part is the only reader of the draws
-        hipLaunchKernelGGL(tile_kernel, dim3((unsigned)ntmax, (unsigned)nchunks, gz), dim3(FYT_THREADS), tile_smem, sf, dcd, (int)g0,
-                           (int)dl);
-        hipLaunchKernelGGL(resolve_kernel, dim3((unsigned)((lt + 255) / 256), (unsigned)nchunks, gz), dim3(256), 0, sf, dcd, (int)g0,
-                           (int)dl, keep_unselected ? B - k : 0);
+        FyGrid gr_tile, gr_res;
+        const dim3 grid_tile = fy_launch_grid(xcd_affine, (unsigned)ntmax, (unsigned)nchunks, gz, FYT_THREADS, &gr_tile);
+        const dim3 grid_res = fy_launch_grid(xcd_affine, (unsigned)((lt + 255) / 256), (unsigned)nchunks, gz, 256, &gr_res);
+        ++(gr_tile.nx && gr_res.nx ? groups_1d : groups_3d);
+        hipLaunchKernelGGL(tile_kernel, grid_tile, dim3(FYT_THREADS), tile_smem, sf, dcd, (int)g0, (int)dl, gr_tile);
+        hipLaunchKernelGGL(resolve_kernel, grid_res, dim3(256), 0, sf, dcd, (int)g0, (int)dl, keep_unselected ? B - k : 0, gr_res);
         ACAV_HIP_TRY(hipEventRecord(lead->ev_tile[ge], sf));
         // ---- main stream: the group's gathers (each with the selection of the iteration before it), back to back
         ACAV_HIP_TRY(hipStreamWaitEvent(st, lead->ev_tile[ge], 0));
@@ -2980,10 +3044,11 @@ static int run_greedy_tiled(acav_mi **mis, int nchunks, const int64_t *const *ca
         ACAV_HIP_TRY(hipStreamSynchronize(st));
         const auto t_loop2 = std::chrono::steady_clock::now();
         fprintf(stderr, "[acav] greedy loop: %d chunk(s), %lld iterations, host enqueue %.2f us/iteration, enqueue + drain %.2f "
-                        "us/iteration (tiles %d, cap %d, lanes %d; streams replaced by the queue probe at create: %d)\n", nchunks, (long long)iters_max,
+                        "us/iteration (tiles %d, cap %d, lanes %d; tile / resolve grids: 1-D XCD-affine in %lld group(s), 3-D in %lld; streams replaced by the queue probe at create: %d)\n",
+                nchunks, (long long)iters_max,
                 std::chrono::duration<double, std::micro>(t_loop1 - t_loop0).count() / (double)(iters_max ? iters_max : 1),
                 std::chrono::duration<double, std::micro>(t_loop2 - t_loop0).count() / (double)(iters_max ? iters_max : 1),
-                plans[0].NT, plans[0].ecap, streams[0].W, mis[0]->queue_probe_replaced);
+                plans[0].NT, plans[0].ecap, streams[0].W, groups_1d, groups_3d, mis[0]->queue_probe_replaced);
     }
     const auto t_tail0 = clk::now();
     for (int c = 0; c < nchunks; ++c) {
@@ -3006,6 +3071,26 @@ static int run_greedy_tiled(acav_mi **mis, int nchunks, const int64_t *const *ca
     if (timing)
         fprintf(stderr, "[acav]   set-up %.1f ms (per-chunk work %.1f: add_samples %.1f, ids %.1f, tables %.1f, generator plan %.1f; then the sync), "
                         "read-back + generator states %.1f ms\n", t_setup, t_chunks, t_add, t_ids, t_fy, t_mt, ms_since(t_tail0));
+    return ACAV_OK;
+}
+
+// The 1-D grid of k_fy_tile_multi / k_fy_resolve_multi for a 3-D grid of nx x ny x gz workgroups, without a device (fy_block_map)
+ACAV_EXPORT int acav_fy_block_grid(int nx, int ny, int gz, int64_t *blocks)
+{
+    ACAV_REQUIRE(blocks, ACAV_EINVAL, "NULL argument");
+    ACAV_REQUIRE(nx > 0 && ny > 0 && gz > 0 && (int64_t)ny * gz < (1 << 24), ACAV_EINVAL, "bad grid %d x %d x %d", nx, ny, gz);
+    *blocks = fy_affine_blocks((unsigned)nx, (unsigned)ny, (unsigned)gz);
+    return ACAV_OK;
+}
+
+ACAV_EXPORT int acav_fy_block_map(int64_t b, int nx, int ny, int gz, int *x, int *y, int *z)
+{
+    ACAV_REQUIRE(x && y && z, ACAV_EINVAL, "NULL argument");
+    ACAV_REQUIRE(nx > 0 && ny > 0 && gz > 0 && (int64_t)ny * gz < (1 << 24), ACAV_EINVAL, "bad grid %d x %d x %d", nx, ny, gz);
+    const long long nb = fy_affine_blocks((unsigned)nx, (unsigned)ny, (unsigned)gz);
+    ACAV_REQUIRE(nb <= 0x7fffffffll && b >= 0 && b < nb, ACAV_EINVAL, "workgroup %lld outside the grid of %lld", (long long)b, nb);
+    const FyBlock q = fy_block_map((unsigned)b, (unsigned)nx, (unsigned)ny, (unsigned)gz);
+    *x = q.work ? q.x : -1, *y = q.work ? q.y : -1, *z = q.work ? q.z : -1;
     return ACAV_OK;
 }
 

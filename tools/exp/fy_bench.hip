@@ -68,8 +68,14 @@ int main(int argc, char **argv)
     printf("part: %s, %zu B of LDS; bucket entries of %d bytes\n", staged ? "staged" : "direct", part_smem, pack ? 4 : 8);
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     auto part = [&]() { hipLaunchKernelGGL(staged ? part_st : part_di, dim3((L + FYA_CH - 1) / FYA_CH, 1, G), dim3(FYA_THREADS), part_smem, 0, dcd, 0, dl); };
-    auto tile = [&]() { hipLaunchKernelGGL(tile_k, dim3(fp.NT, 1, G), dim3(FYT_THREADS), fp.tile_smem(), 0, dcd, 0, dl); };
-    auto resolve = [&]() { hipLaunchKernelGGL(k_fy_resolve_multi, dim3((L + 255) / 256, 1, G), dim3(256), 0, 0, dcd, 0, dl, B - k); };
+    // the product's grids of the tile and resolve kernels (fy_launch_grid) under the product's switch: ACAV_FY_XCD_AFFINE=0 = 3-D
+    const bool affine = !(getenv("ACAV_FY_XCD_AFFINE") && getenv("ACAV_FY_XCD_AFFINE")[0] == '0');
+    FyGrid gr_tile, gr_res;
+    const dim3 grid_tile = fy_launch_grid(affine, (unsigned)fp.NT, 1u, (unsigned)G, FYT_THREADS, &gr_tile);
+    const dim3 grid_res = fy_launch_grid(affine, (unsigned)((L + 255) / 256), 1u, (unsigned)G, 256, &gr_res);
+    printf("tile / resolve grids: %s (%u / %u workgroups in x)\n", gr_tile.nx ? "1-D, one XCD per iteration" : "3-D", grid_tile.x, grid_res.x);
+    auto tile = [&]() { hipLaunchKernelGGL(tile_k, grid_tile, dim3(FYT_THREADS), fp.tile_smem(), 0, dcd, 0, dl, gr_tile); };
+    auto resolve = [&]() { hipLaunchKernelGGL(k_fy_resolve_multi<false>, grid_res, dim3(256), 0, 0, dcd, 0, dl, B - k, gr_res); };
     auto timeit = [&](const char *name, auto fn, double base_us) {
         for (int i = 0; i < 3; ++i) fn();
         CK(hipDeviceSynchronize());
@@ -104,10 +110,10 @@ int main(int argc, char **argv)
     const int sel_m = sel_mode(B, P, k);
     const size_t sel_smem = sel_layout(B, P, D, k, sel_m).total;
     int itg = 0;
-    auto g_sc = [&]() { hipLaunchKernelGGL(k_fy_gather_select_multi, dim3((L + 256 * GS_EPT - 1) / (256 * GS_EPT) + 1, 1), dim3(256), sel_smem, 0, dcd, itg, dl, B, k, sel_m, 1); itg = (itg + 1) % G; };
+    auto g_sc = [&]() { hipLaunchKernelGGL((k_fy_gather_select_multi<false, false>), dim3((L + 256 * GS_EPT - 1) / (256 * GS_EPT) + 1, 1), dim3(256), sel_smem, 0, dcd, itg, dl, B, k, sel_m, 1); itg = (itg + 1) % G; };
     timeit("G x gather+select", [&]() { for (int i = 0; i < G; ++i) g_sc(); }, 0);
     {   // iteration 0 only: no selection in workgroup 0 -- the gather alone
-        auto g0only = [&]() { hipLaunchKernelGGL(k_fy_gather_select_multi, dim3((L + 256 * GS_EPT - 1) / (256 * GS_EPT) + 1, 1), dim3(256), sel_smem, 0, dcd, 0, dl, B, k, sel_m, 1); };
+        auto g0only = [&]() { hipLaunchKernelGGL((k_fy_gather_select_multi<false, false>), dim3((L + 256 * GS_EPT - 1) / (256 * GS_EPT) + 1, 1), dim3(256), sel_smem, 0, dcd, 0, dl, B, k, sel_m, 1); };
         timeit("G x gather (launch 0: no selection)", [&]() { for (int i = 0; i < G; ++i) g0only(); }, 0);
     }
     {   // the same with ONE perm buffer for every iteration (stays in cache) -- how much of the gather is the first touch of perm?
@@ -134,13 +140,13 @@ int main(int argc, char **argv)
         CK(hipStreamCreateWithPriority(&sb, hipStreamNonBlocking, pri ? hi : 0));
         auto side = [&](hipStream_t st) {
             hipLaunchKernelGGL(staged ? part_st : part_di, dim3((L + FYA_CH - 1) / FYA_CH, 1, G), dim3(FYA_THREADS), part_smem, st, dcd, 8, dl);
-            hipLaunchKernelGGL(tile_k, dim3(fp.NT, 1, G), dim3(FYT_THREADS), fp.tile_smem(), st, dcd, 8, dl);
-            hipLaunchKernelGGL(k_fy_resolve_multi, dim3((L + 255) / 256, 1, G), dim3(256), 0, st, dcd, 8, dl, B - k);
+            hipLaunchKernelGGL(tile_k, grid_tile, dim3(FYT_THREADS), fp.tile_smem(), st, dcd, 8, dl, gr_tile);
+            hipLaunchKernelGGL(k_fy_resolve_multi<false>, grid_res, dim3(256), 0, st, dcd, 8, dl, B - k, gr_res);
         };
         const bool nosel = getenv("FYB_NOSEL") != nullptr;  // every gather as launch 0: no selection beside it
         auto gath = [&](hipStream_t st) {
             for (int i = 0; i < G; ++i)
-                hipLaunchKernelGGL(k_fy_gather_select_multi, dim3((L + 256 * GS_EPT - 1) / (256 * GS_EPT) + 1, 1), dim3(256), sel_smem, st, dcd, nosel ? 0 : i, dl, B, k, sel_m, 1);
+                hipLaunchKernelGGL((k_fy_gather_select_multi<false, false>), dim3((L + 256 * GS_EPT - 1) / (256 * GS_EPT) + 1, 1), dim3(256), sel_smem, st, dcd, nosel ? 0 : i, dl, B, k, sel_m, 1);
         };
         auto wall = [&](const char *name, auto fn) {
             fn(); CK(hipDeviceSynchronize());
