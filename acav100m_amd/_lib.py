@@ -93,6 +93,7 @@ SIGNATURES = {
     "acav_mi_set_pair_weights": [vp, vp, i32],
     "acav_mi_get_pair_stats": [vp, vp, vp, vp, vp],
     "acav_mi_get_counts": [vp, vp, vp, vp, C.POINTER(i64)],
+    "acav_mt_stream_fill": [vp, i32, i64, i64, i32, vp],
     "acav_mi_sync": [vp],
     "acav_mi_timer_begin": [vp],
     "acav_mi_timer_end": [vp, C.POINTER(f32)],
@@ -112,7 +113,7 @@ _lib = None
 # entry points that are necessarily the first device call of a handle's life (everything else needs a handle):
 # calling one marks the HIP runtime as initialised for acav100m_amd.configure_runtime()
 _FIRST_DEVICE_CALLS = ("acav_device_count", "acav_device_info", "acav_kmeans_create", "acav_mi_create",
-                       "acav_contrastive_create", "acav_comm_init")
+                       "acav_contrastive_create", "acav_comm_init", "acav_mt_stream_fill")
 _device_touched = False
 
 

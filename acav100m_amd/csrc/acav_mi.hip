@@ -1448,8 +1448,21 @@ __device__ __forceinline__ unsigned mt_twist(unsigned y) { return (y >> 1) ^ ((y
 constexpr int MT_THREADS = 640;
 constexpr int MT_WIDE = 623;
 constexpr int MT_BACK = 1078;
-constexpr int MT_EPOCH = 24;                              // wide steps between two slides of the window
-constexpr int MT_WIN = MT_BACK + MT_WIDE * MT_EPOCH;      // 16030 words = 62.6 KB of LDS
+// The window is sized so that a generator (or jump) workgroup leaves room on its CU for one workgroup of k_fy_tile_multi at
+// the largest tile (wcap = ecap = 8192: 128 KB of dynamic LDS + its few static words): at 24 steps (62.6 KB) a CU that ran a
+// lane could take no tile workgroup for the ~1 ms the lane lasts.  LDS is handed out in granules of 1280 bytes on gfx950.
+#ifndef ACAV_MT_EPOCH
+#define ACAV_MT_EPOCH 9  // -DACAV_MT_EPOCH=24: the earlier window (A/B builds; the fit below is then not asserted)
+#define ACAV_MT_EPOCH_DEFAULT
+#endif
+constexpr int MT_EPOCH = ACAV_MT_EPOCH;                   // wide steps between two slides of the window
+constexpr int MT_WIN = MT_BACK + MT_WIDE * MT_EPOCH;      // 6685 words = 26.1 KB of LDS
+constexpr size_t lds_granules(size_t bytes) { return (bytes + 1279) / 1280 * 1280; }
+static_assert(MT_EPOCH >= 2, "the slide moves the last MT_BACK words to the front: the two ranges must be disjoint");
+#ifdef ACAV_MT_EPOCH_DEFAULT
+static_assert(lds_granules(sizeof(unsigned) * MT_WIN) + lds_granules(8192 * 16 + 1024 /* k_fy_tile_multi's static LDS, rounded up */) <= 160 * 1024,
+              "a generator workgroup and a k_fy_tile_multi workgroup at the largest tile must fit on one CU together");
+#endif
 __device__ __forceinline__ void mt_generate_body(const unsigned *__restrict__ mt_state, unsigned *__restrict__ out, long long n)
 {
     __shared__ unsigned X[MT_WIN];
@@ -1530,14 +1543,18 @@ __global__ __launch_bounds__(MT_THREADS) void k_mt_generate_lanes(unsigned *__re
 
 // states[dst0 + e] <- the window J words ahead of states[src0 + e] (e = blockIdx.x), J given by its polynomial
 // g(t) = t^J mod phi:  Y[k] = XOR over { i : g_i = 1 } of X[i + k], X = the stream continued from the source window.
-// The workgroup regenerates the 19937 + 623 words it needs in LDS (the same folded 623-wide recurrence as the
-// generator), then thread k accumulates Y[k] branch-free.  ~0.1 ms per jump; a lane block takes ~0.85 ms to generate.
-constexpr int MJ_WORDS = MT_BACK + MT_WIDE * 32;  // 21014 >= 624 + 19937
+// The workgroup regenerates the 19937 + 623 words it needs (the same folded 623-wide recurrence as the generator) through
+// the generator's own sliding window: after each stretch of up to MT_EPOCH wide steps thread k accumulates, branch-free,
+// the coefficients i whose X[i + k] are all generated (whole polynomial words only, so a stretch ends at a multiple of 32
+// and the next one starts inside what the slide keeps: 32 wdone >= m0 - 654 > m0 - MT_BACK); XOR commutes, so the order
+// is free.  The whole stream at once took 82 KB of LDS, which kept k_fy_part_multi's and k_fy_tile_multi's workgroups off
+// the CU.  ~0.24 ms per jump alone; a lane block takes ~0.88 ms to generate.
+constexpr unsigned MJ_NEED = 624 + 19937 - 1;  // stream words X[0 .. MJ_NEED) enter the sum: i <= 19936, k <= 623
 __global__ __launch_bounds__(MT_THREADS) void k_mt_jump(unsigned *__restrict__ states, int src0, int dst0,
                                                        const unsigned *__restrict__ poly)
 {
     ACAV_MI_EMPTY_RETURN
-    __shared__ unsigned X[MJ_WORDS];
+    __shared__ unsigned X[MT_WIN];
     const unsigned tid = threadIdx.x;
     const unsigned *src = states + (size_t)(src0 + blockIdx.x) * 625;
     unsigned *dst = states + (size_t)(dst0 + blockIdx.x) * 625;
@@ -1550,23 +1567,54 @@ __global__ __launch_bounds__(MT_THREADS) void k_mt_jump(unsigned *__restrict__ s
         }
         __syncthreads();
     }
-    for (unsigned m0 = MT_BACK; m0 < MJ_WORDS; m0 += MT_WIDE) {
-        if (tid < MT_WIDE) {
-            const unsigned *xw = X + (m0 + tid - MT_BACK);
-            const unsigned a = xw[0] ^ xw[227] ^ xw[454], b2 = xw[1] ^ xw[228] ^ xw[455];
-            X[m0 + tid] = xw[MT_BACK - 681] ^ mt_twist((a & 0x80000000u) | (b2 & 0x7fffffffu));
+    unsigned m0 = MT_BACK;  // stream index of the next word to generate
+    unsigned shift = 0;     // stream index of X[0]
+    unsigned wdone = 0;     // polynomial words accumulated so far
+    unsigned acc = 0u;
+    for (;;) {
+        for (int e = 0; e < MT_EPOCH && m0 < MJ_NEED; ++e, m0 += MT_WIDE) {  // fills the window at most: m0 - shift <= MT_WIN
+            if (tid < MT_WIDE) {
+                unsigned *xw = X + (m0 - shift + tid - MT_BACK);
+                const unsigned a = xw[0] ^ xw[227] ^ xw[454], b2 = xw[1] ^ xw[228] ^ xw[455];
+                xw[MT_BACK] = xw[MT_BACK - 681] ^ mt_twist((a & 0x80000000u) | (b2 & 0x7fffffffu));
+            }
+            __syncthreads();
         }
+        // coefficients i < 32 wend pair with words up to X[32 wend - 1 + 623], all below m0
+        const unsigned wfull = (m0 - 623u) >> 5, wend = wfull < 623u ? wfull : 623u;  // 19937 = 623 * 32 + 1 coefficients
+        // The polynomial words of the stretch come 32 at a time through one VGPR (lane l and lane l + 32 hold word w0 + l) and are
+        // made uniform by readlane: a scalar load per word, with a trip count that is no longer a constant, left its latency
+        // exposed in every pass.  Only lanes 0..31 are read: they are inside the guard in every wave (624 = 9 * 64 + 48).
+        if (tid < 624) {
+            auto poly_at = [&](unsigned w) { return poly[w < 624u ? w : 623u]; };
+            unsigned pnext = poly_at(wdone + (tid & 31u));
+            for (unsigned w0 = wdone; w0 < wend; w0 += 32u) {
+                const unsigned pv = pnext;
+                pnext = poly_at(w0 + 32u + (tid & 31u));  // the next 32 words, fetched under this pass
+                const unsigned cnt = wend - w0 < 32u ? wend - w0 : 32u;
+                for (unsigned j = 0; j < cnt; ++j) {
+                    const unsigned g = __builtin_amdgcn_readlane(pv, j);  // uniform
+                    const unsigned *xk = X + ((w0 + j) * 32u - shift + tid);
+#pragma unroll
+                    for (int b = 0; b < 32; ++b) acc ^= xk[b] & (0u - ((g >> b) & 1u));
+                }
+            }
+        }
+        wdone = wend;
+        if (m0 >= MJ_NEED) break;
+        __syncthreads();  // every read of this stretch is done: slide as the generator does
+        unsigned keep[2];
+        const unsigned from = m0 - shift - MT_BACK;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) keep[u] = tid + u * MT_THREADS < MT_BACK ? X[from + tid + u * MT_THREADS] : 0u;
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+            if (tid + u * MT_THREADS < MT_BACK) X[tid + u * MT_THREADS] = keep[u];
         __syncthreads();
+        shift = m0 - MT_BACK;
     }
     if (tid < 624) {
-        unsigned acc = 0u;
-        const unsigned *xk = X + tid;
-        for (int wi = 0; wi < 623; ++wi) {  // 19937 = 623 * 32 + 1 coefficients
-            const unsigned g = poly[wi];  // uniform
-#pragma unroll
-            for (int b = 0; b < 32; ++b) acc ^= xk[wi * 32 + b] & (0u - ((g >> b) & 1u));
-        }
-        acc ^= xk[623 * 32] & (0u - (poly[623] & 1u));
+        acc ^= X[623u * 32u - shift + tid] & (0u - (poly[623] & 1u));  // m0 >= MJ_NEED: wdone = 623, X[19936 + 623] is there
         dst[tid] = acc;
     }
     if (tid == 0) dst[624] = 624u;
@@ -2307,15 +2355,21 @@ struct MtStream {
     int64_t freed = 0;     // superblocks [0, freed) are no longer read by any iteration still to be enqueued
 
     // L: the longest list (one iteration reads at most L - 1 contiguous draws); span: the most draws one acquire() covers
+    // force_blk / force_W (acav_mt_stream_fill): the caller's lane block length (a multiple of 624) and lane count (a power of
+    // two) instead of the plan's own; with more than NSLOT superblocks it must keep W blk >= 2 span itself
     int plan(acav_mi *mi, hipStream_t consumer, const uint32_t *mtbuf, int idx, int64_t total_draws, int64_t L, int64_t span,
-             hipStream_t generator = nullptr)
+             hipStream_t generator = nullptr, int64_t force_blk = 0, int force_W = 0)
     {
         T = total_draws;
         p0 = idx;
         head = 624 - p0;
         lmax = L;
         const int64_t gen = T > head ? T - head : 0;  // words that must be generated past the host block
-        if (gen <= BLK_DEFAULT) {  // a single lane block, cut to size
+        if (force_blk > 0) {
+            blk = force_blk;
+            nblocks = (gen + blk - 1) / blk;
+            W = force_W;
+        } else if (gen <= BLK_DEFAULT) {  // a single lane block, cut to size
             W = 1;
             blk = 624 * ((gen + 623) / 624);
             nblocks = gen > 0 ? 1 : 0;
@@ -2382,6 +2436,13 @@ struct MtStream {
         const int64_t left = nblocks - s * W;
         const unsigned lanes = (unsigned)(left < W ? left : W);
         unsigned *out0 = ring + PAD + (int64_t)slot * S;
+#ifdef ACAV_MT_ABL_STALE  // timing-only ablation: the ring is filled once, later superblocks keep its stale words (any
+                          // 32-bit word is a valid draw); the events still go round, so the loop runs with no generator beside it
+        if (s >= NSLOT) {
+            ACAV_HIP_TRY(hipEventRecord(ev_mt[slot], smt));
+            return ACAV_OK;
+        }
+#endif
         hipLaunchKernelGGL(k_mt_generate_lanes, dim3(lanes), dim3(MT_THREADS), 0, smt, states, out0, (long long)blk,
                            (long long)(s == 0 ? head : 0));
         if (s + 1 < nsuper)  // every lane moves on to its next block, W blocks further
@@ -3146,6 +3207,45 @@ ACAV_EXPORT int acav_mi_run_greedy_multi(acav_mi **mis, int nchunks, const int64
 // mi.py:212-259), 2 = calc_NMI (EfficientNMI, mi.py:262-271), 3 = ConstantMeasure (mi.py:274-281), 4 / 5 / 6 = Fowlkes-Mallows /
 // Rand / adjusted Rand (correspondence_retrieval efficient_pair.py).  The adjusted and normalised scores read two more host-built
 // tables, ln k and ln k! for k <= V + 1.
+// The device draw stream on its own (tests): `n_words` raw MT19937 words (before tempering) that follow the host state
+// state[624] + idx (0 <= idx <= 624) -> out (host), generated exactly as the greedy loops generate theirs -- an MtStream of W
+// lanes with lane blocks of `blk` words, read back through acquire() / release() in spans of half a slot, so that the ring
+// wraps and every lane jumps when there are more than two superblocks.
+ACAV_EXPORT int acav_mt_stream_fill(const uint32_t *state, int idx, int64_t n_words, int64_t blk, int W, uint32_t *out)
+{
+    ACAV_REQUIRE(state && out && idx >= 0 && idx <= 624 && n_words > 0 && n_words < ((int64_t)1 << 40), ACAV_EINVAL, "bad argument");
+    ACAV_REQUIRE(blk >= 624 && blk % 624 == 0 && blk < ((int64_t)1 << 29) - 624, ACAV_EINVAL, "blk: a multiple of 624 below 2^29 - 624");
+    ACAV_REQUIRE(W >= 1 && W <= 32 && (W & (W - 1)) == 0, ACAV_EINVAL, "W: a power of two up to 32");
+    ACAV_REQUIRE(!is_device_ptr(out), ACAV_EINVAL, "out is a host array");
+    acav_mi *mi = new (std::nothrow) acav_mi;
+    ACAV_REQUIRE(mi, ACAV_ENOMEM, "out of host memory");
+    int rc = mi->ctx.init(0, nullptr);
+    if (rc != ACAV_OK) {
+        delete mi;
+        return rc;
+    }
+    auto body = [&]() -> int {
+        ACAV_TRY(mi_ensure_streams(mi));
+        hipStream_t st = mi->ctx.stream;
+        const int64_t span = (int64_t)W * blk / 2;
+        MtStream ms;
+        ACAV_TRY(ms.plan(mi, st, state, idx, n_words, span, span, nullptr, blk, W));
+        for (int64_t r0 = 0; r0 < n_words; r0 += span) {
+            const int64_t n = n_words - r0 < span ? n_words - r0 : span;
+            const unsigned *draws = nullptr;
+            ACAV_TRY(ms.acquire(r0, n, &draws));
+            ACAV_HIP_TRY(hipMemcpyAsync(out + r0, draws, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+            ACAV_TRY(ms.release(r0 + n));
+        }
+        ACAV_HIP_TRY(hipStreamSynchronize(st));
+        ACAV_HIP_TRY(hipStreamSynchronize(mi->st_mt));
+        return ACAV_OK;
+    };
+    rc = body();
+    const int rc2 = acav_mi_destroy(mi);
+    return rc != ACAV_OK ? rc : rc2;
+}
+
 ACAV_EXPORT int acav_mi_set_measure(acav_mi *mi, int measure)
 {
     ACAV_REQUIRE(mi, ACAV_EINVAL, "handle is NULL");

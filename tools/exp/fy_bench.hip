@@ -4,8 +4,47 @@
 #include <random>
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("err %s line %d\n", hipGetErrorString(e_), __LINE__); exit(1);} } while (0)
 
+// fy_bench mt: the generator's two kernels alone, at the product's lane block (624 * 4096 words) and its real jump polynomial
+static int mt_bench()
+{
+    const int W = 32, reps = 20;
+    const long long blk = MtStream::BLK_DEFAULT;
+    std::mt19937 rng(5);
+    std::vector<unsigned> hs((size_t)625 * W);
+    for (int w = 0; w < W; ++w) {
+        for (int i = 0; i < 624; ++i) hs[(size_t)w * 625 + i] = rng();
+        hs[(size_t)w * 625 + 624] = 624u;
+    }
+    const uint32_t *g = mt_jump_poly((int64_t)W * blk);
+    if (!g) { printf("no jump polynomial\n"); return 1; }
+    unsigned *states, *ring, *poly;
+    CK(hipMalloc(&states, 4 * hs.size())); CK(hipMemcpy(states, hs.data(), 4 * hs.size(), hipMemcpyHostToDevice));
+    CK(hipMalloc(&ring, 4 * (size_t)W * blk));
+    CK(hipMalloc(&poly, 4 * 624)); CK(hipMemcpy(poly, g, 4 * 624, hipMemcpyHostToDevice));
+    hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    printf("MT_EPOCH %d: window of %d words, %zu B of LDS in k_mt_generate_lanes and k_mt_jump\n", MT_EPOCH, MT_WIN, sizeof(unsigned) * MT_WIN);
+    auto timeit = [&](const char *name, auto fn) {
+        fn(); CK(hipDeviceSynchronize());
+        CK(hipEventRecord(e0, 0));
+        for (int i = 0; i < reps; ++i) fn();
+        CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1));
+        float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+        printf("%-44s %8.1f us per launch\n", name, ms * 1000.0 / reps);
+    };
+    for (int lanes : {1, W}) {
+        char name[64];
+        snprintf(name, sizeof(name), "k_mt_generate_lanes, %d lane(s) of %lld words", lanes, blk);
+        timeit(name, [&]() { hipLaunchKernelGGL(k_mt_generate_lanes, dim3(lanes), dim3(MT_THREADS), 0, 0, states, ring, blk, 0ll); });
+        snprintf(name, sizeof(name), "k_mt_jump, %d lane(s)", lanes);
+        timeit(name, [&]() { hipLaunchKernelGGL(k_mt_jump, dim3(lanes), dim3(MT_THREADS), 0, 0, states, 0, 0, poly); });
+    }
+    CK(hipGetLastError());
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc > 1 && !strcmp(argv[1], "mt")) return mt_bench();
     const int L = argc > 1 ? atoi(argv[1]) : 1000000;
     // FYB_SLOTS=R (footprint probe, timing only): the iterations of a group share R src / g buffers (iteration z uses slot z % R)
     // instead of one each -- same launches, grids and work, wrong permutations.  Every iteration of a launch then has the same L
