@@ -93,6 +93,8 @@ SIGNATURES = {
     "acav_mi_set_pair_weights": [vp, vp, i32],
     "acav_mi_get_pair_stats": [vp, vp, vp, vp, vp],
     "acav_mi_get_counts": [vp, vp, vp, vp, C.POINTER(i64)],
+    "acav_mi_score_subset": [vp, vp, i64, vp, i32, u32, vp, vp, vp],
+    "acav_score_compose": [vp, vp],
     "acav_mt_stream_fill": [vp, i32, i64, i64, i32, vp],
     "acav_mi_sync": [vp],
     "acav_mi_timer_begin": [vp],

@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "acav_common.h"
+#include "acav_score.h"
 #include <rocprim/rocprim.hpp>
 #include <vector>
 
@@ -2301,7 +2302,8 @@ struct acav_mi {
     DevBuf chunk_desc;                         // descriptor array of a multi-chunk run (lead handle)
     DevBuf chunk_blocks;                       // workgroup -> descriptor table of acav_mi_run_exact_multi (lead handle)
     DevBuf lane_states, ring, polys;           // MT19937 lanes of the single-chunk greedy (MtStream)
-    DevBuf lnk, lf;   // ln k and ln k! tables of the `ami` score (acav_mi_set_measure)
+    DevBuf lnk, lf;   // ln k and ln k! tables of the `ami` / `nmi` scores and of subset scoring (mi_ensure_log_tables)
+    int64_t log_kmax = -1;  // the tables hold k = 0 .. log_kmax
     int measure = 0;  // exact greedy: 0 = calc_MI, 1 = calc_AMI, 2 = calc_NMI, 3 = constant, 4 = FM, 5 = Rand, 6 = ARI
     int avg = 0;      // average_method of 1 and 2: 0 = arithmetic, 1 = max, 2 = min (acav_mi_set_average_method)
     DevBuf pst;       // PairStat [P] of the pair-counting scores (derived from the tables by k_pair_stats_init)
@@ -3246,23 +3248,31 @@ ACAV_EXPORT int acav_mt_stream_fill(const uint32_t *state, int idx, int64_t n_wo
     return rc != ACAV_OK ? rc : rc2;
 }
 
+// ln k and ln k! for k = 0 .. kmax on the device (built on the host: the scores read them, only exp runs on the device).  The
+// greedy scores need k <= V + 1; a scored id list with repeats can be longer than V.  Growing re-uploads the whole table.
+static int mi_ensure_log_tables(acav_mi *mi, int64_t kmax)
+{
+    if (mi->log_kmax >= kmax) return ACAV_OK;
+    ACAV_HIP_TRY(hipSetDevice(mi->ctx.device));
+    std::vector<double> lnk((size_t)kmax + 1), lf((size_t)kmax + 1);
+    lnk[0] = 0.0, lf[0] = 0.0;
+    for (int64_t k = 1; k <= kmax; ++k) lnk[(size_t)k] = log((double)k), lf[(size_t)k] = lgamma((double)k + 1.0);
+    ACAV_TRY(mi->lnk.ensure(sizeof(double) * lnk.size()));
+    ACAV_TRY(mi->lf.ensure(sizeof(double) * lf.size()));
+    ACAV_HIP_TRY(hipMemcpyAsync(mi->lnk.p, lnk.data(), sizeof(double) * lnk.size(), hipMemcpyHostToDevice, mi->ctx.stream));
+    ACAV_HIP_TRY(hipMemcpyAsync(mi->lf.p, lf.data(), sizeof(double) * lf.size(), hipMemcpyHostToDevice, mi->ctx.stream));
+    ACAV_HIP_TRY(hipStreamSynchronize(mi->ctx.stream));  // the vectors are locals
+    mi->log_kmax = kmax;
+    return ACAV_OK;
+}
+
 ACAV_EXPORT int acav_mi_set_measure(acav_mi *mi, int measure)
 {
     ACAV_REQUIRE(mi, ACAV_EINVAL, "handle is NULL");
     ACAV_REQUIRE(measure >= 0 && measure <= 6, ACAV_EINVAL, "unknown measure %d", measure);
     ACAV_REQUIRE(measure != 2 || (int64_t)mi->C <= mi->V + 1, ACAV_EINVAL, "nmi: ncentroids %d exceeds the ln k table (V + 1 = %lld)",
                  mi->C, (long long)(mi->V + 1));
-    if ((measure == 1 || measure == 2) && !mi->lnk.p) {
-        ACAV_HIP_TRY(hipSetDevice(mi->ctx.device));
-        std::vector<double> lnk((size_t)mi->V + 2), lf((size_t)mi->V + 2);
-        lnk[0] = 0.0, lf[0] = 0.0;
-        for (int64_t k = 1; k < mi->V + 2; ++k) lnk[(size_t)k] = log((double)k), lf[(size_t)k] = lgamma((double)k + 1.0);
-        ACAV_TRY(mi->lnk.ensure(sizeof(double) * lnk.size()));
-        ACAV_TRY(mi->lf.ensure(sizeof(double) * lf.size()));
-        ACAV_HIP_TRY(hipMemcpyAsync(mi->lnk.p, lnk.data(), sizeof(double) * lnk.size(), hipMemcpyHostToDevice, mi->ctx.stream));
-        ACAV_HIP_TRY(hipMemcpyAsync(mi->lf.p, lf.data(), sizeof(double) * lf.size(), hipMemcpyHostToDevice, mi->ctx.stream));
-        ACAV_HIP_TRY(hipStreamSynchronize(mi->ctx.stream));  // the vectors are locals
-    }
+    if (measure == 1 || measure == 2) ACAV_TRY(mi_ensure_log_tables(mi, mi->V + 1));
     mi->measure = measure;
     return ACAV_OK;
 }
@@ -3743,6 +3753,39 @@ ACAV_EXPORT int acav_mi_run_celf(acav_mi *mi, const int64_t *candidates, int64_t
     ACAV_HIP_TRY(hipMemcpyAsync(GAIN_out, mi->G.p, sizeof(double) * (size_t)iters, hipMemcpyDeviceToHost, st));
     ACAV_HIP_TRY(hipStreamSynchronize(st));
     return ACAV_OK;
+}
+
+// the scores of a GIVEN subset (include/acav_hip.h, "subset scoring"; kernels in acav_score.hip).  Of the handle it uses the labels,
+// the pair list, the log tables and the id staging buffers -- never the greedy tables, the measure or the weights.
+ACAV_EXPORT int acav_mi_score_subset(acav_mi *mi, const int64_t *ids, int64_t n, const int64_t *prefix, int nprefix,
+                                     unsigned measure_mask, double *scores, double *per_pair, acav_score_stats *stats)
+{
+    ACAV_REQUIRE(mi && ids && scores, ACAV_EINVAL, "NULL argument");
+    ACAV_REQUIRE(n >= 1 && n < 0x7fffffff, ACAV_EINVAL, "a subset of %lld ids cannot be scored (1 <= n < 2^31)", (long long)n);
+    ACAV_REQUIRE(measure_mask != 0 && (measure_mask >> ACAV_SCORE_COUNT) == 0, ACAV_EINVAL,
+                 "measure_mask 0x%x: at least one of the %d score bits, and no other", measure_mask, ACAV_SCORE_COUNT);
+    ACAV_REQUIRE(!is_device_ptr(ids), ACAV_EINVAL, "ids are a host array");
+    const int64_t whole[1] = {n};
+    if (!prefix) prefix = whole, nprefix = 1;
+    ACAV_REQUIRE(nprefix >= 1, ACAV_EINVAL, "nprefix = %d", nprefix);
+    for (int q = 0; q < nprefix; ++q)
+        ACAV_REQUIRE(prefix[q] > (q ? prefix[q - 1] : 0), ACAV_EINVAL, "prefix %d = %lld does not increase strictly from 1",
+                     q, (long long)prefix[q]);
+    ACAV_REQUIRE(prefix[nprefix - 1] == n, ACAV_EINVAL, "the last prefix is %lld, not n = %lld", (long long)prefix[nprefix - 1],
+                 (long long)n);
+    for (int64_t i = 0; i < n; ++i)
+        ACAV_REQUIRE(ids[i] >= 0 && ids[i] < mi->V, ACAV_EINVAL, "id %lld out of range [0,%lld)", (long long)ids[i], (long long)mi->V);
+    ACAV_HIP_TRY(hipSetDevice(mi->ctx.device));
+    ACAV_TRY(mi_ensure_log_tables(mi, std::max<int64_t>(mi->V + 1, n)));
+    ACAV_TRY(ids_to_device32(mi, ids, n, mi->stage, mi->ids32));
+    ScoreJob job;
+    job.device = mi->ctx.device, job.stream = mi->ctx.stream;
+    job.asg = mi->asg.as<int>(), job.pairs = mi->pairs.as<int>();
+    job.V = mi->V, job.D = mi->D, job.C = mi->C, job.P = mi->P;
+    job.ids = mi->ids32.as<int>(), job.n = n, job.prefix = prefix, job.nprefix = nprefix, job.mask = measure_mask;
+    job.lnk = mi->lnk.as<double>(), job.lf = mi->lf.as<double>();
+    job.scores = scores, job.per_pair = per_pair, job.stats = stats;
+    return score_subset_run(job);
 }
 
 ACAV_EXPORT int acav_mi_sync(acav_mi *mi)

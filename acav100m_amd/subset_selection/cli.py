@@ -1,5 +1,7 @@
 """`python cli.py run|reduce_csvs --shards_path=<brace glob .pkl> --meta_path=<dir> --out_path=<file|dir>`
--- the entry points of subset_selection/code/cli.py:17-100 + args.py:11-34 on the MI355X hot path."""
+-- the entry points of subset_selection/code/cli.py:17-100 + args.py:11-34 on the MI355X hot path.
+`python cli.py evaluate --shards_path=... --meta_path=... --selection_path=<output.csv>` scores a finished selection
+(evaluate.py)."""
 import datetime
 import os
 import sys
@@ -84,6 +86,11 @@ class Cli:
         out = compare_measures(prepare(**kwargs))
         print('done')
         return out
+
+    def evaluate(self, **kwargs):
+        """scores of a finished selection (--selection_path=<output.csv>), per clustering partition: evaluate.py"""
+        from .evaluate import evaluate
+        return evaluate(prepare(**kwargs))
 
     def merge_contrastive(self, **kwargs):
         from .run_contrastive import merge_contrastive

@@ -31,6 +31,44 @@ def _device_index(device):
         return 0
 
 
+# the scores of a given subset (score_subset), in the order of the library's ACAV_SCORE_* bits; the names are sklearn's
+# (sklearn.metrics.<name>_score).  They are scores of a finished selection, not selection measures: get_measure does not know them.
+SCORE_NAMES = ('mutual_info', 'normalized_mutual_info', 'adjusted_mutual_info', 'adjusted_rand', 'fowlkes_mallows', 'rand')
+# acav_score_stats of include/acav_hip.h
+SCORE_STATS_DTYPE = np.dtype([('mi', 'f8'), ('h_row', 'f8'), ('h_col', 'f8'), ('emi', 'f8'), ('tp', 'i8'), ('fp', 'i8'),
+                              ('fn', 'i8'), ('tn', 'i8'), ('n_rows', 'i8'), ('n_cols', 'i8'), ('n', 'i8')])
+
+
+def score_mask(measures=None):
+    """names -> (tuple of names in library order without repeats, bit mask); None = all six.  ValueError for an unknown name
+    or an empty list -- before anything touches a device."""
+    if measures is None:
+        measures = SCORE_NAMES
+    if isinstance(measures, str):
+        measures = [m for m in measures.split(',') if m]
+    names = [str(m).strip().lower() for m in measures]
+    unknown = [m for m in names if m not in SCORE_NAMES]
+    if unknown:
+        raise ValueError("unknown subset score(s) {}: choose from {}".format(unknown, list(SCORE_NAMES)))
+    if not names:
+        raise ValueError("no subset score asked for: choose from {}".format(list(SCORE_NAMES)))
+    mask = 0
+    for m in names:
+        mask |= 1 << SCORE_NAMES.index(m)
+    return tuple(m for m in SCORE_NAMES if m in names), mask
+
+
+def compose_scores(stats):
+    """one pair's raw values (a SCORE_STATS_DTYPE record or a dict of its fields) -> {name: score}: the host-only
+    acav_score_compose, usable without a GPU"""
+    rec = np.zeros(1, SCORE_STATS_DTYPE)
+    for f in SCORE_STATS_DTYPE.names:
+        rec[f] = stats[f]
+    out = np.empty(len(SCORE_NAMES), np.float64)
+    _lib.check(_lib.load_library().acav_score_compose(_lib.ptr(rec), _lib.ptr(out)))
+    return dict(zip(SCORE_NAMES, out.tolist()))
+
+
 class EfficientBatchMI:
     """ this implementation requires the users to use the same ncentroids for all clusterings """
     _takes_weights = True  # the MI score multiplies by the pair weights; the measures that override it ignore them
@@ -120,6 +158,45 @@ class EfficientBatchMI:
         ids = np.ascontiguousarray(ids, dtype=np.int64)
         out = np.empty(len(ids), np.float64)
         _lib.check(_lib._lib.acav_mi_score_batch(self._h, _lib.ptr(ids), len(ids), _lib.ptr(out)))
+        return out
+
+    def score_subset(self, ids, measures=None, prefixes=None, per_pair=False, return_stats=False):
+        """How well the clusterings agree on the clips `ids` (repeats count as often as they occur): sklearn's scores of
+        every clustering pair's two label columns restricted to ids, averaged over the pairs without weights --
+        MutualInformation.get_measure (correspondence_retrieval/code/measures/mutual_information.py:74-85).  Usable after
+        init(); it leaves the tables, the measure and the generator of the handle alone.
+        measures: names out of SCORE_NAMES (default: all six).  prefixes: strictly increasing sizes; the result then holds one
+        value per prefix ids[:k] (a trailing len(ids) is added when missing), arrays instead of floats.
+        -> {name: float | array [len(prefixes)]}; per_pair=True adds 'per_pair': {name: array [..., P]}, return_stats=True
+        adds 'stats': the raw values per (prefix, pair) (SCORE_STATS_DTYPE)."""
+        names, mask = score_mask(measures)
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        if ids.ndim != 1 or len(ids) < 1:
+            raise ValueError("score_subset needs a non-empty list of clip ids")
+        if self._h is None:
+            raise _lib.AcavError("score_subset before init(): the handle does not exist yet")
+        curve = prefixes is not None
+        pre = np.ascontiguousarray(list(prefixes) if curve else [len(ids)], dtype=np.int64)
+        if curve and (len(pre) == 0 or pre[-1] != len(ids)):
+            pre = np.append(pre, len(ids)).astype(np.int64)
+        if len(pre) > 1 and np.any(np.diff(pre) <= 0) or pre[0] < 1:
+            raise ValueError("prefixes must increase strictly from at least 1 to at most len(ids)")
+        q, p = len(pre), self._npairs
+        scores = np.empty((q, len(SCORE_NAMES)), np.float64)
+        pp = np.empty((q, len(SCORE_NAMES), p), np.float64) if per_pair else None
+        stats = np.zeros((q, p), SCORE_STATS_DTYPE) if return_stats else None
+        _lib.check(_lib._lib.acav_mi_score_subset(self._h, _lib.ptr(ids), len(ids), _lib.ptr(pre), q, mask, _lib.ptr(scores),
+                                                  _lib.ptr(pp), _lib.ptr(stats)))
+        nq = q if curve and len(prefixes) == q else q - 1 if curve else 1
+
+        def pick(a):
+            return a[:nq].copy() if curve else a[0].copy() if a.ndim > 1 else float(a[0])
+
+        out = {m: pick(scores[:, SCORE_NAMES.index(m)]) for m in names}
+        if per_pair:
+            out['per_pair'] = {m: pick(pp[:, SCORE_NAMES.index(m), :]) for m in names}
+        if return_stats:
+            out['stats'] = stats[:nq] if curve else stats[0]
         return out
 
     def get_batch_ranges(self):
