@@ -41,6 +41,7 @@ SIGNATURES = {
     "acav_kmeans_train_multi": [vp, i32, vp, vp, i64, f64, vp, vp],
     "acav_kmeans_train_form": [i32, i32, i64, i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32)],
     "acav_kmeans_assign_plan": [i32, i32, i64, i32, i32, i32, i32, C.POINTER(i32)],
+    "acav_kmeans_quality": [vp, vp, i64, vp, vp, vp],
     "acav_kmeans_apply_update": [vp, vp, i64, vp, f64],
     "acav_kmeans_sync": [vp],
     "acav_kmeans_shape": [vp, C.POINTER(i32), C.POINTER(i32)],

@@ -1,0 +1,203 @@
+"""`cli.py evaluate`: how good is a trained clustering?
+
+The clustering stage writes assignment shards and nothing that says whether they are any good: the one figure the
+reference computes -- the mean min-distance KMeans.add returns -- is thrown away by its train loop
+(clustering/code/run_clustering.py:171-175).  This module reports, per view and cached epoch, what a second sweep over
+the rows finds (KMeans.quality, acav_kmeans_quality: float64 distances on the GPU, there is no CPU path):
+
+  for a row x_i with label l_i (calc_best's, under-used-centre discount included):
+    a2_i = ||x_i - c_{l_i}||^2, b2_i = min_{k != l_i} ||x_i - c_k||^2 (+inf when K = 1),
+    displaced_i = (b2_i < a2_i): the discount put the row somewhere other than its nearest centre,
+    s_i = (sqrt b2_i - sqrt a2_i) / max(sqrt a2_i, sqrt b2_i): the centroid ("simplified") silhouette, 0 when both are 0 or K = 1
+  per cluster: count, sum a2, sum sqrt a2, sum s, displaced rows, sum min(a2, b2)
+  from those (compose): sizes and empty clusters, inertia = sum a2 / n, nearest_inertia = sum min(a2, b2) / n, the
+  displaced share, the mean silhouette, Davies-Bouldin with the trained centres (S_k = sum sqrt a2 / count,
+  M_kl = ||c_k - c_l||, DB = mean_k max_{l != k} (S_k + S_l) / M_kl over the non-empty clusters, coincident pairs skipped),
+  and the clusters the discount is active for in that state (fp32 counts < fp32((count / K) ** p)).
+
+    python -m acav100m_amd.clustering.cli evaluate --feature_path=<brace glob .pkl> --meta_path=<dir> \\
+        --out_path=<dir of a cluster run> --clustering.cached_epoch=<e | [e0,e1,...]> \\
+        [--evaluate.out_path=quality.json] [--evaluate.rows_path=<dir>]
+
+Reads cache_epoch_{e}_{name} like a resumed `cluster` run, reads the rows once per row group (data.resident_bytes) and
+evaluates every listed epoch on them while they are on the device.  Writes no assignment shard and no log file.
+evaluate.rows_path: one <shard>.quality.npz per shard with `filename`, `epochs` and, per view, "<model_key>/<layer>" ->
+float64 [epochs, rows, 2] = (a2, b2) -- an outlier or low-margin filter downstream.  One process, one GPU.
+"""
+import json
+from collections import OrderedDict
+from pathlib import Path
+
+import numpy as np
+
+from .sgd_clustering import QUALITY_COLS
+
+COUNT, SUM_A2, SUM_SQRT_A2, SUM_S, DISPLACED, SUM_MIN = range(QUALITY_COLS)  # ACAV_QUALITY_* (include/acav_hip.h)
+
+
+def compose(cluster_stats, centers, counts, count, reinit=(.7, 5.0)):
+    """[K, QUALITY_COLS] per-cluster sums + the state they were taken in -> the report dict (pure numpy, float64)"""
+    cs = np.asarray(cluster_stats, np.float64)
+    centers = np.asarray(centers, np.float32)
+    K = cs.shape[0]
+    if cs.shape != (K, QUALITY_COLS) or centers.shape[0] != K:
+        raise ValueError("cluster_stats {} / centers {} do not belong together".format(cs.shape, centers.shape))
+    sizes = np.rint(cs[:, COUNT]).astype(np.int64)
+    n = int(sizes.sum())
+    nan = float('nan')
+    per_row = lambda col: float(cs[:, col].sum() / n) if n else nan  # noqa: E731
+    # Davies-Bouldin over the non-empty clusters; centre distances in the difference form (coincident centres give exactly 0)
+    ne = np.flatnonzero(sizes > 0)
+    db = nan
+    if len(ne) >= 2:
+        S = cs[ne, SUM_SQRT_A2] / cs[ne, COUNT]
+        C = centers[ne].astype(np.float64)
+        worst = []
+        for i in range(len(ne)):
+            M = np.sqrt(((C - C[i]) ** 2).sum(-1))
+            ok = M > 0
+            ok[i] = False
+            if ok.any():
+                worst.append(((S[i] + S[ok]) / M[ok]).max())
+        db = float(np.mean(worst)) if worst else nan
+    p = float(reinit[0])
+    thr = np.float32((float(count) / K) ** p)
+    under = np.flatnonzero(np.asarray(counts, np.float32) < thr)
+    displaced = int(np.rint(cs[:, DISPLACED].sum()))
+    return {
+        'n': n, 'K': int(K),
+        'empty': int((sizes == 0).sum()), 'empty_clusters': [int(k) for k in np.flatnonzero(sizes == 0)],
+        'sizes': [int(v) for v in sizes], 'size_min': int(sizes.min()), 'size_median': float(np.median(sizes)), 'size_max': int(sizes.max()),
+        'inertia': per_row(SUM_A2), 'nearest_inertia': per_row(SUM_MIN),
+        'displaced': displaced, 'displaced_share': (displaced / n) if n else nan,
+        'silhouette': per_row(SUM_S), 'davies_bouldin': db,
+        'underused': int(len(under)), 'underused_clusters': [int(k) for k in under],
+    }
+
+
+def format_report(report):
+    head = "{:<32}{:>6}{:>10}{:>6}{:>7}{:>11}{:>14}{:>14}{:>11}{:>10}{:>10}".format(
+        'view', 'epoch', 'n', 'K', 'empty', 'underused', 'inertia', 'nearest', 'displaced', 'silh', 'DB')
+    lines = [head]
+    for name, per_epoch in report['views'].items():
+        for epoch, rep in per_epoch.items():
+            lines.append("{:<32}{:>6}{:>10}{:>6}{:>7}{:>11}{:>14.6g}{:>14.6g}{:>10.2f}%{:>10.4f}{:>10.4f}".format(
+                name, epoch, rep['n'], rep['K'], rep['empty'], rep['underused'], rep['inertia'], rep['nearest_inertia'],
+                100.0 * rep['displaced_share'], rep['silhouette'], rep['davies_bouldin']))
+    return '\n'.join(lines)
+
+
+def _epochs(value):
+    if value is None:
+        raise ValueError("evaluate needs --clustering.cached_epoch=<e | [e0,e1,...]>: the epoch(s) of the cluster run to judge")
+    epochs = [value] if isinstance(value, int) else list(value)
+    if not epochs or not all(isinstance(e, int) and not isinstance(e, bool) for e in epochs):
+        raise ValueError("clustering.cached_epoch must be an epoch or a list of epochs, not {!r}".format(value))
+    return epochs
+
+
+def _find(saved, view):
+    """the cached attrs of a view: by its full key, or -- a reference-written file does not name the modality -- by
+    (model_key, layer) like run_clustering.load_clusterings"""
+    if view in saved:
+        return saved[view]
+    for key, val in saved.items():
+        if key[1:] == view[1:]:
+            return val
+    return None
+
+
+def load_states(args, epochs):
+    """{epoch: {(kind, model_key, layer): attrs}} of the listed epochs, refusing -- before any shard is read -- a cache that
+    is missing, unreadable, without a clustering of one of args.models, or still in its warm-up"""
+    from . import run_clustering as rc
+    states = OrderedDict()
+    for e in epochs:
+        path = rc._cache_path(args, e)
+        if not path.is_file() and args.clustering.load_cache_from_shard_subset:
+            path = rc._subset_cache(args, e) or path
+        if not path.is_file():
+            raise FileNotFoundError("no clustering cache of epoch {}: {} does not exist".format(e, path))
+        saved = rc._read_cache(path)
+        if not saved:
+            raise ValueError("clustering cache {} holds no clustering".format(path))
+        for mk in (args.models or []):
+            if not any(key[1] == mk for key in saved):
+                raise ValueError("clustering cache {} lacks a view of model {!r} (it has {})".format(
+                    path, mk, sorted({key[1] for key in saved})))
+        for key, dt in saved.items():
+            K, rounds, count = dt['centers'].shape[0], int(dt.get('initial_rounds', 10)), int(dt.get('count', 0))
+            if count < rounds * K:
+                raise ValueError("clustering cache {}: view {} is still in its warm-up, count = {} < {}*K = {}: its labels are "
+                                 "random draws, train it further first".format(path, '/'.join(key[1:]), count, rounds, rounds * K))
+        states[e] = saved
+    return states
+
+
+def evaluate(args):
+    """the `evaluate` verb: prints one line per view and epoch, writes the report as json when evaluate.out_path is given,
+    returns it"""
+    from .. import shards as io
+    from . import run_clustering as rc
+    from .sgd_clustering import KMeans
+    opts = args.get('evaluate') or {}
+    epochs = _epochs(args.clustering.cached_epoch)
+    states = load_states(args, epochs)
+    out_path, rows_path = opts.get('out_path'), opts.get('rows_path')
+
+    paths = [Path(p) for p in sorted(io.brace_expand(args.data.path))]
+    sizes = io.shard_sizes_from_meta(paths, args.data.meta.path, use_cache=True)
+    paths = [p for p in paths if p.stem in sizes]
+    probe = None
+    for first in paths:
+        probe = io.load_feature_shards([first], model_order=list(args.models or []), audio_models=tuple(args.model_types.audio or ()))
+        if probe.views:
+            break
+    if probe is None or not probe.views:
+        raise ValueError("none of the {} shards of {} could be read".format(len(paths), args.data.path))
+    view_dims = OrderedDict((v, m.shape[1]) for v, m in probe.views.items())
+    dev = rc._device(args)
+    cl = OrderedDict()
+    for e, saved in states.items():
+        for v, d in view_dims.items():
+            dt = _find(saved, v)
+            if dt is None or dt['centers'].shape[1] != d:
+                raise ValueError("the clustering cache of epoch {} lacks view {} (width {})".format(e, '/'.join(v[1:]), d))
+            km = KMeans.load(dt)
+            km.args = None  # one process, one GPU, whatever run wrote the cache
+            cl[e, v] = km.to(dev)
+    row_bytes = 4 * sum(view_dims.values())
+    groups = rc._RowGroups(args, paths, sizes, row_bytes, rc._device_budget(args), view_dims)
+    acc = OrderedDict((key, np.zeros((km.centers.shape[0], QUALITY_COLS), np.float64)) for key, km in cl.items())
+    if rows_path is not None:
+        Path(rows_path).mkdir(parents=True, exist_ok=True)
+    for _gi, table, rows in groups.iterate():
+        per_row = {}
+        for (e, v), km in cl.items():  # every epoch's centres on the rows while they are on the device
+            labels, _ = km.calc_best(rows[v], need_mean=False)
+            res = km.quality(rows[v], labels, rows=rows_path is not None)
+            if rows_path is not None:
+                res, per_row[e, v] = res
+            acc[e, v] += res  # row groups in group order
+        if rows_path is not None:
+            for shard, ids in table.shard_rows.items():
+                if not ids:
+                    continue
+                ids = np.asarray(ids, np.int64)
+                arrays = {'/'.join(v[1:]): np.stack([per_row[e, v][ids] for e in epochs]) for v in view_dims}
+                np.savez(Path(rows_path) / (shard + '.quality.npz'), filename=np.array([table.filename[i] for i in ids]),
+                         epochs=np.asarray(epochs, np.int64), **arrays)
+
+    report = {'feature_path': str(args.data.path), 'clusters_path': str(args.data.output.path), 'epochs': epochs,
+              'views': OrderedDict()}
+    for (e, v), km in cl.items():
+        centers, counts, count, _fb = km.state_arrays()
+        rep = compose(acc[e, v], centers, counts, count, km.reinit)
+        report['views'].setdefault('/'.join(v[1:]), OrderedDict())[str(e)] = rep
+    print(format_report(report))
+    if out_path is not None:
+        out_path = Path(out_path)
+        out_path.parent.mkdir(parents=True, exist_ok=True)
+        with open(out_path, 'w') as f:
+            json.dump(report, f, indent=1)
+    return report

@@ -15,6 +15,9 @@ from .. import _lib
 from ..rng import default_generator
 
 
+QUALITY_COLS = 6  # ACAV_QUALITY_COLS (include/acav_hip.h): count, sum a2, sum sqrt a2, sum s, displaced, sum min(a2, b2)
+
+
 def _as_f32_2d(batch, width=None):
     """-> (object keeping the memory alive, void*, rows, is_torch_cuda); width: the d the library will stride by"""
     shape = tuple(batch.shape) if hasattr(batch, "shape") else np.shape(batch)
@@ -244,6 +247,31 @@ class KMeans:
         mean = C.c_float(0)
         _lib.check(_lib._lib.acav_kmeans_assign(h, xp, b, _lib.ptr(labels), C.byref(mean)))
         return labels, mean.value
+
+    def quality(self, batch, labels=None, rows=False):
+        """Distance statistics of labelled rows (acav_kmeans_quality; no counterpart in the reference) ->
+        cluster_stats float64 [k, QUALITY_COLS]: per cluster count, sum a2, sum sqrt a2, sum s, displaced rows, sum min(a2, b2)
+        (a2 / b2: squared distance to the assigned / the nearest other centre, s: the centroid silhouette); with rows=True
+        also row_stats float64 [b, 2] = (a2, b2) per row.  labels=None: calc_best(batch, need_mean=False)'s.  float64
+        throughout; row_stats do not depend on how the rows are split into calls.  Refused during the warm-up."""
+        h = self._require_handle()
+        k = self._shape[0]
+        keep, xp, b, _ = _as_f32_2d(batch, self._shape[1])
+        if labels is None:
+            labels, _ = self.calc_best(batch, need_mean=False)
+        if hasattr(labels, "data_ptr"):
+            import torch
+            lab = labels.detach().to(torch.long).contiguous()
+            if lab.is_cuda:
+                torch.cuda.current_stream(lab.device).synchronize()
+        else:
+            lab = np.ascontiguousarray(labels, np.int64)
+        if tuple(lab.shape) != (b,):
+            raise ValueError("expected {} labels, got shape {}".format(b, tuple(lab.shape)))
+        cluster_stats = np.empty((k, QUALITY_COLS), np.float64)
+        row_stats = np.empty((b, 2), np.float64) if rows else None
+        _lib.check(_lib._lib.acav_kmeans_quality(h, xp, b, _lib.ptr(lab), _lib.ptr(cluster_stats), _lib.ptr(row_stats)))
+        return (cluster_stats, row_stats) if rows else cluster_stats
 
     def train_stats(self):
         """(bulk training calls that ran as one persistent launch, launches that gave up and were re-run per step)"""
