@@ -42,6 +42,7 @@ SIGNATURES = {
     "acav_kmeans_train_form": [i32, i32, i64, i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32)],
     "acav_kmeans_assign_plan": [i32, i32, i64, i32, i32, i32, i32, C.POINTER(i32)],
     "acav_kmeans_quality": [vp, vp, i64, vp, vp, vp],
+    "acav_kmeans_quality_plan": [i64, i32, i32, C.POINTER(i64)],
     "acav_kmeans_apply_update": [vp, vp, i64, vp, f64],
     "acav_kmeans_sync": [vp],
     "acav_kmeans_shape": [vp, C.POINTER(i32), C.POINTER(i32)],
@@ -96,6 +97,7 @@ SIGNATURES = {
     "acav_mi_get_counts": [vp, vp, vp, vp, C.POINTER(i64)],
     "acav_mi_score_subset": [vp, vp, i64, vp, i32, u32, vp, vp, vp],
     "acav_score_compose": [vp, vp],
+    "acav_score_plan": [i32, i32, i64, i64, i32, C.POINTER(i64)],
     "acav_mt_stream_fill": [vp, i32, i64, i64, i32, vp],
     "acav_mi_sync": [vp],
     "acav_mi_timer_begin": [vp],

@@ -38,6 +38,25 @@ constexpr size_t quality_lds(int K)
 }
 static_assert(quality_lds(QUALITY_MAX_K) <= 160 * 1024, "the per-cluster sums of the largest K must fit a workgroup's LDS");
 
+// the launch shape of k_quality, a function of (n, K, cus) alone: as many workgroups per CU as their LDS lets live there (4 at
+// most), each taking the row tiles b, b + grid, ...
+struct QualityPlan {
+    int64_t ntiles;
+    int grid;
+    size_t lds;
+    int per_cu;
+};
+
+QualityPlan quality_plan(int64_t n, int K, int cus)
+{
+    QualityPlan p;
+    p.ntiles = (n + QM - 1) / QM;
+    p.lds = quality_lds(K);
+    p.per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / p.lds));
+    p.grid = (int)std::min<int64_t>(p.ntiles, (int64_t)cus * p.per_cu);
+    return p;
+}
+
 // labels outside [0, K): counted before anything indexes LDS with them
 __global__ __launch_bounds__(256) void k_quality_labels(const int64_t *__restrict__ labels, int64_t n, int K, unsigned *__restrict__ bad)
 {
@@ -195,6 +214,15 @@ struct StreamDrain {  // declared after the scratch buffers of a call: the strea
 
 }  // namespace
 
+ACAV_EXPORT int acav_kmeans_quality_plan(int64_t n, int k, int cus, int64_t *out)
+{
+    ACAV_REQUIRE(out, ACAV_EINVAL, "NULL argument");
+    ACAV_REQUIRE(n >= 0 && n < ((int64_t)1 << 37) && k > 0 && k <= QUALITY_MAX_K && cus > 0, ACAV_EINVAL, "bad sizes");
+    const QualityPlan p = quality_plan(n, k, cus);
+    out[0] = p.ntiles, out[1] = p.grid, out[2] = (int64_t)p.lds, out[3] = p.per_cu;
+    return ACAV_OK;
+}
+
 ACAV_EXPORT int acav_kmeans_quality(acav_kmeans *km, const float *x, int64_t n, const int64_t *labels, double *cluster_stats,
                                     double *row_stats)
 {
@@ -231,10 +259,8 @@ ACAV_EXPORT int acav_kmeans_quality(acav_kmeans *km, const float *x, int64_t n, 
     ACAV_HIP_TRY(hipStreamSynchronize(st));
     ACAV_REQUIRE(nbad == 0, ACAV_EINVAL, "%u of %lld labels are outside [0, %d)", nbad, (long long)n, K);
 
-    const int64_t ntiles = (n + QM - 1) / QM;
-    const size_t lds = quality_lds(K);
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / lds));
-    const int grid = (int)std::min<int64_t>(ntiles, (int64_t)cus * per_cu);
+    const QualityPlan plan = quality_plan(n, K, cus);
+    const int grid = plan.grid;
     const bool rows_dev = row_stats && is_device_ptr(row_stats);
     ACAV_TRY(cd.ensure(sizeof(double) * (size_t)K * d));
     ACAV_TRY(cn.ensure(sizeof(double) * (size_t)K));
@@ -247,7 +273,7 @@ ACAV_EXPORT int acav_kmeans_quality(acav_kmeans *km, const float *x, int64_t n, 
                                      (int)quality_lds(QUALITY_MAX_K)));
 
     hipLaunchKernelGGL(k_quality_centres, dim3((unsigned)K), dim3(64), 0, st, km->centers.as<float>(), d, cd.as<double>(), cn.as<double>());
-    hipLaunchKernelGGL(k_quality, dim3((unsigned)grid), dim3(256), lds, st, static_cast<const float *>(dx), n, d, cd.as<double>(),
+    hipLaunchKernelGGL(k_quality, dim3((unsigned)grid), dim3(256), plan.lds, st, static_cast<const float *>(dx), n, d, cd.as<double>(),
                        cn.as<double>(), K, static_cast<const int64_t *>(dl), drows, parts.as<double>());
     hipLaunchKernelGGL(k_quality_fold, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, st, parts.as<double>(), grid, len, out.as<double>());
     ACAV_HIP_TRY(hipGetLastError());

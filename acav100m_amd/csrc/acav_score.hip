@@ -227,6 +227,41 @@ int floor_pow2(int x)
     return p;
 }
 
+// launch shapes of one prefix: functions of (C, P, n, m) alone -- n ids scored, the last m of them new to the tables
+struct ScorePlan {
+    bool lds;            // the table of a pair fits the LDS share (k_score_build_lds), else k_score_build_global
+    int64_t slices, per; // table-building workgroups per pair and the ids each takes
+    int nb;              // k_score_cells workgroups per pair
+    int lpc;             // k_score_emi: lanes per column
+    int64_t Z;           //              slices of every cell's n_ij range
+    int emi_parts;       //              partials per pair (0: no EMI)
+};
+
+ScorePlan score_plan(int C, int P, int64_t n, int64_t m, bool want_emi)
+{
+    const size_t cc = (size_t)C * C;
+    ScorePlan s = {};
+    s.nb = (int)((cc + CELL_CHUNK - 1) / CELL_CHUNK);
+    s.lds = cc * sizeof(int) <= LDS_TABLE_MAX;
+    if (s.lds) {
+        // enough slices to fill the device, none shorter than BUILD_IDS_PER_WG ids
+        s.slices = (m + BUILD_IDS_PER_WG - 1) / BUILD_IDS_PER_WG;
+        const int64_t cap = std::max<int64_t>(1, 2048 / P);
+        s.slices = std::min(s.slices, cap);
+        s.per = (m + s.slices - 1) / s.slices;
+    } else {
+        s.slices = (m + 255) / 256, s.per = 256;  // one id per thread
+    }
+    if (want_emi) {
+        // lanes per column: 16 once there are 16 columns to spread a workgroup over, all 256 for a single column
+        s.lpc = std::max(16, 256 / floor_pow2(C));
+        // slices of every cell's n_ij range: few labels and many clips leave (row, pair) alone too coarse to fill the device
+        s.Z = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(8192 / ((int64_t)P * C), n / (2 * s.lpc)), 1024));
+        s.emi_parts = (int)(C * s.Z);
+    }
+    return s;
+}
+
 }  // namespace
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
@@ -268,15 +303,27 @@ ACAV_EXPORT int acav_score_compose(const acav_score_stats *s, double *out)
     return ACAV_OK;
 }
 
+ACAV_EXPORT int acav_score_plan(int C, int P, int64_t n, int64_t m, int want_emi, int64_t *out)
+{
+    ACAV_REQUIRE(out, ACAV_EINVAL, "NULL argument");
+    ACAV_REQUIRE(C >= 1 && C <= 32768 && P >= 1 && P <= 65535 && n >= 1 && n < ((int64_t)1 << 31) && m >= 1 && m <= n, ACAV_EINVAL,
+                 "bad sizes");
+    const ScorePlan s = score_plan(C, P, n, m, want_emi != 0);
+    const int64_t v[ACAV_SCORE_PLAN_LEN] = {s.lds ? 1 : 0, s.slices, s.per, s.nb, s.lpc, s.Z, s.emi_parts};
+    for (int i = 0; i < ACAV_SCORE_PLAN_LEN; ++i) out[i] = v[i];
+    return ACAV_OK;
+}
+
 int acav::score_subset_run(const ScoreJob &job)
 {
     const int C = job.C, P = job.P;
     const size_t cc = (size_t)C * C, pc = (size_t)P * C;
     hipStream_t st = job.stream;
     const bool want_emi = (job.mask >> ACAV_SCORE_ADJUSTED_MUTUAL_INFO) & 1u;
-    // launch shapes: functions of (C, P, n) alone
-    const int nb = (int)((cc + CELL_CHUNK - 1) / CELL_CHUNK);
-    const bool lds = cc * sizeof(int) <= LDS_TABLE_MAX;
+    // launch shapes: functions of (C, P, n) alone; the path and the cell chunks are the same for every prefix
+    const ScorePlan whole = score_plan(C, P, job.n, job.n, want_emi);
+    const int nb = whole.nb;
+    const bool lds = whole.lds;
     ACAV_REQUIRE(P <= 65535, ACAV_EINVAL, "subset scoring launches one workgroup row per pair: P = %d exceeds 65535", P);
     DevBuf N, a, b, part_mi, part_tab, part_emi, raw;
     std::vector<PairRaw> host((size_t)job.nprefix * P);
@@ -300,16 +347,12 @@ int acav::score_subset_run(const ScoreJob &job)
     for (int q = 0; q < job.nprefix; ++q) {
         const int64_t n = job.prefix[q], m = n - done;
         if (timing) ACAV_HIP_TRY(hipEventRecord(ev[0], st));
+        const ScorePlan plan = score_plan(C, P, n, m, want_emi);
         if (lds) {
-            // enough slices to fill the device, none shorter than BUILD_IDS_PER_WG ids
-            int64_t slices = (m + BUILD_IDS_PER_WG - 1) / BUILD_IDS_PER_WG;
-            const int64_t cap = std::max<int64_t>(1, 2048 / P);
-            slices = std::min(slices, cap);
-            const int64_t per = (m + slices - 1) / slices;
-            hipLaunchKernelGGL(k_score_build_lds, dim3((unsigned)slices, (unsigned)P), dim3(256), cc * sizeof(int), st, job.asg, job.D, C,
-                               job.pairs, job.ids, (long long)done, (long long)n, (long long)per, N.as<int>());
+            hipLaunchKernelGGL(k_score_build_lds, dim3((unsigned)plan.slices, (unsigned)P), dim3(256), cc * sizeof(int), st, job.asg, job.D, C,
+                               job.pairs, job.ids, (long long)done, (long long)n, (long long)plan.per, N.as<int>());
         } else {
-            hipLaunchKernelGGL(k_score_build_global, dim3((unsigned)((m + 255) / 256), (unsigned)P), dim3(256), 0, st, job.asg, job.D, C,
+            hipLaunchKernelGGL(k_score_build_global, dim3((unsigned)plan.slices, (unsigned)P), dim3(256), 0, st, job.asg, job.D, C,
                                job.pairs, job.ids, (long long)done, (long long)n, N.as<int>());
         }
         ACAV_HIP_TRY(hipGetLastError());
@@ -321,15 +364,10 @@ int acav::score_subset_run(const ScoreJob &job)
                            b.as<int>(), job.lnk, part_mi.as<double>(), part_tab.as<long long>());
         ACAV_HIP_TRY(hipGetLastError());
         if (timing) ACAV_HIP_TRY(hipEventRecord(ev[2], st));
-        int emi_parts = 0;
+        const int emi_parts = plan.emi_parts;
         if (want_emi) {
-            // lanes per column: 16 once there are 16 columns to spread a workgroup over, all 256 for a single column
-            const int lpc = std::max(16, 256 / floor_pow2(C));
-            // slices of every cell's n_ij range: few labels and many clips leave (row, pair) alone too coarse to fill the device
-            const int64_t Z = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(8192 / ((int64_t)P * C), n / (2 * lpc)), 1024));
-            emi_parts = (int)(C * Z);
             ACAV_TRY(part_emi.ensure(sizeof(double) * (size_t)emi_parts * P));
-            hipLaunchKernelGGL(k_score_emi, dim3((unsigned)C, (unsigned)P, (unsigned)Z), dim3(256), 0, st, C, (long long)n, lpc, a.as<int>(),
+            hipLaunchKernelGGL(k_score_emi, dim3((unsigned)C, (unsigned)P, (unsigned)plan.Z), dim3(256), 0, st, C, (long long)n, plan.lpc, a.as<int>(),
                                b.as<int>(), job.lnk, job.lf, part_emi.as<double>());
             ACAV_HIP_TRY(hipGetLastError());
         }

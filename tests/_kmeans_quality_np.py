@@ -118,6 +118,15 @@ NOISE = np.array([1.0, 0.4])
 SHAPES = [(1, 4, 2), (63, 7, 5), (65, 88, 33), (1000, 128, 64), (777, 1024, 257), (300, 2048, 1024), (129, 352, 1)]
 
 
+def large_shapes(cus):
+    """(n, d, K) at which every workgroup of k_quality takes several row tiles on a device of `cus` compute units (kind
+    'discount').  The grid is min(tiles, cus * per_cu) with 64 rows per tile and per_cu = 4 workgroups per CU while their LDS
+    allows, 1 at K = 2048; every n is 64 m + 1, so the last tile holds one row and is not its workgroup's first:
+        small K, at least 2 tiles per workgroup | two centre passes (K > 64) and a column tail (d = 32 + 8) | the largest K:
+        [K][6] sums carried over tiles, most clusters without a row"""
+    return [(8 * cus * 64 + 65, 8, 5), (8 * cus * 64 + 65, 40, 70), (2 * cus * 64 + 65, 4, 2048)]
+
+
 def make_case(n, d, K, kind='discount', seed=0):
     """-> x [n,d] fp32, centres [K,d] fp32, counts [K] fp32, count.  Even clusters are under-used in the state (counts below
     (count / K) ** 0.7, the library's discount divides their distances by 5), the rows are drawn around the odd ones with noise

@@ -1,7 +1,9 @@
 """Pure float64 / Python-int restatement of the subset scores (include/acav_hip.h, "subset scoring") in numpy -- shared by the
-golden generator (tests/golden/gen_subset_scores.py, which records how far it is from sklearn) and the tests.  It imports
-neither sklearn nor the library."""
+golden generators (tests/golden/gen_subset_scores.py and gen_subset_scores_large.py, which record how far it is from sklearn)
+and the tests.  It imports neither sklearn nor the library."""
+import importlib.util
 import math
+import os
 
 import numpy as np
 
@@ -24,8 +26,8 @@ def table(assign, ids, d1, d2, C):
     return N
 
 
-def emi(N):
-    """exact expected mutual information, every (cell, n_ij) term as one vector element, G added in sklearn's order"""
+def emi_terms(N):
+    """the terms of the exact expected mutual information, one vector element per (cell, n_ij), G added in sklearn's order"""
     n = int(N.sum())
     b, a = N.sum(1), N.sum(0)
     rows, cols = np.nonzero(b)[0], np.nonzero(a)[0]
@@ -43,7 +45,12 @@ def emi(N):
     G = ((((((((lf[B] + lf[A]) + lf[n - B]) + lf[n - A]) - lf[n]) - lf[nij]) - lf[B - nij]) - lf[A - nij])
          - lf[n - B - A + nij])
     t2 = ((ln[n] + ln[nij]) - ln[B]) - ln[A]
-    return float(np.sum(((nij / float(n)) * t2) * np.exp(G)))
+    return ((nij / float(n)) * t2) * np.exp(G)
+
+
+def emi(N):
+    """exact expected mutual information: the sum of emi_terms"""
+    return float(np.sum(emi_terms(N)))
 
 
 def raw_stats(N, with_emi=True):
@@ -93,3 +100,30 @@ def compose(s):
     all_pairs = tp + fp + fn + tn
     rand = 1.0 if all_pairs == 0 else float(tp + tn) / float(all_pairs)
     return dict(zip(NAMES, (mi, nmi, ami, ari, fm, rand)))
+
+
+# ------------------------------------------------------------------------------------------------ the large cases
+def large_inputs(seed, V, D, C, n, repeats):
+    """-> assign [V, D] int64, ids [n] int64 of a case of tests/golden/subset_scores_large.npz, which records these six numbers
+    and not the arrays: make_assign of tests/golden/gen_subset_scores.py on RandomState(seed), then the ids from the same stream"""
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gen_subset_scores.py")
+    spec = importlib.util.spec_from_file_location("_gen_subset_scores", path)
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    rs = np.random.RandomState(seed)
+    assign = gen.make_assign(rs, V, D, C).astype(np.int64)
+    ids = rs.randint(0, V, n) if repeats else rs.choice(V, n, replace=False)
+    return assign, ids.astype(np.int64)
+
+
+def ami_reorder_bound(N, s):
+    """how far two float64 evaluations of adjusted_mutual_info can be apart when they add the same EMI terms in different
+    orders: any order of T terms is within (T - 1) 2^-53 sum|term| of exact, so two orders differ by at most
+    de = T 2^-52 sum|term| (charged in full); AMI = (mi - e) / (h - e) with h = the mean entropy has d AMI / d e =
+    (mi - h) / (h - e)^2, and on the segment between the two values of e the denominator is at least |h - e| - de, hence
+    |d AMI| <= de |h - mi| / (|h - e| (|h - e| - de)).  s: raw_stats(N).  -> de, the bound (inf when the guard leaves no room)"""
+    t = emi_terms(N)
+    de = len(t) * 2.0 ** -52 * float(np.abs(t).sum())
+    h = (s['h_row'] + s['h_col']) / 2.0
+    den = abs(h - s['emi'])
+    return de, (de * abs(h - s['mi']) / (den * (den - de)) if den > de else float('inf'))

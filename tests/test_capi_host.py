@@ -1,7 +1,9 @@
 """CPU-only checks of the product's host side: the C-ABI library loads and exports every symbol
 include/acav_hip.h declares, the host MT19937 stream equals torch's (golden), the mirror classes
-keep the reference's surface, and nothing in the product imports the oracle."""
+keep the reference's surface, nothing in the product imports the oracle, the launch plans of the two evaluate kernels
+(acav_kmeans_quality_plan, acav_score_plan) and the large scoring fixture against the numpy restatement."""
 import ast
+import ctypes as C
 import os
 import re
 
@@ -28,6 +30,118 @@ def test_header_symbols_exported(acav):
         assert hasattr(lib, name), f"{name} declared in include/acav_hip.h but not exported"
     assert declared - {"acav_last_error"} == set(_lib.SIGNATURES), "ctypes table and header drifted"
     assert lib.acav_version() >= 100
+
+
+# (n, K, cus) -> (row tiles, grid, dynamic LDS bytes, workgroups per CU), read off acav_kmeans_quality as it stood before the
+# plan function: tiles = ceil(n / 64); LDS = 8 (6 K + 64 * 34 + 8 * 64) + 4 * 64 * 36 + 4 * 64 = 48 K + 30976 bytes;
+# per_cu = max(1, min(4, 163840 // LDS)); grid = min(tiles, cus * per_cu)
+QUALITY_PLANS = [
+    ((0, 1, 256), (0, 0, 31024, 4)), ((1, 1, 256), (1, 1, 31024, 4)), ((64, 1, 256), (1, 1, 31024, 4)),
+    ((65, 1, 256), (2, 2, 31024, 4)), ((65536, 1, 256), (1024, 1024, 31024, 4)), ((65537, 1, 256), (1025, 1024, 31024, 4)),
+    ((0, 64, 256), (0, 0, 34048, 4)), ((1, 64, 256), (1, 1, 34048, 4)), ((64, 64, 256), (1, 1, 34048, 4)),
+    ((65, 64, 256), (2, 2, 34048, 4)), ((65536, 64, 256), (1024, 1024, 34048, 4)), ((65537, 64, 256), (1025, 1024, 34048, 4)),
+    ((0, 1024, 256), (0, 0, 80128, 2)), ((1, 1024, 256), (1, 1, 80128, 2)), ((64, 1024, 256), (1, 1, 80128, 2)),
+    ((65, 1024, 256), (2, 2, 80128, 2)), ((32768, 1024, 256), (512, 512, 80128, 2)), ((32769, 1024, 256), (513, 512, 80128, 2)),
+    ((0, 2048, 256), (0, 0, 129280, 1)), ((1, 2048, 256), (1, 1, 129280, 1)), ((64, 2048, 256), (1, 1, 129280, 1)),
+    ((65, 2048, 256), (2, 2, 129280, 1)), ((16384, 2048, 256), (256, 256, 129280, 1)), ((16385, 2048, 256), (257, 256, 129280, 1)),
+    # the K at which a CU holds one workgroup fewer: 163840 / 40960 = 4, / 54592 = 3.001, / 81904 = 2.0004
+    ((10 ** 6, 208, 256), (15625, 1024, 40960, 4)), ((10 ** 6, 209, 256), (15625, 768, 41008, 3)),
+    ((10 ** 6, 492, 256), (15625, 768, 54592, 3)), ((10 ** 6, 493, 256), (15625, 512, 54640, 2)),
+    ((10 ** 6, 1061, 256), (15625, 512, 81904, 2)), ((10 ** 6, 1062, 256), (15625, 256, 81952, 1)),
+    # the shapes of tests/_kmeans_quality_np.large_shapes on 256 and on 8 compute units
+    ((131137, 5, 256), (2050, 1024, 31216, 4)), ((131137, 70, 256), (2050, 1024, 34336, 4)), ((32833, 2048, 256), (514, 256, 129280, 1)),
+    ((4161, 5, 8), (66, 32, 31216, 4)), ((1089, 2048, 8), (18, 8, 129280, 1)),
+    ((2 ** 37 - 1, 1, 256), (2 ** 31, 1024, 31024, 4)),
+]
+
+
+@pytest.mark.parametrize("args,want", QUALITY_PLANS, ids=["n{}-k{}-cus{}".format(*a) for a, _ in QUALITY_PLANS])
+def test_quality_plan_table(acav, args, want):
+    lib = acav.load_library()
+    out = (C.c_int64 * 4)(-7, -7, -7, -7)
+    assert lib.acav_kmeans_quality_plan(*args, out) == 0
+    assert tuple(out) == want
+
+
+def test_quality_plan_refuses_bad_sizes(acav):
+    lib = acav.load_library()
+    out = (C.c_int64 * 4)()
+    for args in ((-1, 8, 256), (2 ** 37, 8, 256), (100, 0, 256), (100, 2049, 256), (100, 8, 0)):
+        assert lib.acav_kmeans_quality_plan(*args, out) == -1, args
+    assert lib.acav_kmeans_quality_plan(100, 8, 256, None) == -1
+
+
+# (C, P, n, m, want_emi) -> (LDS table, table-building workgroups per pair, ids of each, cell workgroups per pair, EMI lanes per
+# column, EMI slices Z, EMI partials per pair), read off score_subset_run as it stood before the plan function:
+# nb = ceil(C^2 / 4096); LDS table when 4 C^2 <= 81920 (C <= 143), then slices = min(ceil(m / 8192), max(1, 2048 // P)) and
+# per = ceil(m / slices), else slices = ceil(m / 256) of 256 ids; lpc = max(16, 256 // 2^floor(log2 C));
+# Z = max(1, min(8192 // (P C), n // (2 lpc), 1024)); partials = C Z
+SCORE_PLANS = [
+    # the cases of tests/golden/subset_scores_large.npz
+    ((7, 2, 20000, 20000, 1), (1, 3, 6667, 1, 64, 156, 1092)), ((7, 2, 5000, 5000, 1), (1, 1, 5000, 1, 64, 39, 273)),
+    ((7, 2, 20000, 15000, 1), (1, 2, 7500, 1, 64, 156, 1092)),
+    ((143, 2, 20000, 20000, 1), (1, 3, 6667, 5, 16, 28, 4004)), ((144, 2, 20000, 20000, 1), (0, 79, 256, 6, 16, 28, 4032)),
+    ((300, 2, 20000, 20000, 1), (0, 79, 256, 22, 16, 13, 3900)),
+    ((2, 1, 300000, 300000, 1), (1, 37, 8109, 1, 128, 1024, 2048)), ((2, 1, 304097, 304097, 1), (1, 38, 8003, 1, 128, 1024, 2048)),
+    ((32, 45, 400000, 400000, 0), (1, 45, 8889, 1, 0, 0, 0)), ((32, 45, 400000, 400000, 1), (1, 45, 8889, 1, 16, 5, 160)),
+    # m at one workgroup's share and one past it
+    ((2, 1, 8192, 8192, 1), (1, 1, 8192, 1, 128, 32, 64)), ((2, 1, 8193, 8193, 1), (1, 2, 4097, 1, 128, 32, 64)),
+    ((2, 1, 20000, 8193, 0), (1, 2, 4097, 1, 0, 0, 0)),
+    # the cap on the workgroups per pair: 2048 // P, at least 1
+    ((2, 1024, 400000, 400000, 0), (1, 2, 200000, 1, 0, 0, 0)), ((2, 2048, 400000, 400000, 0), (1, 1, 400000, 1, 0, 0, 0)),
+    ((2, 2049, 400000, 400000, 1), (1, 1, 400000, 1, 128, 1, 2)),
+    ((1, 1, 2 ** 31 - 1, 2 ** 31 - 1, 1), (1, 2048, 1048576, 1, 256, 1024, 1024)),
+    # C: one label, the lanes-per-column steps, the last LDS table and the first global one, Z down to 1
+    ((1, 1, 1, 1, 1), (1, 1, 1, 1, 256, 1, 1)), ((3, 1, 1000, 1000, 1), (1, 1, 1000, 1, 128, 3, 9)),
+    ((15, 1, 1000, 1000, 1), (1, 1, 1000, 1, 32, 15, 225)), ((16, 1, 1000, 1000, 1), (1, 1, 1000, 1, 16, 31, 496)),
+    ((64, 2, 2500, 2500, 1), (1, 1, 2500, 1, 16, 64, 4096)),
+    ((143, 45, 1000, 1000, 1), (1, 1, 1000, 5, 16, 1, 143)), ((144, 45, 1000, 1000, 1), (0, 4, 256, 6, 16, 1, 144)),
+    ((300, 45, 1000, 1000, 1), (0, 4, 256, 22, 16, 1, 300)),
+    # Z reaches its cap at n = 1024 * 2 lpc
+    ((2, 1, 262143, 262143, 1), (1, 32, 8192, 1, 128, 1023, 2046)), ((2, 1, 262144, 262144, 1), (1, 32, 8192, 1, 128, 1024, 2048)),
+]
+
+
+@pytest.mark.parametrize("args,want", SCORE_PLANS, ids=["c{}-p{}-n{}-m{}-emi{}".format(*a) for a, _ in SCORE_PLANS])
+def test_score_plan_table(acav, args, want):
+    lib = acav.load_library()
+    out = (C.c_int64 * 7)(*([-7] * 7))
+    assert lib.acav_score_plan(*args, out) == 0
+    assert tuple(out) == want
+
+
+def test_score_plan_refuses_bad_sizes(acav):
+    lib = acav.load_library()
+    out = (C.c_int64 * 7)()
+    for args in ((0, 1, 10, 10, 1), (32769, 1, 10, 10, 1), (2, 0, 10, 10, 1), (2, 65536, 10, 10, 1), (2, 1, 0, 0, 1),
+                 (2, 1, 2 ** 31, 10, 1), (2, 1, 10, 0, 1), (2, 1, 10, 11, 1)):
+        assert lib.acav_score_plan(*args, out) == -1, args
+    assert lib.acav_score_plan(2, 1, 10, 10, 1, None) == -1
+
+
+def test_large_scoring_fixture_is_what_the_restatement_gives(golden_dir):
+    """tests/golden/subset_scores_large.npz holds seeds, not arrays: the inputs rebuilt from them give, through the numpy
+    restatement, exactly the recorded distances from sklearn -- the fixture is checked without a GPU and without sklearn"""
+    from tests import _subset_scores_np as R
+    g = np.load(os.path.join(golden_dir, "subset_scores_large.npz"))
+    names = g["cases"].tolist()
+    assert names == ["c7_n20000", "c143_n20000", "c300_n20000", "c2_n300000", "c2_n304097", "c32_p45_n400000"]
+    checked = 0
+    for name in names:
+        C_, with_emi = int(g[name + ".C"]), bool(g[name + ".emi"])
+        assign, ids = R.large_inputs(*(int(g[name + "." + k]) for k in ("seed", "V", "D", "C", "n", "repeats")))
+        assert assign.max() == C_ - 1 and len(ids) == int(g[name + ".n"]) == g[name + ".prefix"][-1]
+        assert (len(np.unique(ids)) < len(ids)) == bool(g[name + ".repeats"])
+        sk, dev = g[name + ".sk"], g[name + ".dev"]
+        assert np.isnan(sk[..., 2]).all() == (not with_emi) and np.isfinite(np.delete(sk, 2, -1)).all()
+        for q, k in enumerate(g[name + ".prefix"].tolist()):
+            for p, (d1, d2) in enumerate(g[name + ".pairs"].tolist()):
+                ours = R.compose(R.raw_stats(R.table(assign, ids[:k], d1, d2, C_), with_emi=with_emi))
+                got = np.array([abs(ours[m] - s) for m, s in zip(R.NAMES, sk[q, p])])
+                assert np.array_equal(got, dev[q, p], equal_nan=True), (name, k, p, got, dev[q, p])
+                assert not dev[q, p, 3:].any()  # adjusted_rand, fowlkes_mallows, rand: integers and one division
+                checked += 1
+    assert checked == 4 + 2 + 2 + 1 + 1 + 45 and float(np.nanmax(g["c300_n20000.dev"])) < 1e-10
 
 
 def test_trim_device_cache_is_callable_without_a_gpu(acav):

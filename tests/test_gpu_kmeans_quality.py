@@ -1,7 +1,8 @@
 """GPU: KMeans.quality / acav_kmeans_quality (acav100m_amd/csrc/acav_kmeans_quality.hip) against the float64 restatement of
 tests/_kmeans_quality_np.py within its derived bounds, its determinism and split invariance, its refusals, and that it leaves
 the handle alone.  The labels are calc_best's (pinned to the oracle in tests/test_gpu_kmeans.py); the states have under-used
-clusters, so the discount moves rows away from their nearest centre."""
+clusters, so the discount moves rows away from their nearest centre.  The `large` tests run the same checks at the smallest
+sizes at which every workgroup of k_quality takes several row tiles (R.large_shapes, from the device's CU count)."""
 import ctypes as C
 
 import numpy as np
@@ -44,8 +45,70 @@ def _case(kind, n, d, K):
     return _cache[key]
 
 
+def _cus():
+    import torch
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def _plan(n, K, cus):
+    """acav_kmeans_quality_plan -> (ntiles, grid, lds_bytes, per_cu)"""
+    from acav100m_amd import _lib
+    out = (C.c_int64 * 4)()
+    _lib.check(_lib.load_library().acav_kmeans_quality_plan(n, K, cus, out))
+    return tuple(out)
+
+
 @pytest.mark.parametrize("case", CASES, ids=_IDS)
 def test_rows_and_clusters_within_the_derived_bounds(env, case):
+    _check_rows_and_clusters(case)
+
+
+LARGE_IDS = ["small_k", "two_centre_passes", "largest_k"]  # the rows of R.large_shapes
+
+
+@pytest.mark.parametrize("which", range(3), ids=LARGE_IDS)
+def test_large_rows_and_clusters_within_the_derived_bounds(env, which):
+    """every workgroup takes at least two tiles (sums carried over, labs and rv reused, the last tile of one row is not its
+    workgroup's first); then the checks of test_rows_and_clusters_within_the_derived_bounds, the same bounds"""
+    cus = _cus()
+    n, d, K = R.large_shapes(cus)[which]
+    ntiles, grid, _, per_cu = _plan(n, K, cus)
+    assert ntiles >= 2 * grid and grid == cus * per_cu and n % 64 == 1, (n, K, cus, ntiles, grid)
+    assert per_cu == (1 if K == 2048 else 4)
+    _check_rows_and_clusters(("discount", n, d, K))
+
+
+@pytest.mark.parametrize("which", range(3), ids=LARGE_IDS)
+def test_large_whole_call_equals_one_tile_per_workgroup_pieces(env, which):
+    """the whole call (several tiles per workgroup) against the same rows in pieces of at most grid * 64 rows, each of which
+    runs one tile per workgroup -- the path the small cases pin: the same row_stats bytes, equal counts, float sums within the
+    reference's bounds; and the whole call twice gives the same bytes"""
+    cus = _cus()
+    n, d, K = R.large_shapes(cus)[which]
+    ntiles, grid, _, _ = _plan(n, K, cus)
+    assert ntiles >= 2 * grid
+    km, xt, labels, cs, rows, ref = _case("discount", n, d, K)
+    g = grid * 64
+    cuts = [0, g - 27, 2 * g - 27, n]  # a first piece that ends inside a tile, a full grid of tiles, the rest (92 rows)
+    total = np.zeros_like(cs)
+    pieces = []
+    for a, b in zip(cuts[:-1], cuts[1:]):
+        piece_tiles, piece_grid, _, _ = _plan(b - a, K, cus)
+        assert 0 < b - a <= g and piece_tiles == piece_grid
+        c_part, r_part = km.quality(xt[a:b], labels[a:b], rows=True)
+        total += c_part
+        pieces.append(r_part)
+    assert np.concatenate(pieces).tobytes() == rows.tobytes()
+    for col in (R.COUNT, R.DISPLACED):
+        assert np.array_equal(total[:, col], cs[:, col])
+    for col in (R.SUM_A2, R.SUM_SQRT_A2, R.SUM_S, R.SUM_MIN):
+        assert (np.abs(total[:, col] - ref.cluster[:, col]) <= ref.cluster_tol[:, col]).all(), col
+    cs2, rows2 = km.quality(xt, labels, rows=True)
+    assert cs2.tobytes() == cs.tobytes() and rows2.tobytes() == rows.tobytes()
+    assert km.quality(xt, labels).tobytes() == cs.tobytes()  # without row_stats
+
+
+def _check_rows_and_clusters(case):
     kind, n, d, K = case
     km, xt, labels, cs, rows, ref = _case(*case)
     assert cs.shape == (K, R.COLS) and rows.shape == (n, 2) and cs.dtype == rows.dtype == np.float64
