@@ -1,1 +1,2 @@
 from .sgd_clustering import KMeans  # noqa: F401
+from .whiten import ColumnMoments, whiten, whiten_  # noqa: F401

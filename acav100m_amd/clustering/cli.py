@@ -6,7 +6,7 @@ import sys
 
 from .. import shards as io
 from ..config import CLUSTERING_DEFAULTS, merge, parse_cli
-from .run_clustering import run_clustering, store_shards_set
+from .run_clustering import check_whiten, run_clustering, store_shards_set
 
 
 def get_args(**kwargs):
@@ -35,6 +35,8 @@ class Cli:
 
     def cluster(self, **kwargs):
         args = get_args(**kwargs)
+        from ..parallel import world
+        check_whiten(args, world()[1])  # before anything is created or read
         args.data.output.path.mkdir(parents=True, exist_ok=True)
         saved = run_clustering(args)
         store_shards_set(args, saved)
@@ -66,6 +68,8 @@ def main(argv=None):
             import torch
             want = torch.cuda.device_count()
         if int(want) > 1:
+            if command in ('cluster', 'run'):  # refused here, not once per spawned process
+                check_whiten(merge(CLUSTERING_DEFAULTS, {k: v for k, v in kwargs.items() if k.startswith('clustering.')}), int(want))
             launch.spawn_per_gpu('acav100m_amd.clustering.cli', argv, int(want))
             return None
     else:

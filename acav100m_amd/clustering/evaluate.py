@@ -21,6 +21,9 @@ the rows finds (KMeans.quality, acav_kmeans_quality: float64 distances on the GP
 
 Reads cache_epoch_{e}_{name} like a resumed `cluster` run, reads the rows once per row group (data.resident_bytes) and
 evaluates every listed epoch on them while they are on the device.  Writes no assignment shard and no log file.
+A cache that holds `whiten_std` (a `cluster --clustering.whiten=True` run) has its rows divided by it on their way to the
+device, like the run itself: the report and the rows_path values are then in whitened space, and the view's report carries
+"whitened": true and "zero_variance_columns" (divisors that are exactly 1).  Epochs that disagree on it are refused.
 evaluate.rows_path: one <shard>.quality.npz per shard with `filename`, `epochs` and, per view, "<model_key>/<layer>" ->
 float64 [epochs, rows, 2] = (a2, b2) -- an outlier or low-margin filter downstream.  One process, one GPU.
 """
@@ -131,6 +134,15 @@ def load_states(args, epochs):
                 raise ValueError("clustering cache {}: view {} is still in its warm-up, count = {} < {}*K = {}: its labels are "
                                  "random draws, train it further first".format(path, '/'.join(key[1:]), count, rounds, rounds * K))
         states[e] = saved
+    # one set of rows serves every listed epoch: they have to agree on the space the rows are judged in
+    first = next(iter(states.values()), {})
+    for e, saved in states.items():
+        for key in set(first) | set(saved):
+            a, b = (_find(first, key) or {}).get('whiten_std'), (_find(saved, key) or {}).get('whiten_std')
+            same = (a is None and b is None) or (a is not None and b is not None and a.shape == b.shape and a.tobytes() == b.tobytes())
+            if not same:
+                raise ValueError("the clustering caches of epochs {} and {} disagree on whiten_std of view {}: evaluate them in "
+                                 "separate runs".format(epochs[0], e, '/'.join(key[1:])))
     return states
 
 
@@ -168,6 +180,13 @@ def evaluate(args):
             cl[e, v] = km.to(dev)
     row_bytes = 4 * sum(view_dims.values())
     groups = rc._RowGroups(args, paths, sizes, row_bytes, rc._device_budget(args), view_dims)
+    # a whitened run's centres live in x / whiten_std space: the rows are divided on their way to the device, like the run's own
+    stds = OrderedDict((v, (_find(states[epochs[0]], v) or {}).get('whiten_std')) for v in view_dims)
+    for v, s_ in stds.items():
+        if s_ is not None and s_.shape != (view_dims[v],):
+            raise ValueError("whiten_std of view {} has shape {}, the rows have {} columns".format('/'.join(v[1:]), s_.shape, view_dims[v]))
+    if any(s_ is not None for s_ in stds.values()):
+        groups.set_whitening(stds)
     acc = OrderedDict((key, np.zeros((km.centers.shape[0], QUALITY_COLS), np.float64)) for key, km in cl.items())
     if rows_path is not None:
         Path(rows_path).mkdir(parents=True, exist_ok=True)
@@ -193,6 +212,9 @@ def evaluate(args):
     for (e, v), km in cl.items():
         centers, counts, count, _fb = km.state_arrays()
         rep = compose(acc[e, v], centers, counts, count, km.reinit)
+        if stds[v] is not None:  # every figure of this view is in whitened space; a zero-variance column's divisor is exactly 1
+            rep['whitened'] = True
+            rep['zero_variance_columns'] = int((stds[v] == np.float32(1.0)).sum())
         report['views'].setdefault('/'.join(v[1:]), OrderedDict())[str(e)] = rep
     print(format_report(report))
     if out_path is not None:

@@ -97,7 +97,7 @@ def _attrs_of(obj):
         dt = dict(obj.get_attrs())
     else:
         dt = dict(vars(obj))
-    for key in ('centers', 'counts'):
+    for key in ('centers', 'counts') + (('whiten_std',) if dt.get('whiten_std') is not None else ()):
         v = dt[key]
         if hasattr(v, 'detach'):
             v = v.detach().cpu().numpy()
@@ -136,9 +136,11 @@ def _read_cache(path):
         return None
 
 
-def save_clusterings(args, epoch, cl):
+def save_clusterings(args, epoch, cl, whiten_std=None):
     """torch.save of {model_key: {layer: attrs}} -- the reference's file and layout (its save_scheme_ver2 form,
-    run_clustering.py:110-116: plain attrs instead of pickled objects, so either side can read it)."""
+    run_clustering.py:110-116: plain attrs instead of pickled objects, so either side can read it).
+    whiten_std: {view: fp32 [d]} of a whitened run (clustering.whiten) -> 'whiten_std' beside '_kind': the centres live in
+    x / whiten_std space, and whoever assigns or judges rows with them divides by it first.  An unwhitened run adds no key."""
     import torch
     path = _cache_path(args, epoch)
     print("saving clustering cache to: {}".format(path))
@@ -147,8 +149,70 @@ def save_clusterings(args, epoch, cl):
     for (kind, mk, layer), km in cl.items():
         dt = km.get_attrs_plain()
         dt['_kind'] = kind
+        if whiten_std and whiten_std.get((kind, mk, layer)) is not None:
+            dt['whiten_std'] = np.ascontiguousarray(whiten_std[kind, mk, layer], np.float32)
         nested.setdefault(mk, OrderedDict())[layer] = dt
     torch.save(nested, str(path))
+
+
+def check_whiten(args, world_size):
+    """clustering.whiten needs every row of a view on the rank that takes its moments: refused (ValueError) when several GPUs
+    partition the ROWS (clustering.multi_gpu = striped / reference / rows).  Pure: no device, no file."""
+    if not args.clustering.whiten:
+        return
+    mode = multi_gpu_mode(args)
+    if int(world_size) > 1 and mode != 'views':
+        raise ValueError("clustering.whiten with clustering.multi_gpu={} on {} GPUs: the rows are partitioned over the ranks and "
+                         "the column moments are not merged across them; use clustering.multi_gpu=views or one GPU".format(
+                             mode, world_size))
+
+
+def cached_whitening(args):
+    """(cache file, {(model_key, layer): whiten_std}) of the cache that clustering.cached_epoch names -- the file
+    load_clusterings will load -- or (None, {}) when there is none.  The cache is authoritative: its std is used as it is, so
+    new shards are assigned in the space the centres were trained in."""
+    epoch = args.clustering.cached_epoch
+    if not isinstance(epoch, int):
+        return None, {}
+    path = _cache_path(args, epoch)
+    if not path.is_file() and args.clustering.load_cache_from_shard_subset:
+        path = _subset_cache(args, epoch)
+    if path is None or not path.is_file():
+        return None, {}
+    saved = _read_cache(path)
+    if not saved:
+        return None, {}
+    return path, {key[1:]: dt['whiten_std'] for key, dt in saved.items() if dt.get('whiten_std') is not None}
+
+
+def compute_whitening(groups):
+    """The stats pre-pass of clustering.whiten: one pass over the row groups, per view one acav_colstats call per group with
+    the group's shards as segments, merged in shard order (whiten.ColumnMoments) -> {view: std fp32 [d]}.  Resident data: the
+    pass uploads the rows training keeps using.  Streamed data: one extra read of every shard."""
+    from .whiten import ColumnMoments
+    if groups.streamed:
+        print("whitening: the column moments take one extra read of every shard ({} groups stream)".format(len(groups.groups)))
+    moments = OrderedDict()
+    for _gi, table, rows in groups.iterate():
+        prefix = [0]
+        for stem, ids in table.shard_rows.items():  # the group's shards in shard order, each a run of consecutive table rows
+            if not ids:
+                continue
+            if ids[0] != prefix[-1] or ids[-1] - ids[0] != len(ids) - 1:
+                raise RuntimeError("shard {} is not a run of consecutive table rows".format(stem))
+            prefix.append(ids[-1] + 1)
+        for v, x in rows.items():
+            if v not in moments:
+                moments[v] = ColumnMoments(x.shape[1], x.device)
+            if len(prefix) > 1 and x.shape[1] > 0:
+                moments[v].update(x[:prefix[-1]], prefix)
+        del rows
+    stds = OrderedDict()
+    for v, cm in moments.items():
+        stds[v] = cm.std()
+        print("whitening {}: {} rows, {} zero-variance columns of {} (divided by 1), std min {:.6g} max {:.6g}".format(
+            '/'.join(v[1:]), cm.n, cm.zero_columns, cm.d, float(stds[v].min()) if cm.d else 0.0, float(stds[v].max()) if cm.d else 0.0))
+    return stds
 
 
 class _RowGroups:
@@ -190,7 +254,34 @@ class _RowGroups:
             print("streaming {} shards in {} groups (device budget {:.1f} MB, data {:.1f} MB)".format(
                 len(paths), len(self.groups), budget / 1e6, total / 1e6))
         self._resident = None
+        self.whiten_std = None  # clustering.whiten: {view: fp32 [d]}, set_whitening()
         self.t_wait = self.t_upload = 0.0  # main-thread seconds waiting for the loader / copying host -> device (tools/bench_streamed.py)
+
+    def _upload(self, v, m, dev):
+        """host rows of view v -> device: the ONE way feature rows reach the device.  With a std set for the view
+        (clustering.whiten) the copy is divided by it right there (whiten.whiten_): training, the assign sweep and evaluate see
+        whitened rows, the host arrays of the table stay raw."""
+        import time
+        import torch
+        t0 = time.perf_counter()
+        t = torch.from_numpy(np.ascontiguousarray(m)).to(dev)
+        std = None if self.whiten_std is None else self.whiten_std.get(v)
+        if std is not None and t.shape[0] and t.shape[1]:
+            from .whiten import whiten_
+            whiten_(t, std)
+        self.t_upload += time.perf_counter() - t0
+        return t
+
+    def set_whitening(self, stds):
+        """{view: std} for every later upload.  Rows that are already resident on the device -- uploaded raw by the stats
+        pre-pass -- are divided in place here, exactly once."""
+        assert self.whiten_std is None, "the whitening of a run is set once"
+        from .whiten import whiten_
+        self.whiten_std = dict(stds)
+        if self._resident is not None:
+            for v, x in self._resident[1].items():
+                if self.whiten_std.get(v) is not None and x.shape[0] and x.shape[1]:
+                    whiten_(x, self.whiten_std[v])
 
     @property
     def streamed(self):
@@ -275,11 +366,7 @@ class _RowGroups:
         def up(v, m):
             if views is not None and v not in views:
                 return torch.empty((m.shape[0], 0))
-            import time
-            t0 = time.perf_counter()
-            t = torch.from_numpy(np.ascontiguousarray(m)).to(dev)
-            self.t_upload += time.perf_counter() - t0
-            return t
+            return self._upload(v, m, dev)
 
         from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(max_workers=1) as pool:
@@ -328,11 +415,7 @@ class _RowGroups:
         def up(v, m):
             if views is not None and v not in views:
                 return torch.empty((m.shape[0], 0))
-            import time
-            t0 = time.perf_counter()
-            t = torch.from_numpy(np.ascontiguousarray(m)).to(dev)
-            self.t_upload += time.perf_counter() - t0
-            return t
+            return self._upload(v, m, dev)
 
         if not self.streamed:
             if self._resident is None:
@@ -485,7 +568,7 @@ def train_clusters(args, probe, groups, shard_stems=()):
             from ..parallel import broadcast_states
             broadcast_states(cl)
         if rank == 0:
-            save_clusterings(args, epoch, cl)
+            save_clusterings(args, epoch, cl, groups.whiten_std)
     return cl
 
 
@@ -568,7 +651,7 @@ def _train_clusters_planned(args, cl, groups, pre, epochs, b, mode, shard_stems)
         for i, km in enumerate(kms):
             km.broadcast_state_from(trainers[i], comm_slot=i)
         if rank == 0:
-            save_clusterings(args, epoch, cl)
+            save_clusterings(args, epoch, cl, groups.whiten_std)
     return cl
 
 
@@ -615,9 +698,15 @@ def assign_clusters(args, groups, cl, shard_names):
 
 
 def run_clustering(args):
+    rank, w = world()
+    check_whiten(args, w)
+    # a cached run (assign-only, resume_training, a cache of a shard subset) whitens with the cache's std or not at all
+    cache_file, cached_std = cached_whitening(args)
+    if args.clustering.whiten and cache_file is not None and not cached_std:
+        raise ValueError("clustering.whiten=True, but the clustering cache {} holds no whiten_std: its centres were trained on "
+                         "unwhitened rows".format(cache_file))
     paths = [Path(p) for p in sorted(io.brace_expand(args.data.path))]
     sizes = io.shard_sizes_from_meta(paths, args.data.meta.path, use_cache=True)
-    rank, w = world()
     if args.data.meta.path is not None and rank == 0:  # the reference's meta_cache.pkl in the meta dir: read above, kept up to date
         cache_path = Path(args.data.meta.path) / 'meta_cache.pkl'
         try:
@@ -650,6 +739,19 @@ def run_clustering(args):
     # reference / rows mode: a rank reads, holds and labels its own shards only (rank::world) -- training included
     groups = _RowGroups(args, paths[rank::w] if partitioned else paths, sizes, row_bytes, _device_budget(args), view_dims)
     groups.all_sizes = sizes  # metadata sizes of ALL shards (the loader length of a partitioned run is computed over all of them)
+    if cached_std:  # the space the cached centres were trained in; nothing is recomputed
+        if partitioned:
+            raise ValueError("the clustering cache {} is whitened: clustering.multi_gpu={} partitions the rows, use views".format(
+                cache_file, multi_gpu_mode(args)))
+        stds = OrderedDict((v, cached_std.get(v[1:])) for v in view_dims)
+        for v, s in stds.items():
+            if s is not None and s.shape != (view_dims[v],):
+                raise ValueError("whiten_std of view {} in {} has shape {}, the rows have {} columns".format(
+                    '/'.join(v[1:]), cache_file, s.shape, view_dims[v]))
+        print("whitening with the std of the clustering cache {}".format(cache_file))
+        groups.set_whitening(stds)
+    elif args.clustering.whiten:
+        groups.set_whitening(compute_whitening(groups))
     cl = train_clusters(args, probe, groups, [p.stem for p in paths])
     mine = [p.stem for p in paths][rank::w]  # assign: shards strided over ranks (mps/distributed.py:439)
     return assign_clusters(args, groups, cl, mine)

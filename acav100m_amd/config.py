@@ -125,6 +125,12 @@ CLUSTERING_DEFAULTS = {
         # 'rows': a LARGE-BATCH operating point, not the reference's run: batch_size rows of every GPU's own shards per step
         #   (global batch N x batch_size), ceil(epochs / N) epochs -- N x N fewer SGD steps than 'reference' (64 x at N = 8).
         'multi_gpu': 'views',
+        # ours: divide every feature column by its standard deviation over all rows before clustering (scipy.cluster.vq.whiten,
+        # which every clusterer of the reference's correspondence_retrieval/code/clustering.py:54-63 runs first; no centring).
+        # One stats pass over the rows before the first epoch (streamed data: one extra read of every shard); the cache file keeps
+        # the divisors as 'whiten_std', and a cached run (clustering.cached_epoch) uses the cache's, whatever this switch says.
+        # Several GPUs: clustering.multi_gpu=views only.  False (default): every file stays what it is without the switch.
+        'whiten': False,
     },
     'debug': False,
 }

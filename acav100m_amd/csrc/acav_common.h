@@ -103,6 +103,12 @@ struct DevBuf {
     template <class T> T *as() const { return static_cast<T *>(p); }
 };
 
+// Declared after the scratch DevBufs of one call: the stream is idle before they go back to the pool.
+struct StreamDrain {
+    hipStream_t st;
+    ~StreamDrain() { (void)hipStreamSynchronize(st); }
+};
+
 // Returns a device pointer for `src` (n bytes): src itself when it already is one, otherwise a
 // staged copy in `stage` (async on stream).
 int to_device(const void *src, size_t bytes, DevBuf &stage, hipStream_t stream, const void **out);

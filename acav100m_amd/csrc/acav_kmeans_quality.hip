@@ -207,11 +207,6 @@ __global__ __launch_bounds__(256) void k_quality_fold(const double *__restrict__
     out[i] = s;
 }
 
-struct StreamDrain {  // declared after the scratch buffers of a call: the stream is idle before they go back to the pool
-    hipStream_t st;
-    ~StreamDrain() { (void)hipStreamSynchronize(st); }
-};
-
 }  // namespace
 
 ACAV_EXPORT int acav_kmeans_quality_plan(int64_t n, int k, int cus, int64_t *out)
