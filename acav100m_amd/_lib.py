@@ -46,6 +46,9 @@ SIGNATURES = {
     "acav_colstats": [i32, vp, i64, i32, vp, i32, vp, vp],
     "acav_colstats_plan": [i64, i32, i32, i32, C.POINTER(i64)],
     "acav_rows_scale": [i32, vp, i64, i32, vp, vp],
+    "acav_rows_scatter": [i32, vp, i64, i32, vp, i32, vp, vp, vp, vp],
+    "acav_rows_scatter_plan": [i64, i32, i32, C.POINTER(i64)],
+    "acav_rows_project": [i32, vp, i64, i32, vp, vp, i32, vp, vp],
     "acav_kmeans_apply_update": [vp, vp, i64, vp, f64],
     "acav_kmeans_sync": [vp],
     "acav_kmeans_shape": [vp, C.POINTER(i32), C.POINTER(i32)],
@@ -121,7 +124,8 @@ _lib = None
 # entry points that are necessarily the first device call of a handle's life (everything else needs a handle):
 # calling one marks the HIP runtime as initialised for acav100m_amd.configure_runtime()
 _FIRST_DEVICE_CALLS = ("acav_device_count", "acav_device_info", "acav_kmeans_create", "acav_mi_create",
-                       "acav_contrastive_create", "acav_comm_init", "acav_mt_stream_fill", "acav_colstats", "acav_rows_scale")
+                       "acav_contrastive_create", "acav_comm_init", "acav_mt_stream_fill", "acav_colstats", "acav_rows_scale",
+                       "acav_rows_scatter", "acav_rows_project")
 _device_touched = False
 
 

@@ -24,6 +24,9 @@ evaluates every listed epoch on them while they are on the device.  Writes no as
 A cache that holds `whiten_std` (a `cluster --clustering.whiten=True` run) has its rows divided by it on their way to the
 device, like the run itself: the report and the rows_path values are then in whitened space, and the view's report carries
 "whitened": true and "zero_variance_columns" (divisors that are exactly 1).  Epochs that disagree on it are refused.
+A cache that holds `pca_components` (a `cluster --clustering.pca_dim=P` run) has its rows projected through the same helper,
+after the division: the view is judged in projected space and its report carries "pca_dim" and
+"pca_explained_variance_ratio" (the kept share of the total variance).  Epochs that disagree on a view's projection are refused.
 evaluate.rows_path: one <shard>.quality.npz per shard with `filename`, `epochs` and, per view, "<model_key>/<layer>" ->
 float64 [epochs, rows, 2] = (a2, b2) -- an outlier or low-margin filter downstream.  One process, one GPU.
 """
@@ -143,6 +146,12 @@ def load_states(args, epochs):
             if not same:
                 raise ValueError("the clustering caches of epochs {} and {} disagree on whiten_std of view {}: evaluate them in "
                                  "separate runs".format(epochs[0], e, '/'.join(key[1:])))
+            a, b = rc._pca_of(_find(first, key)), rc._pca_of(_find(saved, key))
+            same = (a is None and b is None) or (a is not None and b is not None and all(
+                np.shape(a[k]) == np.shape(b[k]) and np.asarray(a[k]).tobytes() == np.asarray(b[k]).tobytes() for k in a))
+            if not same:
+                raise ValueError("the clustering caches of epochs {} and {} disagree on the pca projection of view {}: evaluate "
+                                 "them in separate runs".format(epochs[0], e, '/'.join(key[1:])))
     return states
 
 
@@ -169,10 +178,17 @@ def evaluate(args):
         raise ValueError("none of the {} shards of {} could be read".format(len(paths), args.data.path))
     view_dims = OrderedDict((v, m.shape[1]) for v, m in probe.views.items())
     dev = rc._device(args)
+    # a projected run's centres live in the space of its components (after the division, if there is one)
+    fits = OrderedDict((v, rc._pca_of(_find(states[epochs[0]], v))) for v in view_dims)
+    for v, f in fits.items():
+        if f is not None and (f['components'].ndim != 2 or f['components'].shape[1] != view_dims[v] or f['mean'].shape != (view_dims[v],)):
+            raise ValueError("pca_components of view {} has shape {}, the rows have {} columns".format(
+                '/'.join(v[1:]), f['components'].shape, view_dims[v]))
     cl = OrderedDict()
     for e, saved in states.items():
         for v, d in view_dims.items():
             dt = _find(saved, v)
+            d = d if fits[v] is None else fits[v]['components'].shape[0]
             if dt is None or dt['centers'].shape[1] != d:
                 raise ValueError("the clustering cache of epoch {} lacks view {} (width {})".format(e, '/'.join(v[1:]), d))
             km = KMeans.load(dt)
@@ -187,6 +203,8 @@ def evaluate(args):
             raise ValueError("whiten_std of view {} has shape {}, the rows have {} columns".format('/'.join(v[1:]), s_.shape, view_dims[v]))
     if any(s_ is not None for s_ in stds.values()):
         groups.set_whitening(stds)
+    if any(f is not None for f in fits.values()):
+        groups.set_projection(fits)
     acc = OrderedDict((key, np.zeros((km.centers.shape[0], QUALITY_COLS), np.float64)) for key, km in cl.items())
     if rows_path is not None:
         Path(rows_path).mkdir(parents=True, exist_ok=True)
@@ -215,6 +233,10 @@ def evaluate(args):
         if stds[v] is not None:  # every figure of this view is in whitened space; a zero-variance column's divisor is exactly 1
             rep['whitened'] = True
             rep['zero_variance_columns'] = int((stds[v] == np.float32(1.0)).sum())
+        if fits[v] is not None:  # every figure of this view is in projected space
+            tv = float(fits[v]['total_variance'])
+            rep['pca_dim'] = int(fits[v]['components'].shape[0])
+            rep['pca_explained_variance_ratio'] = float(fits[v]['explained_variance'].sum() / tv) if tv > 0 else float('nan')
         report['views'].setdefault('/'.join(v[1:]), OrderedDict())[str(e)] = rep
     print(format_report(report))
     if out_path is not None:

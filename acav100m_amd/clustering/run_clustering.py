@@ -36,11 +36,12 @@ def _cache_path(args, epoch):
     return Path(args.data.output.path) / "cache_epoch_{}_{}".format(epoch, Path(args.data.path).name)
 
 
-def init_clusterings(args, table):
-    """run_clustering.py:32-52 -- one KMeans per view, created in view order (RNG order)."""
+def init_clusterings(args, table, widths=None):
+    """run_clustering.py:32-52 -- one KMeans per view, created in view order (RNG order).  widths: {view: columns} of the views
+    that are not trained at the width of their stored rows (clustering.pca_dim: a projected view has d = p)."""
     cl = OrderedDict()
     for view, mat in table.views.items():
-        cl[view] = KMeans(args, mat.shape[1], args.clustering.ncentroids)
+        cl[view] = KMeans(args, (widths or {}).get(view, mat.shape[1]), args.clustering.ncentroids)
     return _to_device(args, cl)
 
 
@@ -52,7 +53,7 @@ def _to_device(args, cl):
     return cl
 
 
-def load_clusterings(args, table):
+def load_clusterings(args, table, widths=None):
     """run_clustering.py:55-107: resume from cache_epoch_{e}_{name} (or a cache trained on a subset of
     these shards) when --clustering.cached_epoch is set."""
     epoch = args.clustering.cached_epoch
@@ -75,7 +76,7 @@ def load_clusterings(args, table):
             if saved is not None:
                 print("clustering cache features does not match with the given models")
         print("no clustering cache found.")
-    return init_clusterings(args, table), False
+    return init_clusterings(args, table, widths), False
 
 
 def _subset_cache(args, epoch):
@@ -102,7 +103,24 @@ def _attrs_of(obj):
         if hasattr(v, 'detach'):
             v = v.detach().cpu().numpy()
         dt[key] = np.ascontiguousarray(v, np.float32)
+    if dt.get('pca_components') is not None:
+        for key, kind in zip(PCA_KEYS, (np.float32, np.float32, np.float64, np.float64)):
+            v = dt[key]
+            if hasattr(v, 'detach'):
+                v = v.detach().cpu().numpy()
+            dt[key] = np.ascontiguousarray(v, kind) if key != 'pca_total_variance' else np.float64(v)
     return dt
+
+
+# the cache keys of a projected view (clustering.pca_dim): fp32 [d], fp32 [p, d], f64 [p], f64
+PCA_KEYS = ('pca_mean', 'pca_components', 'pca_explained_variance', 'pca_total_variance')
+
+
+def _pca_of(dt):
+    """the projection a cached view's attrs hold -> dict(mean, components, explained_variance, total_variance) or None"""
+    if dt is None or dt.get('pca_components') is None:
+        return None
+    return {key[4:]: dt[key] for key in PCA_KEYS}
 
 
 def _read_cache(path):
@@ -136,11 +154,14 @@ def _read_cache(path):
         return None
 
 
-def save_clusterings(args, epoch, cl, whiten_std=None):
+def save_clusterings(args, epoch, cl, whiten_std=None, pca=None):
     """torch.save of {model_key: {layer: attrs}} -- the reference's file and layout (its save_scheme_ver2 form,
     run_clustering.py:110-116: plain attrs instead of pickled objects, so either side can read it).
     whiten_std: {view: fp32 [d]} of a whitened run (clustering.whiten) -> 'whiten_std' beside '_kind': the centres live in
-    x / whiten_std space, and whoever assigns or judges rows with them divides by it first.  An unwhitened run adds no key."""
+    x / whiten_std space, and whoever assigns or judges rows with them divides by it first.  An unwhitened run adds no key.
+    pca: {view: dict(mean, components, explained_variance, total_variance) | None} of a projected run (clustering.pca_dim) ->
+    PCA_KEYS beside it: the centres live in the space of acav_rows_project's output (after the division, if there is one).  An
+    unprojected view or run adds no key."""
     import torch
     path = _cache_path(args, epoch)
     print("saving clustering cache to: {}".format(path))
@@ -151,6 +172,12 @@ def save_clusterings(args, epoch, cl, whiten_std=None):
         dt['_kind'] = kind
         if whiten_std and whiten_std.get((kind, mk, layer)) is not None:
             dt['whiten_std'] = np.ascontiguousarray(whiten_std[kind, mk, layer], np.float32)
+        if pca and pca.get((kind, mk, layer)) is not None:
+            f = pca[kind, mk, layer]
+            dt['pca_mean'] = np.ascontiguousarray(f['mean'], np.float32)
+            dt['pca_components'] = np.ascontiguousarray(f['components'], np.float32)
+            dt['pca_explained_variance'] = np.ascontiguousarray(f['explained_variance'], np.float64)
+            dt['pca_total_variance'] = np.float64(f['total_variance'])
         nested.setdefault(mk, OrderedDict())[layer] = dt
     torch.save(nested, str(path))
 
@@ -167,10 +194,25 @@ def check_whiten(args, world_size):
                              mode, world_size))
 
 
-def cached_whitening(args):
-    """(cache file, {(model_key, layer): whiten_std}) of the cache that clustering.cached_epoch names -- the file
-    load_clusterings will load -- or (None, {}) when there is none.  The cache is authoritative: its std is used as it is, so
-    new shards are assigned in the space the centres were trained in."""
+def check_pca(args, world_size):
+    """clustering.pca_dim needs every row of a view on the rank that takes its scatter matrix: refused (ValueError) when several
+    GPUs partition the ROWS (clustering.multi_gpu = striped / reference / rows), and when it is not a positive integer.  Pure:
+    no device, no file."""
+    dim = args.clustering.pca_dim
+    if dim is None:
+        return
+    if isinstance(dim, bool) or not isinstance(dim, int) or dim < 1:
+        raise ValueError("clustering.pca_dim must be a positive integer or None, not {!r}".format(dim))
+    mode = multi_gpu_mode(args)
+    if int(world_size) > 1 and mode != 'views':
+        raise ValueError("clustering.pca_dim with clustering.multi_gpu={} on {} GPUs: the rows are partitioned over the ranks and "
+                         "the scatter matrices are not merged across them; use clustering.multi_gpu=views or one GPU".format(
+                             mode, world_size))
+
+
+def _cached_attrs(args):
+    """(cache file, {(kind, model_key, layer): attrs}) of the cache that clustering.cached_epoch names -- the file
+    load_clusterings will load -- or (None, {}) when there is none"""
     epoch = args.clustering.cached_epoch
     if not isinstance(epoch, int):
         return None, {}
@@ -182,7 +224,87 @@ def cached_whitening(args):
     saved = _read_cache(path)
     if not saved:
         return None, {}
+    return path, saved
+
+
+def cached_whitening(args, cached=None):
+    """(cache file, {(model_key, layer): whiten_std}) of the cache that clustering.cached_epoch names -- the file
+    load_clusterings will load -- or (None, {}) when there is none.  The cache is authoritative: its std is used as it is, so
+    new shards are assigned in the space the centres were trained in."""
+    path, saved = cached if cached is not None else _cached_attrs(args)
     return path, {key[1:]: dt['whiten_std'] for key, dt in saved.items() if dt.get('whiten_std') is not None}
+
+
+def cached_projection(args, cached=None):
+    """(cache file, {(model_key, layer): projection}) of that cache, like cached_whitening: nothing is recomputed.  Raises the two
+    ValueErrors of a cached run that names the file: clustering.pca_dim set against a cache without the keys, and a pca_dim
+    that disagrees with the cached p."""
+    path, saved = cached if cached is not None else _cached_attrs(args)
+    found = {key[1:]: _pca_of(dt) for key, dt in saved.items() if _pca_of(dt) is not None}
+    dim = args.clustering.pca_dim
+    if dim is not None and path is not None:
+        if not found:
+            raise ValueError("clustering.pca_dim={}, but the clustering cache {} holds no pca_components: its centres were trained "
+                             "on unprojected rows".format(dim, path))
+        for key, f in found.items():
+            if f['components'].shape[0] != dim:
+                raise ValueError("clustering.pca_dim={}, but view {} of the clustering cache {} was projected to {} columns".format(
+                    dim, '/'.join(key), path, f['components'].shape[0]))
+    return path, found
+
+
+def _shard_prefix(table):
+    """the row offsets of a group's non-empty shards in shard order, each a run of consecutive table rows"""
+    prefix = [0]
+    for stem, ids in table.shard_rows.items():
+        if not ids:
+            continue
+        if ids[0] != prefix[-1] or ids[-1] - ids[0] != len(ids) - 1:
+            raise RuntimeError("shard {} is not a run of consecutive table rows".format(stem))
+        prefix.append(ids[-1] + 1)
+    return prefix
+
+
+def compute_pca(groups, dim):
+    """The pre-pass of clustering.pca_dim, after the whitening is set: one pass over the row groups, per view one
+    acav_rows_scatter call per group with the group's shards as segments, into float64 accumulators on the device
+    (pca.ScatterMoments) -> {view: dict(mean, components, explained_variance, total_variance) | None}.  The shift is the
+    fp32-rounded column mean of the view's first non-empty shard (one ColumnMoments.update on it).  A view with d <= dim is left
+    alone (None).  Resident data: the pass uploads the rows training keeps using.  Streamed data: one extra read of every shard."""
+    from .pca import ScatterMoments, components_from_scatter
+    from .whiten import ColumnMoments
+    if groups.streamed:
+        print("pca: the scatter matrices take one extra read of every shard ({} groups stream)".format(len(groups.groups)))
+    moments, widths = OrderedDict(), OrderedDict()
+    for _gi, table, rows in groups.iterate():
+        prefix = _shard_prefix(table)
+        for v, x in rows.items():
+            widths[v] = x.shape[1]
+            if x.shape[1] <= dim or len(prefix) < 2:
+                continue
+            if v not in moments:
+                cm = ColumnMoments(x.shape[1], x.device)
+                cm.update(x[prefix[0]:prefix[1]])
+                moments[v] = ScatterMoments(x.shape[1], cm.mean.astype(np.float32), x.device)
+            moments[v].update(x[:prefix[-1]], prefix)
+        del rows
+    fits = OrderedDict()
+    for v, d in widths.items():
+        name = '/'.join(v[1:])
+        sm = moments.pop(v, None)
+        if sm is None:
+            fits[v] = None
+            print("pca {}: {} columns <= pca_dim {}: left alone".format(name, d, dim))
+            continue
+        n, mean, S = sm.finish()
+        del sm
+        f = fits[v] = components_from_scatter(n, mean, S, dim, what="view {}".format(name))
+        w = f['explained_variance']
+        gap = float(((w[:-1] - w[1:]) / w[:-1]).min()) if len(w) > 1 and w[-2] > 0 else float('nan')
+        ratio = float(w.sum() / f['total_variance']) if f['total_variance'] > 0 else float('nan')
+        print("pca {}: {} rows, {} of {} columns, explained variance ratio {:.6g}, smallest relative gap between kept "
+              "eigenvalues {:.3g}".format(name, n, dim, d, ratio, gap))
+    return fits
 
 
 def compute_whitening(groups):
@@ -194,13 +316,7 @@ def compute_whitening(groups):
         print("whitening: the column moments take one extra read of every shard ({} groups stream)".format(len(groups.groups)))
     moments = OrderedDict()
     for _gi, table, rows in groups.iterate():
-        prefix = [0]
-        for stem, ids in table.shard_rows.items():  # the group's shards in shard order, each a run of consecutive table rows
-            if not ids:
-                continue
-            if ids[0] != prefix[-1] or ids[-1] - ids[0] != len(ids) - 1:
-                raise RuntimeError("shard {} is not a run of consecutive table rows".format(stem))
-            prefix.append(ids[-1] + 1)
+        prefix = _shard_prefix(table)
         for v, x in rows.items():
             if v not in moments:
                 moments[v] = ColumnMoments(x.shape[1], x.device)
@@ -255,12 +371,14 @@ class _RowGroups:
                 len(paths), len(self.groups), budget / 1e6, total / 1e6))
         self._resident = None
         self.whiten_std = None  # clustering.whiten: {view: fp32 [d]}, set_whitening()
+        self.pca = None  # clustering.pca_dim: {view: projection} of the projected views, set_projection()
         self.t_wait = self.t_upload = 0.0  # main-thread seconds waiting for the loader / copying host -> device (tools/bench_streamed.py)
 
     def _upload(self, v, m, dev):
         """host rows of view v -> device: the ONE way feature rows reach the device.  With a std set for the view
         (clustering.whiten) the copy is divided by it right there (whiten.whiten_): training, the assign sweep and evaluate see
-        whitened rows, the host arrays of the table stay raw."""
+        whitened rows, the host arrays of the table stay raw.  With a projection set for the view (clustering.pca_dim) the
+        whitened copy is projected (pca.project) and dropped: what comes back is [rows, p]."""
         import time
         import torch
         t0 = time.perf_counter()
@@ -269,8 +387,26 @@ class _RowGroups:
         if std is not None and t.shape[0] and t.shape[1]:
             from .whiten import whiten_
             whiten_(t, std)
+        f = None if self.pca is None else self.pca.get(v)
+        if f is not None and t.shape[1]:
+            from .pca import project
+            t = project(t, f['mean'], f['components'])
         self.t_upload += time.perf_counter() - t0
         return t
+
+    def set_projection(self, fits):
+        """{view: projection | None} for every later upload.  Rows that are already resident on the device -- uploaded (and
+        whitened) at full width by the pre-pass -- are replaced by their projection here, exactly once and one view at a time:
+        the peak is one extra view."""
+        assert self.pca is None, "the projection of a run is set once"
+        from .pca import project
+        self.pca = {v: f for v, f in fits.items() if f is not None}
+        if self._resident is not None:
+            on_dev = self._resident[1]
+            for v in list(on_dev):
+                f = self.pca.get(v)
+                if f is not None and on_dev[v].shape[1]:
+                    on_dev[v] = project(on_dev[v], f['mean'], f['components'])
 
     def set_whitening(self, stds):
         """{view: std} for every later upload.  Rows that are already resident on the device -- uploaded raw by the stats
@@ -482,7 +618,9 @@ def _device_budget(args):
 
 def train_clusters(args, probe, groups, shard_stems=()):
     import torch
-    cl, loaded = load_clusterings(args, probe)
+    # a projected view (clustering.pca_dim) trains at d = p
+    widths = {v: f['components'].shape[0] for v, f in (groups.pca or {}).items()}
+    cl, loaded = load_clusterings(args, probe, widths)
     if loaded and not args.clustering.resume_training:
         return cl
     pre = args.clustering.cached_epoch if loaded else 0
@@ -568,7 +706,7 @@ def train_clusters(args, probe, groups, shard_stems=()):
             from ..parallel import broadcast_states
             broadcast_states(cl)
         if rank == 0:
-            save_clusterings(args, epoch, cl, groups.whiten_std)
+            save_clusterings(args, epoch, cl, groups.whiten_std, groups.pca)
     return cl
 
 
@@ -700,8 +838,12 @@ def assign_clusters(args, groups, cl, shard_names):
 def run_clustering(args):
     rank, w = world()
     check_whiten(args, w)
-    # a cached run (assign-only, resume_training, a cache of a shard subset) whitens with the cache's std or not at all
-    cache_file, cached_std = cached_whitening(args)
+    check_pca(args, w)
+    # a cached run (assign-only, resume_training, a cache of a shard subset) whitens with the cache's std or not at all, and
+    # projects with the cache's components or not at all
+    cached = _cached_attrs(args)
+    cache_file, cached_std = cached_whitening(args, cached)
+    _, cached_pca = cached_projection(args, cached)
     if args.clustering.whiten and cache_file is not None and not cached_std:
         raise ValueError("clustering.whiten=True, but the clustering cache {} holds no whiten_std: its centres were trained on "
                          "unwhitened rows".format(cache_file))
@@ -752,6 +894,20 @@ def run_clustering(args):
         groups.set_whitening(stds)
     elif args.clustering.whiten:
         groups.set_whitening(compute_whitening(groups))
+    if cached_pca:  # likewise
+        if partitioned:
+            raise ValueError("the clustering cache {} is projected: clustering.multi_gpu={} partitions the rows, use views".format(
+                cache_file, multi_gpu_mode(args)))
+        fits = OrderedDict((v, cached_pca.get(v[1:])) for v in view_dims)
+        for v, f in fits.items():
+            if f is not None and (f['components'].ndim != 2 or f['components'].shape[1] != view_dims[v]
+                                  or f['mean'].shape != (view_dims[v],)):
+                raise ValueError("pca_components of view {} in {} has shape {}, the rows have {} columns".format(
+                    '/'.join(v[1:]), cache_file, f['components'].shape, view_dims[v]))
+        print("projecting with the components of the clustering cache {}".format(cache_file))
+        groups.set_projection(fits)
+    elif args.clustering.pca_dim is not None and cache_file is None:
+        groups.set_projection(compute_pca(groups, int(args.clustering.pca_dim)))
     cl = train_clusters(args, probe, groups, [p.stem for p in paths])
     mine = [p.stem for p in paths][rank::w]  # assign: shards strided over ranks (mps/distributed.py:439)
     return assign_clusters(args, groups, cl, mine)

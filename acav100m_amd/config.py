@@ -131,6 +131,14 @@ CLUSTERING_DEFAULTS = {
         # the divisors as 'whiten_std', and a cached run (clustering.cached_epoch) uses the cache's, whatever this switch says.
         # Several GPUs: clustering.multi_gpu=views only.  False (default): every file stays what it is without the switch.
         'whiten': False,
+        # ours: project every view onto its pca_dim leading principal components before clustering (after the whitening, if on):
+        # sklearn.decomposition.PCA(n_components=pca_dim).fit_transform, the second half of the front-end of the reference's
+        # correspondence_retrieval/code/clustering.py:62-78 (pca.py: pca_features); no whiten=True scaling.  One scatter-matrix
+        # pass over the rows before the first epoch (streamed data: one extra read of every shard); a view that is not wider than
+        # pca_dim is left alone.  The cache file keeps 'pca_mean', 'pca_components', 'pca_explained_variance' and
+        # 'pca_total_variance', and a cached run (clustering.cached_epoch) projects with the cache's, refusing a pca_dim that
+        # disagrees.  Several GPUs: clustering.multi_gpu=views only.  None (default): every file stays what it is without the key.
+        'pca_dim': None,
     },
     'debug': False,
 }
