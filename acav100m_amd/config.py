@@ -173,6 +173,10 @@ SUBSET_DEFAULTS = {
     'batch': {'batch_size': 20, 'selection_size': 4, 'keep_unselected': True},
     'contrastive': {'num_epochs': 3, 'num_warmup_steps': 1, 'base_lr': 2e-4, 'train_batch_size': 128, 'test_batch_size': 128,
                     'cached_epoch': None, 'train_from_cached': False},
+    # the pca measures (pca, pca_ip, pca_cs, pca_l1, pca_l2: run_pca.py): every view is whitened (x / std(x, axis=0)) unless
+    #   whiten is False, then projected onto its `dim` leading principal components (None: the smallest view width), as the
+    #   front-end of the reference's correspondence_retrieval/code/clustering.py:54-78 does for them
+    'pca': {'dim': None, 'whiten': True},
     'measure_name': 'batch_mi',
     # celf_ratio: share of the picks of an exact-greedy measure taken by CELF lazy greedy (correspondence_retrieval args.py:32);
     #   0 = plain greedy.  batch_mi and contrastive refuse a nonzero value

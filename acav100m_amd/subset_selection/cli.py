@@ -52,6 +52,11 @@ def run(args):
     from .run_greedy import check_celf_ratio, check_weight_type
     check_weight_type(args.measure_name, args.clustering.weight_type)  # before any shard is read
     check_celf_ratio(args.measure_name, args.get('celf_ratio', 0))
+    from .run_pca import is_pca_measure
+    if is_pca_measure(args.measure_name):  # pca, pca_ip, pca_cs, pca_l1, pca_l2: they read feature shards (run_pca.py)
+        from .run_pca import check_pca_run, run_chunks_pca, run_single_pca
+        check_pca_run(args)  # a lockstep width is refused here too, before any shard is read
+        return run_single_pca(args) if args.chunk_size is None else run_chunks_pca(args)
     if args.measure_name == 'contrastive':
         from .run_contrastive import run_chunks_contrastive, run_single_contrastive
         return run_single_contrastive(args) if args.chunk_size is None else run_chunks_contrastive(args)

@@ -84,7 +84,8 @@ def run_single(args):
 def lockstep_supported(measure_name, celf_ratio=0):
     """computation.concurrent_chunks > 1: can this configuration run its chunks in lockstep?  Returns None, or raises
     ValueError with the reason.  Every measure of the registry can, except `contrastive` (it trains a model: there is no
-    greedy loop to share); a non-zero celf_ratio cannot yet (the lazy greedy has no lockstep form)."""
+    greedy loop to share) and the pca measures (one ranking per chunk: no loop either); a non-zero celf_ratio cannot yet (the
+    lazy greedy has no lockstep form)."""
     name = str(measure_name).lower()
     if not hasattr(get_measure(name), 'run_greedy_multi'):
         raise ValueError("computation.concurrent_chunks: the measure {!r} has no lockstep form; run its chunks one after "

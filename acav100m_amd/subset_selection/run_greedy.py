@@ -30,7 +30,7 @@ def check_weight_type(measure_name, weight_type):
 
 
 # the measures that cannot run CELF: the reference asserts efficient_greedy for celf_ratio and its batch measure drops the value
-NO_CELF_MEASURES = ('batch_mi', 'contrastive')
+NO_CELF_MEASURES = ('batch_mi', 'contrastive', 'pca', 'pca_ip', 'pca_cs', 'pca_l1', 'pca_l2')  # (pca*: one ranking, no greedy loop)
 
 
 def check_celf_ratio(measure_name, celf_ratio):
