@@ -49,6 +49,9 @@ SIGNATURES = {
     "acav_rows_scatter": [i32, vp, i64, i32, vp, i32, vp, vp, vp, vp],
     "acav_rows_scatter_plan": [i64, i32, i32, C.POINTER(i64)],
     "acav_rows_project": [i32, vp, i64, i32, vp, vp, i32, vp, vp],
+    "acav_rows_absmax": [i32, vp, i64, i32, C.POINTER(f32), vp],
+    "acav_lloyd_accumulate": [i32, vp, i64, i32, vp, i32, i32, vp, vp, vp],
+    "acav_lloyd_accumulate_plan": [vp, i32, i32, i32, C.POINTER(i64), vp, i64],
     "acav_pair_scores": [i32, vp, i32, i64, i32, vp, i32, i32, vp, vp],
     "acav_pair_scores_plan": [i64, i32, i32, i32, i32, C.POINTER(i64)],
     "acav_rank_desc": [i32, vp, i64, i64, vp, vp, vp],
@@ -128,7 +131,8 @@ _lib = None
 # calling one marks the HIP runtime as initialised for acav100m_amd.configure_runtime()
 _FIRST_DEVICE_CALLS = ("acav_device_count", "acav_device_info", "acav_kmeans_create", "acav_mi_create",
                        "acav_contrastive_create", "acav_comm_init", "acav_mt_stream_fill", "acav_colstats", "acav_rows_scale",
-                       "acav_rows_scatter", "acav_rows_project", "acav_pair_scores", "acav_rank_desc")
+                       "acav_rows_scatter", "acav_rows_project", "acav_pair_scores", "acav_rank_desc", "acav_rows_absmax",
+                       "acav_lloyd_accumulate")
 _device_touched = False
 
 

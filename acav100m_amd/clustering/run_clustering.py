@@ -14,6 +14,8 @@ Same observable behaviour as the reference:
   * lr = 0.1 ** (2 + epoch // 5), drop_last batches; several GPUs: clustering.multi_gpu (config.py) -- `views` keeps the
     one-GPU batch stream and epoch count, `reference` is the reference's own N-GPU stream with ceil(epochs / num_gpus) epochs
   * cache_epoch_{e}_{name} checkpoints, skip of already written shards, log_*.json manifest
+clustering.algorithm=lloyd (ours; clustering/lloyd.py) trains with batch k-means instead: train_clusters branches once, to
+_train_clusters_lloyd; the caches, cached_epoch, the assign sweep and `evaluate` are the ones above.
 """
 import math
 import pickle
@@ -24,6 +26,7 @@ import numpy as np
 
 from .. import shards as io
 from ..parallel import world
+from .lloyd import check_algorithm
 from .sgd_clustering import KMeans
 
 
@@ -208,6 +211,20 @@ def check_pca(args, world_size):
         raise ValueError("clustering.pca_dim with clustering.multi_gpu={} on {} GPUs: the rows are partitioned over the ranks and "
                          "the scatter matrices are not merged across them; use clustering.multi_gpu=views or one GPU".format(
                              mode, world_size))
+
+
+def check_cached_algorithm(args, cached=None):
+    """clustering.resume_training continues a cache with the algorithm that trained it: refused (ValueError) when the cache
+    clustering.cached_epoch names was trained by the other one ('algorithm' in its states; none: sgd).  No device."""
+    path, saved = cached if cached is not None else _cached_attrs(args)
+    if path is None or not args.clustering.resume_training:
+        return
+    want = args.clustering.algorithm or 'sgd'
+    for key, dt in saved.items():
+        have = dt.get('algorithm') or 'sgd'
+        if have != want:
+            raise ValueError("clustering.resume_training with clustering.algorithm={}, but view {} of the clustering cache {} was "
+                             "trained by {}: a run continues with the algorithm it started with".format(want, '/'.join(key[1:]), path, have))
 
 
 def _cached_attrs(args):
@@ -631,6 +648,8 @@ def train_clusters(args, probe, groups, shard_stems=()):
     # batch_size / N: that run is `clustering.multi_gpu=reference`, _train_clusters_planned.)
     epochs = int(args.clustering.epochs)
     b = int(args.data.batch_size)
+    if args.clustering.algorithm == 'lloyd':
+        return _train_clusters_lloyd(args, cl, groups, pre, epochs, loaded)
     print("training sgd kmeans for views: {}".format([v[1:] for v in cl]))
     if w > 1 and multi_gpu_mode(args) != 'views':
         return _train_clusters_planned(args, cl, groups, pre, epochs, b, multi_gpu_mode(args), shard_stems)
@@ -705,6 +724,86 @@ def train_clusters(args, probe, groups, shard_stems=()):
         if w > 1:  # state identical to the one-GPU run on every rank
             from ..parallel import broadcast_states
             broadcast_states(cl)
+        if rank == 0:
+            save_clusterings(args, epoch, cl, groups.whiten_std, groups.pca)
+    return cl
+
+
+def _train_clusters_lloyd(args, cl, groups, pre, iters, resumed):
+    """clustering.algorithm=lloyd: `iters` iterations of batch k-means per view (clustering/lloyd.py), each one pass over the row
+    groups with two sweeps per view -- the assign sweep and acav_lloyd_accumulate into int64 tables on the device -- and the centre
+    update on the host.  Before the first one, one read-once pass takes every view's largest magnitude (the scale of the fixed
+    point) and, for a fresh run, the initial centres: the rows generator.randperm(N)[:K], drawn view by view, read as the
+    front-ends deliver them.  The tables are integer sums, so resident and streamed rows give the same bytes.  N comes from the
+    metadata when the rows stream (like the batch plan of the SGD loop) and is checked against what the shards deliver.
+    Several GPUs (clustering.multi_gpu=views): every rank runs every view -- the result is a pure function of the rows, the ranks
+    end in the same state without an exchange -- and rank 0 writes the caches."""
+    import torch
+    from . import lloyd
+    rank, _w = world()
+    K = int(args.clustering.ncentroids)
+    print("training lloyd kmeans for views: {}".format([v[1:] for v in cl]))
+    if groups.streamed:
+        n_total = sum(int(groups.sizes[p.stem]) for p in groups.paths)
+    else:
+        (_gi, table, _rows), = list(groups.iterate(views=set()))  # (reads the shards; uploads nothing yet)
+        n_total = len(table)
+    if K > n_total:
+        raise ValueError("clustering.algorithm=lloyd: clustering.ncentroids={} initial centres cannot be {} distinct rows".format(K, n_total))
+    picks = OrderedDict()
+    if not resumed:
+        for v, km in cl.items():
+            picks[v] = km._generator.randperm(n_total)[:K]
+    absmax = OrderedDict((v, 0.0) for v in cl)
+    init = OrderedDict((v, np.zeros(km._shape, np.float32)) for v, km in cl.items())
+    base = 0
+    for _gi, _table, rows in groups.iterate():
+        n_g = next(iter(rows.values())).shape[0] if rows else 0
+        for v in cl:
+            x = rows[v]
+            absmax[v] = max(absmax[v], lloyd.rows_absmax(x))
+            if not resumed:
+                sel = np.flatnonzero((picks[v] >= base) & (picks[v] < base + n_g))
+                if len(sel):
+                    init[v][sel] = x[torch.from_numpy(picks[v][sel] - base).to(x.device)].cpu().numpy()
+        base += n_g
+        del rows
+    if base != n_total:
+        raise RuntimeError("the shards delivered {} rows, their metadata states {}: fix the metadata or drop the unreadable shards "
+                           "from the list".format(base, n_total))
+    shift = OrderedDict()
+    for v, km in cl.items():
+        try:
+            shift[v] = lloyd.fixed_point_shift(absmax[v], n_total)
+        except ValueError as exc:
+            raise ValueError("view {}: {}".format('/'.join(v[1:]), exc))
+        if not resumed:
+            km.to_lloyd(init[v])
+        print("lloyd {}: {} rows, {} centres, largest magnitude {:.6g}, fixed point 2^{}".format(
+            '/'.join(v[1:]), n_total, K, absmax[v], shift[v]))
+    prev = {v: {} for v in cl}  # {view: {row group: the labels of the previous iteration}}
+    done = OrderedDict((v, False) for v in cl)
+    for epoch in range(pre, pre + iters):
+        live = [v for v in cl if not done[v]]
+        if not live:
+            print("lloyd: every view has converged: cache_epoch_{} holds the final state".format(epoch - 1))
+            break
+        tables = {v: (None, None) for v in live}
+        changed = dict.fromkeys(live, 0)
+        for gi, _table, rows in groups.iterate(views=set(live)):
+            for v in live:
+                labels, sums, counts = lloyd.lloyd_update(cl[v], rows[v], shift[v], *tables[v])
+                tables[v] = (sums, counts)
+                old = prev[v].get(gi)
+                changed[v] += int(labels.numel()) if old is None else int((labels != old).sum())
+                prev[v][gi] = labels
+            del rows
+        for v in live:
+            splits = lloyd.finish_iteration(cl[v], tables[v][0], tables[v][1], shift[v])
+            print("lloyd {}: iteration {}: {} labels changed, {} empty clusters split".format('/'.join(v[1:]), epoch, changed[v], splits))
+            if changed[v] == 0:
+                done[v] = True
+                print("lloyd {}: iteration {} changed no label: converged, no further iteration".format('/'.join(v[1:]), epoch))
         if rank == 0:
             save_clusterings(args, epoch, cl, groups.whiten_std, groups.pca)
     return cl
@@ -839,11 +938,13 @@ def run_clustering(args):
     rank, w = world()
     check_whiten(args, w)
     check_pca(args, w)
+    check_algorithm(args, w)
     # a cached run (assign-only, resume_training, a cache of a shard subset) whitens with the cache's std or not at all, and
     # projects with the cache's components or not at all
     cached = _cached_attrs(args)
     cache_file, cached_std = cached_whitening(args, cached)
     _, cached_pca = cached_projection(args, cached)
+    check_cached_algorithm(args, cached)
     if args.clustering.whiten and cache_file is not None and not cached_std:
         raise ValueError("clustering.whiten=True, but the clustering cache {} holds no whiten_std: its centres were trained on "
                          "unwhitened rows".format(cache_file))
@@ -861,6 +962,9 @@ def run_clustering(args):
     if not paths:
         print(f"All shards of {args.data.path} processing already done!")
         return []
+    if args.clustering.algorithm == 'lloyd' and cache_file is None and int(args.clustering.ncentroids) > sum(sizes[p.stem] for p in paths):
+        raise ValueError("clustering.algorithm=lloyd: clustering.ncentroids={} initial centres cannot be {} distinct rows".format(
+            args.clustering.ncentroids, sum(sizes[p.stem] for p in paths)))
     print(f"processing {len(paths)} shards")
     # the first shard THAT LOADS tells the views and their widths (the order KMeans objects are created in, and the row
     # size): the loader reports and skips an unreadable shard, and an empty probe would create no clustering at all

@@ -72,6 +72,7 @@ class KMeans:
             self.initial_rounds = initial_rounds
             self.reinit = reinit
             self.sequential = False
+            self.algorithm = None  # 'lloyd' once to_lloyd() has run (clustering/lloyd.py); an SGD state carries no such key
 
     # ------------------------------------------------------------------ handle management
     def __del__(self):
@@ -81,6 +82,28 @@ class KMeans:
         h, self._h = getattr(self, "_h", None), None
         if h and _lib is not None and _lib._lib is not None:  # module globals die first at interpreter exit
             _lib._lib.acav_kmeans_destroy(h)
+
+    def _refuse_lloyd(self, what):
+        if self.algorithm == 'lloyd':
+            raise _lib.AcavError("KMeans.{} is an SGD step, and this state was trained by batch (Lloyd) k-means: its centres are "
+                                 "cluster means and its hyper-parameters switch the warm-up and the discount off.  Continue it with "
+                                 "clustering.algorithm=lloyd (clustering.lloyd.lloyd_update); the two are not mixed".format(what))
+
+    def to_lloyd(self, centers=None):
+        """Make this a batch (Lloyd) k-means state (clustering/lloyd.py): no warm-up (initial_rounds = 0) and a discount that
+        divides by exactly 1 (reinit = (.7, 1.0)), so calc_best labels every row with its plainly nearest centre; the state says
+        so under 'algorithm', and the SGD entry points refuse it.  centers [k, d]: the initial centres (counts and count start
+        at 0); None keeps the current state."""
+        self.algorithm = 'lloyd'
+        self.initial_rounds, self.reinit = 0, (.7, 1.0)
+        if self._h is not None:
+            _lib.check(_lib._lib.acav_kmeans_set_hyper(self._h, 0, .7, 1.0))
+        if centers is not None:
+            c = np.ascontiguousarray(centers, np.float32)
+            if c.shape != tuple(self._shape):
+                raise ValueError("expected {} initial centres, got shape {}".format(tuple(self._shape), c.shape))
+            self.load_state_arrays(c, np.zeros(c.shape[0], np.float32), 0, 0)
+        return self
 
     def _require_handle(self):
         if self._h is None:
@@ -185,7 +208,7 @@ class KMeans:
     def get_attrs(self):
         """sgd_clustering.py:34-46"""
         centers, counts, count, fallback = self._host_state()
-        return {
+        dt = {
             'args': self.args,
             'count': count,
             'lr': self.lr,
@@ -196,6 +219,9 @@ class KMeans:
             'centers': centers,
             'counts': counts,
         }
+        if self.algorithm is not None:  # only a Lloyd state has the key: an SGD state's attrs stay what they were
+            dt['algorithm'] = self.algorithm
+        return dt
 
     def load_from_saves(self, dt):
         """sgd_clustering.py:48-52"""
@@ -204,6 +230,7 @@ class KMeans:
         self.initial_rounds = dt.get('initial_rounds', 10)
         self.reinit = tuple(dt.get('reinit', (.7, 5.0)))
         self.sequential = dt.get('sequential', False)
+        self.algorithm = dt.get('algorithm')
         self._centers0 = np.ascontiguousarray(dt['centers'], np.float32)
         self._counts0 = np.ascontiguousarray(dt['counts'], np.float32)
         self._count0 = int(dt.get('count', 0))
@@ -315,6 +342,7 @@ class KMeans:
     def add(self, batch):
         """sgd_clustering.py:94-129 (fast parallel update).  Returns the mean min-distance."""
         h = self._require_handle()
+        self._refuse_lloyd('add')
         if self.sequential:
             raise NotImplementedError("the reference's slow `sequential` branch is never enabled (sequential=False)")
         k = self._shape[0]
@@ -337,6 +365,7 @@ class KMeans:
 
     def apply_update(self, x, best, lr):
         """The update half of add() on an already-labelled global batch (sgd_clustering.py:113-128)."""
+        self._refuse_lloyd('apply_update')
         keep, xp, b, _ = _as_f32_2d(x, self._shape[1])
         if hasattr(best, "data_ptr"):
             import torch
@@ -361,6 +390,7 @@ class KMeans:
         warm_best [need,b]: pre-drawn warm-up labels (when several clusterings share the RNG stream
         and must consume it batch by batch); drawn here otherwise."""
         h = self._require_handle()
+        self._refuse_lloyd('train_epoch')
         lr = self.lr if lr is None else lr
         keep, xp, n, _ = _as_f32_2d(x, self._shape[1])
         need = self.warmup_steps(batch_size, n // batch_size)
@@ -387,6 +417,7 @@ class KMeans:
         keep, ptrs, ns, warms, needs = [], [], [], [], []
         for i, (km, x) in enumerate(zip(kms, xs)):
             km._require_handle()
+            km._refuse_lloyd('train_epoch_multi')
             k, xp, n, _ = _as_f32_2d(x, km._shape[1])
             need = km.warmup_steps(batch_size, n // batch_size)
             if warm_bests is None or warm_bests[i] is None:
@@ -416,6 +447,7 @@ class KMeans:
         """One epoch in the large-batch mode (global batch = world * batch_size rows, rank-major: every rank feeds
         batch_size of its own rows per step -- not the reference's N-GPU run, see train_epoch_plan_multi) without a
         collective per step: acav100m_amd/parallel/kmeans_dp.py:train_epoch_dp."""
+        self._refuse_lloyd('train_epoch_distributed')
         lr = self.lr if lr is None else lr
         from ..parallel.rccl_comm import default_comm
         comm = default_comm(comm_slot) if hasattr(x_local, "is_cuda") and x_local.is_cuda else None
@@ -434,6 +466,8 @@ class KMeans:
         kms = list(clusterings)
         if not kms:
             return []
+        for km in kms:
+            km._refuse_lloyd('train_epoch_distributed_multi')
         from ..parallel.collectives import world as _world
         from ..parallel.rccl_comm import default_comm
         rank, w = _world()
@@ -495,6 +529,8 @@ class KMeans:
         kms = list(clusterings)
         if not kms:
             return []
+        for km in kms:
+            km._refuse_lloyd('train_epoch_plan_multi')
         from ..parallel.collectives import world as _world
         from ..parallel.kmeans_dp import plan_warmup_labels, train_epoch_plan
         from ..parallel.rccl_comm import default_comm
@@ -554,6 +590,7 @@ class KMeans:
         trainer: the ONE rank that runs the chain (every rank passes the same number, train_here == (rank == trainer)):
         the rows are sent to it instead of all-gathered."""
         import torch
+        self._refuse_lloyd('train_epoch_comm')
         keep, xp, n_local, on_gpu = _as_f32_2d(x_local, self._shape[1])
         w = comm.world
         steps = n_local // b_local
@@ -598,6 +635,11 @@ class KMeans:
         dt = self.get_attrs()
         dt['args'] = None
         return dt
+
+    def lloyd_update(self, x, s, sums=None, counts=None):
+        """one Lloyd iteration's two sweeps over a row group (clustering/lloyd.py: lloyd_update)"""
+        from .lloyd import lloyd_update
+        return lloyd_update(self, x, s, sums, counts)
 
     def synchronize(self):
         _lib.check(_lib._lib.acav_kmeans_sync(self._require_handle()))

@@ -139,6 +139,16 @@ CLUSTERING_DEFAULTS = {
         # 'pca_total_variance', and a cached run (clustering.cached_epoch) projects with the cache's, refusing a pca_dim that
         # disagrees.  Several GPUs: clustering.multi_gpu=views only.  None (default): every file stays what it is without the key.
         'pca_dim': None,
+        # ours: 'sgd' (default: the chain of sgd_clustering.py, every file stays what it is without the key) or 'lloyd': batch
+        # k-means, what the clusterers of the reference's correspondence_retrieval/code/clustering.py run (clustering_func_type
+        # 'faiss' / 'scipy', args.py:18: full passes that move every centre to the mean of its rows), after the whitening and the
+        # projection if they are on.  `epochs` is then the number of Lloyd iterations (one pass over all rows each, two sweeps:
+        # assign, accumulate); the initial centres are the rows randperm(N)[:ncentroids] of the seeded generator; a cache file is
+        # written after every iteration, and the loop stops early when an iteration changes no label.  The cached state carries
+        # 'algorithm': 'lloyd' with initial_rounds = 0 and reinit = (.7, 1.0): a cached run, the assign stage and `evaluate` then
+        # label every row with its plainly nearest centre.  resume_training from a cache of the other algorithm is refused.
+        # Several GPUs: clustering.multi_gpu=views only.
+        'algorithm': 'sgd',
     },
     'debug': False,
 }
