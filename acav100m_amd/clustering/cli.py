@@ -6,8 +6,7 @@ import sys
 
 from .. import shards as io
 from ..config import CLUSTERING_DEFAULTS, merge, parse_cli
-from .lloyd import check_algorithm
-from .run_clustering import check_pca, check_whiten, run_clustering, store_shards_set
+from .run_clustering import check_options, run_clustering, store_shards_set
 
 
 def get_args(**kwargs):
@@ -37,9 +36,7 @@ class Cli:
     def cluster(self, **kwargs):
         args = get_args(**kwargs)
         from ..parallel import world
-        check_whiten(args, world()[1])  # before anything is created or read
-        check_pca(args, world()[1])
-        check_algorithm(args, world()[1])
+        check_options(args, world()[1])  # before anything is created or read
         args.data.output.path.mkdir(parents=True, exist_ok=True)
         saved = run_clustering(args)
         store_shards_set(args, saved)
@@ -73,9 +70,7 @@ def main(argv=None):
         if int(want) > 1:
             if command in ('cluster', 'run'):  # refused here, not once per spawned process
                 early = merge(CLUSTERING_DEFAULTS, {k: v for k, v in kwargs.items() if k.startswith('clustering.')})
-                check_whiten(early, int(want))
-                check_pca(early, int(want))
-                check_algorithm(early, int(want))
+                check_options(early, int(want))
             launch.spawn_per_gpu('acav100m_amd.clustering.cli', argv, int(want))
             return None
     else:

@@ -19,10 +19,11 @@ the rows finds (KMeans.quality, acav_kmeans_quality: float64 distances on the GP
         --out_path=<dir of a cluster run> --clustering.cached_epoch=<e | [e0,e1,...]> \\
         [--evaluate.out_path=quality.json] [--evaluate.rows_path=<dir>]
 
-Reads cache_epoch_{e}_{name} like a resumed `cluster` run, reads the rows once per row group (data.resident_bytes) and
-evaluates every listed epoch on them while they are on the device.  Writes no assignment shard and no log file.
+Reads cache_epoch_{e}_{name} like a resumed `cluster` run (cache.py: locate, read, find), reads the rows once per row group
+(row_groups.py, data.resident_bytes) and evaluates every listed epoch on them while they are on the device.  Writes no assignment
+shard and no log file.
 A cache that holds `whiten_std` (a `cluster --clustering.whiten=True` run) has its rows divided by it on their way to the
-device, like the run itself: the report and the rows_path values are then in whitened space, and the view's report carries
+device, like the run itself (frontend.py: FrontEnd): the report and the rows_path values are then in whitened space, and the view's report carries
 "whitened": true and "zero_variance_columns" (divisors that are exactly 1).  Epochs that disagree on it are refused.
 A cache that holds `pca_components` (a `cluster --clustering.pca_dim=P` run) has its rows projected through the same helper,
 after the division: the view is judged in projected space and its report carries "pca_dim" and
@@ -36,6 +37,8 @@ from pathlib import Path
 
 import numpy as np
 
+from . import cache
+from .frontend import FrontEnd
 from .sgd_clustering import QUALITY_COLS
 
 COUNT, SUM_A2, SUM_SQRT_A2, SUM_S, DISPLACED, SUM_MIN = range(QUALITY_COLS)  # ACAV_QUALITY_* (include/acav_hip.h)
@@ -102,29 +105,15 @@ def _epochs(value):
     return epochs
 
 
-def _find(saved, view):
-    """the cached attrs of a view: by its full key, or -- a reference-written file does not name the modality -- by
-    (model_key, layer) like run_clustering.load_clusterings"""
-    if view in saved:
-        return saved[view]
-    for key, val in saved.items():
-        if key[1:] == view[1:]:
-            return val
-    return None
-
-
 def load_states(args, epochs):
     """{epoch: {(kind, model_key, layer): attrs}} of the listed epochs, refusing -- before any shard is read -- a cache that
     is missing, unreadable, without a clustering of one of args.models, or still in its warm-up"""
-    from . import run_clustering as rc
     states = OrderedDict()
     for e in epochs:
-        path = rc._cache_path(args, e)
-        if not path.is_file() and args.clustering.load_cache_from_shard_subset:
-            path = rc._subset_cache(args, e) or path
+        path = cache.locate(args, e)
         if not path.is_file():
             raise FileNotFoundError("no clustering cache of epoch {}: {} does not exist".format(e, path))
-        saved = rc._read_cache(path)
+        saved = cache.read(path)
         if not saved:
             raise ValueError("clustering cache {} holds no clustering".format(path))
         for mk in (args.models or []):
@@ -141,17 +130,10 @@ def load_states(args, epochs):
     first = next(iter(states.values()), {})
     for e, saved in states.items():
         for key in set(first) | set(saved):
-            a, b = (_find(first, key) or {}).get('whiten_std'), (_find(saved, key) or {}).get('whiten_std')
-            same = (a is None and b is None) or (a is not None and b is not None and a.shape == b.shape and a.tobytes() == b.tobytes())
-            if not same:
-                raise ValueError("the clustering caches of epochs {} and {} disagree on whiten_std of view {}: evaluate them in "
-                                 "separate runs".format(epochs[0], e, '/'.join(key[1:])))
-            a, b = rc._pca_of(_find(first, key)), rc._pca_of(_find(saved, key))
-            same = (a is None and b is None) or (a is not None and b is not None and all(
-                np.shape(a[k]) == np.shape(b[k]) and np.asarray(a[k]).tobytes() == np.asarray(b[k]).tobytes() for k in a))
-            if not same:
-                raise ValueError("the clustering caches of epochs {} and {} disagree on the pca projection of view {}: evaluate "
-                                 "them in separate runs".format(epochs[0], e, '/'.join(key[1:])))
+            what = FrontEnd.from_attrs(cache.find(first, key)).differs(FrontEnd.from_attrs(cache.find(saved, key)))
+            if what is not None:
+                raise ValueError("the clustering caches of epochs {} and {} disagree on {} of view {}: evaluate them in "
+                                 "separate runs".format(epochs[0], e, what, '/'.join(key[1:])))
     return states
 
 
@@ -159,7 +141,7 @@ def evaluate(args):
     """the `evaluate` verb: prints one line per view and epoch, writes the report as json when evaluate.out_path is given,
     returns it"""
     from .. import shards as io
-    from . import run_clustering as rc
+    from .row_groups import current_device, open_row_groups, probe_shards
     from .sgd_clustering import KMeans
     opts = args.get('evaluate') or {}
     epochs = _epochs(args.clustering.cached_epoch)
@@ -169,42 +151,27 @@ def evaluate(args):
     paths = [Path(p) for p in sorted(io.brace_expand(args.data.path))]
     sizes = io.shard_sizes_from_meta(paths, args.data.meta.path, use_cache=True)
     paths = [p for p in paths if p.stem in sizes]
-    probe = None
-    for first in paths:
-        probe = io.load_feature_shards([first], model_order=list(args.models or []), audio_models=tuple(args.model_types.audio or ()))
-        if probe.views:
-            break
-    if probe is None or not probe.views:
+    _probe, view_dims = probe_shards(args, paths)
+    if view_dims is None:
         raise ValueError("none of the {} shards of {} could be read".format(len(paths), args.data.path))
-    view_dims = OrderedDict((v, m.shape[1]) for v, m in probe.views.items())
-    dev = rc._device(args)
-    # a projected run's centres live in the space of its components (after the division, if there is one)
-    fits = OrderedDict((v, rc._pca_of(_find(states[epochs[0]], v))) for v in view_dims)
-    for v, f in fits.items():
-        if f is not None and (f['components'].ndim != 2 or f['components'].shape[1] != view_dims[v] or f['mean'].shape != (view_dims[v],)):
-            raise ValueError("pca_components of view {} has shape {}, the rows have {} columns".format(
-                '/'.join(v[1:]), f['components'].shape, view_dims[v]))
+    dev = current_device(args)
+    # a whitened run's centres live in x / whiten_std space, a projected run's in the space of its components (after the
+    # division, if there is one): the rows go through the same front-end on their way to the device as the run's own
+    fronts = OrderedDict((v, FrontEnd.from_attrs(cache.find(states[epochs[0]], v))) for v in view_dims)
+    for v, f in fronts.items():
+        f.check_width(v, view_dims[v])
     cl = OrderedDict()
     for e, saved in states.items():
         for v, d in view_dims.items():
-            dt = _find(saved, v)
-            d = d if fits[v] is None else fits[v]['components'].shape[0]
+            dt = cache.find(saved, v)
+            d = fronts[v].width_out(d)
             if dt is None or dt['centers'].shape[1] != d:
                 raise ValueError("the clustering cache of epoch {} lacks view {} (width {})".format(e, '/'.join(v[1:]), d))
             km = KMeans.load(dt)
             km.args = None  # one process, one GPU, whatever run wrote the cache
             cl[e, v] = km.to(dev)
-    row_bytes = 4 * sum(view_dims.values())
-    groups = rc._RowGroups(args, paths, sizes, row_bytes, rc._device_budget(args), view_dims)
-    # a whitened run's centres live in x / whiten_std space: the rows are divided on their way to the device, like the run's own
-    stds = OrderedDict((v, (_find(states[epochs[0]], v) or {}).get('whiten_std')) for v in view_dims)
-    for v, s_ in stds.items():
-        if s_ is not None and s_.shape != (view_dims[v],):
-            raise ValueError("whiten_std of view {} has shape {}, the rows have {} columns".format('/'.join(v[1:]), s_.shape, view_dims[v]))
-    if any(s_ is not None for s_ in stds.values()):
-        groups.set_whitening(stds)
-    if any(f is not None for f in fits.values()):
-        groups.set_projection(fits)
+    groups = open_row_groups(args, paths, sizes, view_dims)
+    groups.add_front_ends(fronts)
     acc = OrderedDict((key, np.zeros((km.centers.shape[0], QUALITY_COLS), np.float64)) for key, km in cl.items())
     if rows_path is not None:
         Path(rows_path).mkdir(parents=True, exist_ok=True)
@@ -230,13 +197,14 @@ def evaluate(args):
     for (e, v), km in cl.items():
         centers, counts, count, _fb = km.state_arrays()
         rep = compose(acc[e, v], centers, counts, count, km.reinit)
-        if stds[v] is not None:  # every figure of this view is in whitened space; a zero-variance column's divisor is exactly 1
+        std, fit = fronts[v].std, fronts[v].pca
+        if std is not None:  # every figure of this view is in whitened space; a zero-variance column's divisor is exactly 1
             rep['whitened'] = True
-            rep['zero_variance_columns'] = int((stds[v] == np.float32(1.0)).sum())
-        if fits[v] is not None:  # every figure of this view is in projected space
-            tv = float(fits[v]['total_variance'])
-            rep['pca_dim'] = int(fits[v]['components'].shape[0])
-            rep['pca_explained_variance_ratio'] = float(fits[v]['explained_variance'].sum() / tv) if tv > 0 else float('nan')
+            rep['zero_variance_columns'] = int((std == np.float32(1.0)).sum())
+        if fit is not None:  # every figure of this view is in projected space
+            tv = float(fit['total_variance'])
+            rep['pca_dim'] = int(fit['components'].shape[0])
+            rep['pca_explained_variance_ratio'] = float(fit['explained_variance'].sum() / tv) if tv > 0 else float('nan')
         report['views'].setdefault('/'.join(v[1:]), OrderedDict())[str(e)] = rep
     print(format_report(report))
     if out_path is not None:

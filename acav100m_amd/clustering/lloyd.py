@@ -21,6 +21,7 @@ import math
 import numpy as np
 
 from .. import _lib
+from .options import needs_every_row
 from .sgd_clustering import KMeans, _as_f32_2d, _device_index
 
 ALGORITHMS = ('sgd', 'lloyd')
@@ -35,12 +36,7 @@ def check_algorithm(args, world_size=1):
     if not isinstance(algo, str) or algo not in ALGORITHMS:
         raise ValueError("clustering.algorithm must be 'sgd' or 'lloyd', not {!r}".format(algo))
     if algo == 'lloyd':
-        from .run_clustering import multi_gpu_mode
-        mode = multi_gpu_mode(args)
-        if int(world_size) > 1 and mode != 'views':
-            raise ValueError("clustering.algorithm=lloyd with clustering.multi_gpu={} on {} GPUs: the rows are partitioned over the "
-                             "ranks and the cluster sums are not merged across them; use clustering.multi_gpu=views or one "
-                             "GPU".format(mode, world_size))
+        needs_every_row(args, world_size, "clustering.algorithm=lloyd", "cluster sums")
         if isinstance(args.clustering.epochs, bool) or int(args.clustering.epochs) < 1:
             raise ValueError("clustering.epochs={!r}: lloyd needs at least one iteration".format(args.clustering.epochs))
     return algo

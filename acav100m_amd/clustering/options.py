@@ -1,0 +1,34 @@
+"""The options of the clustering stage that need every row of a view on one rank, and the one rule that refuses them when several
+GPUs partition the ROWS (clustering.multi_gpu = striped / reference / rows).  Pure: no device, no file."""
+
+
+def multi_gpu_mode(args):
+    """clustering.multi_gpu: 'views' (default), 'striped', 'reference' or 'rows' -- see config.py"""
+    mode = str(args.clustering.multi_gpu or 'views')
+    if mode not in ('views', 'striped', 'reference', 'rows'):
+        raise ValueError("clustering.multi_gpu must be 'views', 'striped', 'reference' or 'rows', not {!r}".format(mode))
+    return mode
+
+
+def needs_every_row(args, world_size, option, unmerged):
+    """ValueError when `option` runs on several GPUs in a mode that partitions the rows; unmerged: what it would have to merge"""
+    mode = multi_gpu_mode(args)
+    if int(world_size) > 1 and mode != 'views':
+        raise ValueError("{} with clustering.multi_gpu={} on {} GPUs: the rows are partitioned over the ranks and the {} are not "
+                         "merged across them; use clustering.multi_gpu=views or one GPU".format(option, mode, world_size, unmerged))
+
+
+def check_whiten(args, world_size):
+    """clustering.whiten needs every row of a view on the rank that takes its moments"""
+    if args.clustering.whiten:
+        needs_every_row(args, world_size, "clustering.whiten", "column moments")
+
+
+def check_pca(args, world_size):
+    """clustering.pca_dim needs every row of a view on the rank that takes its scatter matrix, and is a positive integer"""
+    dim = args.clustering.pca_dim
+    if dim is None:
+        return
+    if isinstance(dim, bool) or not isinstance(dim, int) or dim < 1:
+        raise ValueError("clustering.pca_dim must be a positive integer or None, not {!r}".format(dim))
+    needs_every_row(args, world_size, "clustering.pca_dim", "scatter matrices")

@@ -47,7 +47,7 @@ def run(glob, out, n, k, label, d=1024):
     import torch
     import acav100m_amd
     from acav100m_amd import shards as io
-    from acav100m_amd.clustering import cli, run_clustering as rc
+    from acav100m_amd.clustering import cli, row_groups as rg, run_clustering as rc
     from acav100m_amd.clustering.sgd_clustering import KMeans
     acc = {"load": 0.0, "upload": 0.0, "train": 0.0, "assign": 0.0, "write": 0.0, "groups": 0}
     orig_load, orig_multi, orig_best, orig_dump = io.load_feature_shards, KMeans.train_epoch_multi, KMeans.calc_best, io.dump_pickle
@@ -95,15 +95,14 @@ def run(glob, out, n, k, label, d=1024):
     class _Up:  # time the H2D copies issued by _RowGroups (torch.from_numpy(...).to(dev))
         pass
     io.load_feature_shards, KMeans.train_epoch_multi, KMeans.calc_best, io.dump_pickle = load, staticmethod(multi), best, dump
-    rc.io.load_feature_shards = load
     made = []
-    orig_groups = rc._RowGroups
+    orig_groups = rg._RowGroups  # (row_groups.open_row_groups constructs through this name)
 
     class Groups(orig_groups):
         def __init__(self, *a, **kw):
             super().__init__(*a, **kw)
             made.append(self)
-    rc._RowGroups = Groups
+    rg._RowGroups = Groups
     try:
         shutil.rmtree(out, ignore_errors=True)
         acav100m_amd.manual_seed(0)
@@ -122,8 +121,7 @@ def run(glob, out, n, k, label, d=1024):
         wall = time.perf_counter() - t0
     finally:
         io.load_feature_shards, KMeans.train_epoch_multi, KMeans.calc_best, io.dump_pickle = orig_load, orig_multi, orig_best, orig_dump
-        rc.io.load_feature_shards = orig_load
-        rc._RowGroups = orig_groups
+        rg._RowGroups = orig_groups
         io.AssignmentWriter.finish = orig_finish
     t_wait, t_up = sum(g.t_wait for g in made), sum(g.t_upload for g in made)
     passes = 3  # 2 training epochs + the assign pass each read every row once
