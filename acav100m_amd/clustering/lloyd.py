@@ -177,23 +177,43 @@ def finish_iteration(km, sums, counts, s):
     return splits
 
 
-def fit(x, k, iters, generator=None, device="cuda"):
+class FitReport(list):
+    """fit's report: the list of (changed labels, splits) per iteration; potential: the potentials int64 [k] of a k-means++
+    seeding (None with init='random')"""
+    potential = None
+
+
+def fit(x, k, iters, generator=None, device="cuda", init='random', trials=1, sample=None):
     """Lloyd k-means of x [n, d] (numpy or a torch tensor) in one resident piece -> (KMeans in its lloyd state, labels of the last
-    iteration's assignment, report: per iteration (changed labels, splits)).  Initial centres: the rows generator.randperm(n)[:k].
+    iteration's assignment, report: per iteration (changed labels, splits)).  Initial centres: the rows generator.randperm(n)[:k]
+    (init='random'), or (init='kmeans++', clustering/kmeanspp.py) k-means++ seeds with `trials` trials per pick on the sample
+    made of the first min(n, sample or 256 k) entries of the same permutation, in ascending order -- the uniforms are the
+    generator's draws after the permutation, and report.potential holds the seeding's potentials, int64 [k].
     Stops early when an iteration changes no label."""
     import torch
+    from . import kmeanspp
+    if init not in kmeanspp.INITS:
+        raise ValueError("init must be 'random' or 'kmeans++', not {!r}".format(init))
     dev = x.device if hasattr(x, "is_cuda") and x.is_cuda else torch.device("cuda:{}".format(_device_index(device)))
     t = (x.detach() if hasattr(x, "data_ptr") else torch.from_numpy(np.ascontiguousarray(x, np.float32))).to(dev, torch.float32).contiguous()
     n, d = t.shape
     if k > n:
         raise ValueError("{} centres from {} rows: K > N".format(k, n))
     from ..rng import default_generator
-    perm = (generator if generator is not None else default_generator).randperm(n)[:k]  # the generator's next draw
+    gen = generator if generator is not None else default_generator
+    potential = None
+    if init == 'random':
+        perm = gen.randperm(n)[:k]  # the generator's next draw
+    else:
+        rows = np.sort(gen.randperm(n)[:kmeanspp.sample_size(n, k, sample)])
+        picked, potential = kmeanspp.seed(t[torch.from_numpy(rows).to(dev)], k, trials, generator=gen)
+        perm = rows[picked]
     km = KMeans(None, d, k, generator=generator)
     km.to_lloyd(t[torch.from_numpy(perm).to(dev)].cpu().numpy())
     km.to(dev)
     s = fixed_point_shift(rows_absmax(t), n)
-    report, prev = [], None
+    report, prev = FitReport(), None
+    report.potential = potential
     for _it in range(int(iters)):
         labels, sums, counts = lloyd_update(km, t, s)
         changed = n if prev is None else int((labels != prev).sum())

@@ -30,6 +30,7 @@ from ..parallel import world
 from . import cache
 from .cache import path as _cache_path, read as _read_cache  # noqa: F401  (the names of before the cache module)
 from .frontend import PCA_KEYS, FrontEnd, pca_of as _pca_of  # noqa: F401
+from .kmeanspp import check_init
 from .lloyd import check_algorithm
 from .options import check_pca, check_whiten, multi_gpu_mode
 from . import row_groups
@@ -47,6 +48,7 @@ def check_options(args, world_size):
     check_whiten(args, world_size)
     check_pca(args, world_size)
     check_algorithm(args, world_size)
+    check_init(args)
 
 
 def init_clusterings(args, table, widths=None):
@@ -333,12 +335,14 @@ def _train_clusters_lloyd(args, cl, groups, pre, iters, resumed):
     groups with two sweeps per view -- the assign sweep and acav_lloyd_accumulate into int64 tables on the device -- and the centre
     update on the host.  Before the first one, one read-once pass takes every view's largest magnitude (the scale of the fixed
     point) and, for a fresh run, the initial centres: the rows generator.randperm(N)[:K], drawn view by view, read as the
-    front-ends deliver them.  The tables are integer sums, so resident and streamed rows give the same bytes.  N comes from the
-    metadata when the rows stream (like the batch plan of the SGD loop) and is checked against what the shards deliver.
+    front-ends deliver them -- or, with clustering.init=kmeans++, k-means++ seeds drawn from a sample of the rows that the same
+    pass gathers (clustering/kmeanspp.py).  The tables are integer sums, so resident and streamed rows give the same bytes.
+    N comes from the metadata when the rows stream (like the batch plan of the SGD loop) and is checked against what the shards
+    deliver.
     Several GPUs (clustering.multi_gpu=views): every rank runs every view -- the result is a pure function of the rows, the ranks
     end in the same state without an exchange -- and rank 0 writes the caches."""
     import torch
-    from . import lloyd
+    from . import kmeanspp, lloyd
     rank, _w = world()
     K = int(args.clustering.ncentroids)
     print("training lloyd kmeans for views: {}".format([v[1:] for v in cl]))
@@ -348,10 +352,19 @@ def _train_clusters_lloyd(args, cl, groups, pre, iters, resumed):
         n_total = len(groups.resident_table())
     if K > n_total:
         raise ValueError("clustering.algorithm=lloyd: clustering.ncentroids={} initial centres cannot be {} distinct rows".format(K, n_total))
-    picks = OrderedDict()
+    # clustering.init=kmeans++ (a fresh run only; a resumed one ignores the keys as it ignores the picks): the same pass gathers,
+    # instead of the K initial rows, the seeding sample -- the first M entries of the same randperm, in ascending order -- into
+    # one device tensor per view; the views are then seeded in turn (clustering/kmeanspp.py), each from the uniforms its
+    # generator delivers at that point, i.e. after the permutations of all views
+    plus = not resumed and kmeanspp.check_init(args) == 'kmeans++'
+    if plus:
+        M = kmeanspp.sample_size(n_total, K, args.clustering.init_sample)
+        T = kmeanspp.trials_for(K, 1 if args.clustering.init_trials is None else args.clustering.init_trials)
+    picks, sample = OrderedDict(), OrderedDict()
     if not resumed:
         for v, km in cl.items():
-            picks[v] = km._generator.randperm(n_total)[:K]
+            perm = km._generator.randperm(n_total)
+            picks[v] = np.sort(perm[:M]) if plus else perm[:K]
     absmax = OrderedDict((v, 0.0) for v in cl)
     init = OrderedDict((v, np.zeros(km._shape, np.float32)) for v, km in cl.items())
     base = 0
@@ -360,7 +373,13 @@ def _train_clusters_lloyd(args, cl, groups, pre, iters, resumed):
         for v in cl:
             x = rows[v]
             absmax[v] = max(absmax[v], lloyd.rows_absmax(x))
-            if not resumed:
+            if plus:
+                lo, hi = (int(i) for i in np.searchsorted(picks[v], (base, base + n_g)))
+                if v not in sample:
+                    sample[v] = torch.empty((M, x.shape[1]), dtype=torch.float32, device=x.device)
+                if hi > lo:
+                    sample[v][lo:hi] = x[torch.from_numpy(picks[v][lo:hi] - base).to(x.device)]
+            elif not resumed:
                 sel = np.flatnonzero((picks[v] >= base) & (picks[v] < base + n_g))
                 if len(sel):
                     init[v][sel] = x[torch.from_numpy(picks[v][sel] - base).to(x.device)].cpu().numpy()
@@ -369,6 +388,17 @@ def _train_clusters_lloyd(args, cl, groups, pre, iters, resumed):
     if base != n_total:
         raise RuntimeError("the shards delivered {} rows, their metadata states {}: fix the metadata or drop the unreadable shards "
                            "from the list".format(base, n_total))
+    if plus:
+        for v, km in cl.items():
+            x = sample.pop(v)  # (freed before the next view is seeded)
+            try:
+                seeds, potential = kmeanspp.seed(x, K, T, u=kmeanspp.uniforms(km._generator, 1 + (K - 1) * T))
+            except ValueError as exc:
+                raise ValueError("view {}: {}".format('/'.join(v[1:]), exc))
+            init[v] = x[torch.from_numpy(seeds).to(x.device)].cpu().numpy()
+            print("lloyd {}: k-means++ seeds from a sample of {} rows, {} trials per pick: potential {} -> {}".format(
+                '/'.join(v[1:]), M, T, int(potential[0]), int(potential[-1])))
+            del x
     shift = OrderedDict()
     for v, km in cl.items():
         try:

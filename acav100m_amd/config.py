@@ -149,6 +149,20 @@ CLUSTERING_DEFAULTS = {
         # label every row with its plainly nearest centre.  resume_training from a cache of the other algorithm is refused.
         # Several GPUs: clustering.multi_gpu=views only.
         'algorithm': 'sgd',
+        # ours (algorithm=lloyd only): how the initial centres are chosen.  'random' (default: the rows randperm(N)[:ncentroids],
+        # every file and every generator draw stays what it is without the key) or 'kmeans++': D^2 sampling (scipy's
+        # kmeans2(minit='++'), sklearn's default) on a sample of the rows -- the first init_sample entries of the same randperm --
+        # gathered on the device during the pass that reads the initial rows today; every pick is one read-once sweep over the
+        # sample (clustering/kmeanspp.py, acav_kmeanspp_seed), the result a pure function of the rows and the seed.  What to turn
+        # when `evaluate` reports empty or under-used clusters, or `cluster` reports splits.  A resumed run ignores the three
+        # keys.  Several GPUs: clustering.multi_gpu=views only (every rank computes the same seeds).
+        'init': 'random',
+        # local trials per k-means++ pick: 1 (default, the classical algorithm), 'auto' = min(16, 2 + floor(ln ncentroids))
+        # (sklearn's greedy variant: of the trials' rows the one that lowers the potential most is kept) or an integer in [1, 16]
+        'init_trials': 1,
+        # rows of the k-means++ sample: None (default) = min(N, 256 * ncentroids) (faiss's max_points_per_centroid), or an
+        # integer of at least ncentroids; only the sample has to be resident, the rows themselves may stream
+        'init_sample': None,
     },
     'debug': False,
 }
