@@ -1760,6 +1760,14 @@ constexpr int FY_DEPTH = ACAV_FY_DEPTH;     // groups of perm buffers in flight:
 constexpr int FY_NBUF = FY_DEPTH * FY_GROUP;  // of the gathers (a cross-stream hand-off costs 15-45 us: two deep, both hand-offs
                                               // of a group sat on the critical cycle and left a ~30 us bubble per group)
 constexpr int GS_EPT = 4;          // outputs per thread of the gather
+// defaults of the gather's XCD subset (gs_block_map; ACAV_GS_XCDS / ACAV_GS_XCD_ROT / ACAV_GS_XCD_MIN_L override them per call).
+// Loop at L = 10^6, enqueue + drain us per iteration: 8 XCDs 28.5-29.4, 4 rotating 27.36, 4 fixed 32.38, 2 rotating 34.71, 1
+// rotating 51.81.  Crossover, 8 -> 4 rotating: L = 5 10^5 14.5 -> 15.0 / 15.3 and 2.5 10^5
+// 11.6 -> 11.9, 6.5 10^5 17.3 -> 18.4 (slower: a list well below an L2 stays resident on all eight), 8 10^5 (the list runs down
+// to 7.2 10^5 in the 20 000 iterations measured) 21.97 -> 22.14 / 22.19: the crossover is at about 8 10^5
+constexpr int GS_XCDS_DEFAULT = 4;
+constexpr bool GS_XCD_ROT_DEFAULT = true;
+constexpr long long GS_XCD_MIN_L_DEFAULT = 800000;
 constexpr int FY_SHARDS = 8;       // sub-buckets per tile (capg entries each), filled by workgroups b with b % 8 == shard
 constexpr int FYT_THREADS = ACAV_FYT_THREADS;  // k_fy_tile: the list walks are chains of dependent LDS reads -- many waves hide them
 // Bucket entries in 4 bytes instead of an int2 (step, target) -- half of the bucket stream that k_fy_part writes and k_fy_tile reads
@@ -2112,6 +2120,51 @@ static dim3 fy_launch_grid(bool affine, unsigned nx, unsigned ny, unsigned gz, u
     return dim3(nx, ny, gz);
 }
 
+// XCD subset of the gather (k_fy_gather_select_multi, single-chunk launches).  The candidate list A is read at uniformly random
+// positions by every gather workgroup, and at 10^6 candidates it is exactly one L2 in size: every XCD that runs gather workgroups
+// pulls in all of it, so on n XCDs the list crosses the fabric n times per iteration (8 x 31.25 k of the gather's 279 k read
+// requests at n = 8).  How many XCDs gather is a matter of where the workgroups run, not of the algorithm: workgroup 0 stays the
+// selection, a workgroup b >= 1 gathers only if its class b % 8 lies in {(rot + j) % 8 : j < n_xcd}, the gathering workgroups are
+// numbered densely in ascending b (that number stands where blockIdx.x - 1 stood), and every other workgroup is padding that
+// returns at once.  n_xcd = 8: g = b - 1 and no padding, the grid as it was.  As with fy_block_map the placement is observed,
+// not promised, and nothing crosses workgroups that did not before: a wrong guess costs speed only.  Plain C++ on both sides:
+// acav_gs_block_map() exposes it to the tests without a device.
+struct GsGrid {
+    unsigned n_xcd, rot;  // rot: the first class of the set, 0..7
+};
+struct GsBlock {
+    int g;  // the gather index, GS_SELECT or GS_NONE
+};
+constexpr int GS_SELECT = -1, GS_NONE = -2;
+// bit c: class c gathers
+__host__ __device__ inline unsigned gs_class_mask(unsigned n_xcd, unsigned rot)
+{
+    const unsigned m = ((1u << n_xcd) - 1u) << rot;  // n_xcd <= 8, rot < 8: 15 bits
+    return (m | (m >> FY_XCDS)) & ((1u << FY_XCDS) - 1u);
+}
+__host__ __device__ inline GsBlock gs_block_map(unsigned b, unsigned n_xcd, unsigned rot)
+{
+    if (b == 0) return {GS_SELECT};
+    const unsigned mask = gs_class_mask(n_xcd, rot), c = b % FY_XCDS;
+    if (!(mask >> c & 1u)) return {GS_NONE};
+    // the gathering workgroups below b: n_xcd in every full row of eight, the set's classes below c in this one, less workgroup 0
+    return {(int)(b / FY_XCDS * n_xcd + (unsigned)__builtin_popcount(mask & ((1u << c) - 1u)) - (mask & 1u))};
+}
+// the 1-D grid: the selection, and the shortest row behind it that holds gather_blocks gathering workgroups
+__host__ __device__ inline long long gs_grid_blocks(long long gather_blocks, unsigned n_xcd, unsigned rot)
+{
+    if (gather_blocks <= 0) return 1;
+    const unsigned mask = gs_class_mask(n_xcd, rot);
+    const long long t = gather_blocks - 1 + (mask & 1u);  // the last one is the t-th (from 0) workgroup of the set, workgroup 0 counted
+    unsigned r = (unsigned)(t % n_xcd), c = 0;
+    for (;; ++c)
+        if (mask >> c & 1u) {
+            if (r == 0) break;
+            --r;
+        }
+    return t / n_xcd * FY_XCDS + c + 1;
+}
+
 template <bool STAGED, bool PACK>
 __global__ __launch_bounds__(FYA_THREADS) void k_fy_part_multi(const TileChunk *__restrict__ cd, int it0, int dl)
 {
@@ -2192,22 +2245,24 @@ __global__ __launch_bounds__(256) void k_fy_resolve_multi(const TileChunk *__res
 // through LDS instead of one register per thread, and the hand-over loops over the nreq (up to B - 1) positions
 template <bool W, bool WIDE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_fy_gather_select_multi(
-    const TileChunk *__restrict__ cd, int it, int dl, int B, int k, int mode, int keep_unselected)
+    const TileChunk *__restrict__ cd, int it, int dl, int B, int k, int mode, int keep_unselected, GsGrid gr)
 {
     ACAV_MI_EMPTY_RETURN
+    const GsBlock blk = gs_block_map(blockIdx.x, gr.n_xcd, gr.rot);
+    if (blk.g == GS_NONE) return;  // padding: its XCD does not gather in this launch
     const TileChunk &c = cd[blockIdx.y];
     const int L = c.L0 - it * dl;  // list length of iteration `it`
     const int nreq = keep_unselected ? B - k : 0;
     const int bcap = WIDE ? c.bcap : SEL_MAXB;
     const int bstride = bcap * (1 + c.D);  // one half of the batch buffer: ids [bcap], label rows [bcap][D]
-    if (blockIdx.x != 0) {
+    if (blk.g != GS_SELECT) {
         if (it >= c.iters) return;
         // GS_EPT outputs per thread, every index load before the first content load (1 -> 4 per thread: 34.9 -> 33.7 us per
         // iteration at L = 10^6; 8 the same, 16 slower)
         int av[GS_EPT], vv[GS_EPT];
 #pragma unroll
         for (int u = 0; u < GS_EPT; ++u) {
-            const int i = (int)(((blockIdx.x - 1) * GS_EPT + u) * 256 + threadIdx.x);
+            const int i = (int)(((unsigned)blk.g * GS_EPT + u) * 256 + threadIdx.x);
             av[u] = i < L ? (int)c.perm[it % FY_NBUF][i] : -1;
         }
 #pragma unroll
@@ -2217,7 +2272,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         }
 #pragma unroll
         for (int u = 0; u < GS_EPT; ++u) {
-            const int i = (int)(((blockIdx.x - 1) * GS_EPT + u) * 256 + threadIdx.x);
+            const int i = (int)(((unsigned)blk.g * GS_EPT + u) * 256 + threadIdx.x);
             if (av[u] < 0) continue;
             const int v = vv[u];
             if (i < B) {  // a batch entry travels with its label row: the next launch's selection starts one level further on
@@ -2934,6 +2989,15 @@ static int run_greedy_tiled(acav_mi **mis, int nchunks, const int64_t *const *ca
     // =0: the 3-D grids of the tile and resolve kernels, every item's workgroups dealt over all XCDs (A/B; see fy_block_map)
     const char *vaff = getenv("ACAV_FY_XCD_AFFINE");
     const bool xcd_affine = !(vaff && vaff[0] == '0');
+    // The gather's XCD subset (gs_block_map), single-chunk runs only -- the per-chunk lists of a lockstep launch are a tenth of an
+    // L2 and keep their 2-D grid.  ACAV_GS_XCDS = 1, 2, 4: that many XCDs gather, 8: all of them (no padding); ACAV_GS_XCD_ROT=1
+    // moves the set by its size every launch, =0 keeps it at classes 0..n-1; ACAV_GS_XCD_MIN_L: the list length of a launch from
+    // which the subset form is used (below it the list does not compete for an L2 and fewer CUs only slow the gather down).
+    const char *vgx = getenv("ACAV_GS_XCDS"), *vgr = getenv("ACAV_GS_XCD_ROT"), *vgl = getenv("ACAV_GS_XCD_MIN_L");
+    int gs_xcds = vgx ? atoi(vgx) : GS_XCDS_DEFAULT;
+    ACAV_REQUIRE(gs_xcds == 1 || gs_xcds == 2 || gs_xcds == 4 || gs_xcds == 8, ACAV_EINVAL, "ACAV_GS_XCDS=%s: 1, 2, 4 or 8", vgx);
+    const bool gs_rot = vgr ? vgr[0] == '1' : GS_XCD_ROT_DEFAULT;
+    const long long gs_min_l = vgl ? atoll(vgl) : GS_XCD_MIN_L_DEFAULT;
     int pmax = 1, dmax = 1, ntmax = 1;
     bool weighted = false;  // some chunk has pair weights: the weighted selection for the whole launch
     size_t part_smem = 0, part_smem_staged = 0, tile_smem = 0;
@@ -3059,6 +3123,7 @@ static int run_greedy_tiled(acav_mi **mis, int nchunks, const int64_t *const *ca
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)sel_smem));
     const auto t_loop0 = std::chrono::steady_clock::now();
     long long groups_1d = 0, groups_3d = 0;  // launch form of the tile / resolve grids, per group (diagnostics: ACAV_MI_TIMING prints it)
+    long long gs_launches_sub = 0, gs_launches_all = 0;  // gather launches on a subset of the XCDs / on all eight (the same)
     for (int64_t g0 = 0; g0 < iters_max; g0 += FY_GROUP) {
         const int64_t g1 = g0 + FY_GROUP < iters_max ? g0 + FY_GROUP : iters_max;
         const unsigned gz = (unsigned)(g1 - g0);
@@ -3091,15 +3156,20 @@ static int run_greedy_tiled(acav_mi **mis, int nchunks, const int64_t *const *ca
         // ---- main stream: the group's gathers (each with the selection of the iteration before it), back to back
         ACAV_HIP_TRY(hipStreamWaitEvent(st, lead->ev_tile[ge], 0));
         for (int64_t it = g0; it < g1; ++it) {
-            const dim3 grid((unsigned)((lmax - it * dl + 256 * GS_EPT - 1) / (256 * GS_EPT)) + 1u, (unsigned)nchunks);
-            hipLaunchKernelGGL(gs_kernel, grid, dim3(256), sel_smem, st, dcd, (int)it, (int)dl, B, k, sel_f, keep_unselected);
+            const int64_t lit = lmax - it * dl, gather_blocks = (lit + 256 * GS_EPT - 1) / (256 * GS_EPT);
+            GsGrid gr_gs = {(unsigned)FY_XCDS, 0u};
+            if (nchunks == 1 && gs_xcds < FY_XCDS && lit >= gs_min_l)
+                gr_gs = {(unsigned)gs_xcds, gs_rot ? (unsigned)(gs_launches_sub * gs_xcds % FY_XCDS) : 0u};
+            ++(gr_gs.n_xcd < (unsigned)FY_XCDS ? gs_launches_sub : gs_launches_all);
+            const dim3 grid((unsigned)gs_grid_blocks(gather_blocks, gr_gs.n_xcd, gr_gs.rot), (unsigned)nchunks);
+            hipLaunchKernelGGL(gs_kernel, grid, dim3(256), sel_smem, st, dcd, (int)it, (int)dl, B, k, sel_f, keep_unselected, gr_gs);
         }
         ACAV_HIP_TRY(hipGetLastError());
         ACAV_HIP_TRY(hipEventRecord(lead->ev_gather[ge], st));
     }
     if (iters_max > 0)  // the selection of the last iteration
         hipLaunchKernelGGL(gs_kernel, dim3(1u, (unsigned)nchunks), dim3(256), sel_smem, st, dcd, (int)iters_max, (int)dl, B, k,
-                           sel_f, keep_unselected);
+                           sel_f, keep_unselected, GsGrid{(unsigned)FY_XCDS, 0u});
     ACAV_HIP_TRY(hipGetLastError());
     const auto t_loop1 = std::chrono::steady_clock::now();
     ACAV_HIP_TRY(hipStreamSynchronize(sf));
@@ -3107,11 +3177,13 @@ static int run_greedy_tiled(acav_mi **mis, int nchunks, const int64_t *const *ca
         ACAV_HIP_TRY(hipStreamSynchronize(st));
         const auto t_loop2 = std::chrono::steady_clock::now();
         fprintf(stderr, "[acav] greedy loop: %d chunk(s), %lld iterations, host enqueue %.2f us/iteration, enqueue + drain %.2f "
-                        "us/iteration (tiles %d, cap %d, lanes %d; tile / resolve grids: 1-D XCD-affine in %lld group(s), 3-D in %lld; streams replaced by the queue probe at create: %d)\n",
+                        "us/iteration (tiles %d, cap %d, lanes %d; tile / resolve grids: 1-D XCD-affine in %lld group(s), 3-D in %lld; "
+                        "gather grid: %d XCD(s), rotation %d, subset form in %lld launch(es), all eight in %lld; streams replaced by the queue probe at create: %d)\n",
                 nchunks, (long long)iters_max,
                 std::chrono::duration<double, std::micro>(t_loop1 - t_loop0).count() / (double)(iters_max ? iters_max : 1),
                 std::chrono::duration<double, std::micro>(t_loop2 - t_loop0).count() / (double)(iters_max ? iters_max : 1),
-                plans[0].NT, plans[0].ecap, streams[0].W, groups_1d, groups_3d, mis[0]->queue_probe_replaced);
+                plans[0].NT, plans[0].ecap, streams[0].W, groups_1d, groups_3d, gs_xcds, (int)gs_rot, gs_launches_sub, gs_launches_all,
+                mis[0]->queue_probe_replaced);
     }
     const auto t_tail0 = clk::now();
     for (int c = 0; c < nchunks; ++c) {
@@ -3154,6 +3226,27 @@ ACAV_EXPORT int acav_fy_block_map(int64_t b, int nx, int ny, int gz, int *x, int
     ACAV_REQUIRE(nb <= 0x7fffffffll && b >= 0 && b < nb, ACAV_EINVAL, "workgroup %lld outside the grid of %lld", (long long)b, nb);
     const FyBlock q = fy_block_map((unsigned)b, (unsigned)nx, (unsigned)ny, (unsigned)gz);
     *x = q.work ? q.x : -1, *y = q.work ? q.y : -1, *z = q.work ? q.z : -1;
+    return ACAV_OK;
+}
+
+// The 1-D row of k_fy_gather_select_multi when n_xcd of the eight XCDs gather, without a device (gs_block_map)
+ACAV_EXPORT int acav_gs_block_grid(int64_t gather_blocks, int n_xcd, int rot, int64_t *blocks)
+{
+    ACAV_REQUIRE(blocks, ACAV_EINVAL, "NULL argument");
+    ACAV_REQUIRE((n_xcd == 1 || n_xcd == 2 || n_xcd == 4 || n_xcd == 8) && rot >= 0 && rot < FY_XCDS && gather_blocks >= 0, ACAV_EINVAL,
+                 "bad row: %lld gather workgroups on %d XCD(s), rotation %d", (long long)gather_blocks, n_xcd, rot);
+    *blocks = gs_grid_blocks(gather_blocks, (unsigned)n_xcd, (unsigned)rot);
+    return ACAV_OK;
+}
+
+ACAV_EXPORT int acav_gs_block_map(int64_t b, int n_xcd, int rot, int *role, int64_t *g)
+{
+    ACAV_REQUIRE(role && g, ACAV_EINVAL, "NULL argument");
+    ACAV_REQUIRE((n_xcd == 1 || n_xcd == 2 || n_xcd == 4 || n_xcd == 8) && rot >= 0 && rot < FY_XCDS && b >= 0 && b <= 0xffffffffll,
+                 ACAV_EINVAL, "bad workgroup %lld on %d XCD(s), rotation %d", (long long)b, n_xcd, rot);
+    const GsBlock q = gs_block_map((unsigned)b, (unsigned)n_xcd, (unsigned)rot);
+    *role = q.g == GS_SELECT ? 0 : q.g == GS_NONE ? 2 : 1;
+    *g = q.g >= 0 ? q.g : -1;
     return ACAV_OK;
 }
 

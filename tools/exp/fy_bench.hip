@@ -148,11 +148,28 @@ int main(int argc, char **argv)
     // gathers of iterations 0..G-1, alone (perm / src / g of the last group are in place)
     const int sel_m = sel_mode(B, P, k);
     const size_t sel_smem = sel_layout(B, P, D, k, sel_m).total;
+    // the product's switches of the gather's XCD subset (gs_block_map): ACAV_GS_XCDS = 1, 2, 4, 8 and ACAV_GS_XCD_ROT = 0 / 1.
+    // FYB_GS_PAD=n (probe, timing only): all eight classes gather, the grid padded to the length it has at ACAV_GS_XCDS=n -- what
+    // the padding workgroups alone cost
+    const int gs_n = getenv("ACAV_GS_XCDS") ? atoi(getenv("ACAV_GS_XCDS")) : GS_XCDS_DEFAULT;
+    if (gs_n != 1 && gs_n != 2 && gs_n != 4 && gs_n != 8) { printf("ACAV_GS_XCDS: 1, 2, 4 or 8\n"); return 1; }
+    const bool gs_rot = getenv("ACAV_GS_XCD_ROT") ? getenv("ACAV_GS_XCD_ROT")[0] == '1' : GS_XCD_ROT_DEFAULT;
+    const int gs_pad = getenv("FYB_GS_PAD") ? atoi(getenv("FYB_GS_PAD")) : 0;
+    if (gs_pad != 0 && gs_pad != 1 && gs_pad != 2 && gs_pad != 4 && gs_pad != 8) { printf("FYB_GS_PAD: 1, 2, 4 or 8\n"); return 1; }
+    GsGrid gr_gs = {(unsigned)FY_XCDS, 0u};
+    long long gs_launch = 0;
+    auto gs_grid = [&]() {  // sets gr_gs for the launch that follows
+        const long long gb = (L + 256 * GS_EPT - 1) / (256 * GS_EPT);
+        if (gs_pad) return dim3((unsigned)gs_grid_blocks(gb, (unsigned)gs_pad, 0u), 1);
+        gr_gs = {(unsigned)gs_n, gs_rot && gs_n < FY_XCDS ? (unsigned)(gs_launch++ * gs_n % FY_XCDS) : 0u};
+        return dim3((unsigned)gs_grid_blocks(gb, gr_gs.n_xcd, gr_gs.rot), 1);
+    };
+    printf("gather grid: %d XCD(s), rotation %d, %u workgroups%s\n", gs_n, (int)gs_rot, gs_grid().x, gs_pad ? "  [all eight gather, padded row]" : "");
     int itg = 0;
-    auto g_sc = [&]() { hipLaunchKernelGGL((k_fy_gather_select_multi<false, false>), dim3((L + 256 * GS_EPT - 1) / (256 * GS_EPT) + 1, 1), dim3(256), sel_smem, 0, dcd, itg, dl, B, k, sel_m, 1); itg = (itg + 1) % G; };
+    auto g_sc = [&]() { hipLaunchKernelGGL((k_fy_gather_select_multi<false, false>), gs_grid(), dim3(256), sel_smem, 0, dcd, itg, dl, B, k, sel_m, 1, gr_gs); itg = (itg + 1) % G; };
     timeit("G x gather+select", [&]() { for (int i = 0; i < G; ++i) g_sc(); }, 0);
     {   // iteration 0 only: no selection in workgroup 0 -- the gather alone
-        auto g0only = [&]() { hipLaunchKernelGGL((k_fy_gather_select_multi<false, false>), dim3((L + 256 * GS_EPT - 1) / (256 * GS_EPT) + 1, 1), dim3(256), sel_smem, 0, dcd, 0, dl, B, k, sel_m, 1); };
+        auto g0only = [&]() { hipLaunchKernelGGL((k_fy_gather_select_multi<false, false>), gs_grid(), dim3(256), sel_smem, 0, dcd, 0, dl, B, k, sel_m, 1, gr_gs); };
         timeit("G x gather (launch 0: no selection)", [&]() { for (int i = 0; i < G; ++i) g0only(); }, 0);
     }
     {   // the same with ONE perm buffer for every iteration (stays in cache) -- how much of the gather is the first touch of perm?
@@ -185,7 +202,7 @@ int main(int argc, char **argv)
         const bool nosel = getenv("FYB_NOSEL") != nullptr;  // every gather as launch 0: no selection beside it
         auto gath = [&](hipStream_t st) {
             for (int i = 0; i < G; ++i)
-                hipLaunchKernelGGL((k_fy_gather_select_multi<false, false>), dim3((L + 256 * GS_EPT - 1) / (256 * GS_EPT) + 1, 1), dim3(256), sel_smem, st, dcd, nosel ? 0 : i, dl, B, k, sel_m, 1);
+                hipLaunchKernelGGL((k_fy_gather_select_multi<false, false>), gs_grid(), dim3(256), sel_smem, st, dcd, nosel ? 0 : i, dl, B, k, sel_m, 1, gr_gs);
         };
         auto wall = [&](const char *name, auto fn) {
             fn(); CK(hipDeviceSynchronize());
