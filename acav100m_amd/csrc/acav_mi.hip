@@ -752,13 +752,92 @@ __device__ __forceinline__ bool exact_better(double s, int p, double so, int po)
     return so > s || (so == s && po < p);
 }
 
+// The MI tables of one handle as the exact-greedy and CELF kernels see them (mi_tables() on the host): the labels and the
+// pair list, the counts with their running phi sums, the scalars, and what the handle's measure reads beside them -- the log
+// tables (ami / nmi), the pair sums ps (fm / rand / arand), the fp32 pair weights pw (NULL unless the weighted mi runs)
+struct MiTables {
+    const int *asg;
+    int D, C, P;
+    const int *pairs;
+    int *Nc, *ac, *bc;
+    double *SN, *Sa, *Sb;
+    const double *phi;
+    MiScalars *sc;
+    int measure;
+    const double *lnk, *lf;
+    int avg;
+    PairStat *ps;
+    const float *pw;
+};
+
+// The score of candidate `id` for pair p against tables that hold n samples.  measure 0: calc_MI ('mi' / 'mem_mi'); 1: calc_AMI
+// ('ami'); 2: calc_NMI (mi.py:262-271); 3: ConstantMeasure (mi.py:274-281: every candidate scores 1, the first remaining one
+// is taken); 4 / 5 / 6: Fowlkes-Mallows / Rand / adjusted Rand (efficient_pair.py; ps holds their per-pair sums).  avg:
+// average_method of 1 and 2.
 // PAIR: the pair-counting scores (measures 4-6) in an instantiation of their own, so that the code of measures 0-3 is what
 // it was before they existed.  W (measure 0 only): the weighted pair mean sum_p(s_p w_p) / P with the handle's fp32 pair
 // weights pw (acav_mi_set_pair_weights), in an instantiation of its own for the same reason
+template <bool PAIR, bool W>
+__device__ __forceinline__ double cand_pair_score(const MiTables &t, int p, int id, long long n)
+{
+    if constexpr (PAIR) {
+        return pair_count_score(t.asg, t.D, t.C, p, t.pairs, id, t.Nc, t.ac, t.bc, t.ps, n, t.measure);
+    } else if constexpr (W) {
+        return mi_pair_score(t.asg, t.D, t.C, p, t.pairs, id, t.Nc, t.ac, t.bc, t.SN, t.Sa, t.Sb, t.phi, n) * (double)t.pw[p];
+    } else {
+        if (t.measure == 1)
+            return ami_pair_score(t.asg, t.D, t.C, p, t.pairs, id, t.Nc, t.ac, t.bc, t.SN, t.Sa, t.Sb, t.phi, t.lnk, t.lf, n, t.avg);
+        if (t.measure == 2)
+            return nmi_pair_score(t.asg, t.D, t.C, p, t.pairs, id, t.Nc, t.ac, t.bc, t.SN, t.Sa, t.Sb, t.phi, t.lnk, n, t.avg);
+        if (t.measure == 3) return 1.0;
+        return mi_pair_score(t.asg, t.D, t.C, p, t.pairs, id, t.Nc, t.ac, t.bc, t.SN, t.Sa, t.Sb, t.phi, n);
+    }
+}
+template <bool PAIR>
+__device__ __forceinline__ double cand_pair_mean(const MiTables &t, double tot, long long n)
+{  // scores.mean(-1); Rand's shared denominator joins the division
+    if constexpr (PAIR)
+        if (t.measure == 5) return tot / ((double)t.P * (double)(n * (n + 1) / 2));
+    return tot / (double)t.P;
+}
+
+// update_cache (one pick; update_cache_celf, efficient.py:188-196, is the same): clip `id` joins the tables.  One workgroup,
+// thread tid of 256
+template <bool PAIR>
+__device__ __forceinline__ void commit_pick(const MiTables &t, int id, int tid)
+{
+    for (int p = tid; p < t.P; p += 256) {
+        const int *row = t.asg + (size_t)id * t.D;
+        const int i = row[t.pairs[2 * p]], j = row[t.pairs[2 * p + 1]];
+        const size_t cell = ((size_t)p * t.C + i) * t.C + j;
+        const int cN = t.Nc[cell], ca = t.ac[(size_t)p * t.C + j], cb = t.bc[(size_t)p * t.C + i];
+        // every load ahead of the first store: the commit is on the critical path of every pick, and the view's pointers
+        // carry no __restrict__, so a store would hold the loads after it back
+        PairStat st{};
+        if constexpr (PAIR) st = t.ps[p];
+        const double sN = t.SN[p] - t.phi[cN] + t.phi[cN + 1];
+        const double sa = t.Sa[p] - t.phi[ca] + t.phi[ca + 1];
+        const double sb = t.Sb[p] - t.phi[cb] + t.phi[cb + 1];
+        t.Nc[cell] = cN + 1;
+        t.ac[(size_t)p * t.C + j] = ca + 1;
+        t.bc[(size_t)p * t.C + i] = cb + 1;
+        t.SN[p] = sN;
+        t.Sa[p] = sa;
+        t.Sb[p] = sb;
+        if constexpr (PAIR) {  // the running pair sums (update_cache, efficient_pair.py:74-81: cache += the pick's deltas)
+            st.tab += cN, st.ta += ca, st.tb += cb;
+            st.rtp = st.tab ? 0 : st.rtp + 1;
+            st.rfp = st.ta - st.tab ? 0 : st.rfp + (ca == 0 ? t.C - 1 : 0);
+            st.rfn = st.tb - st.tab ? 0 : st.rfn + (cb == 0 ? t.C - 1 : 0);
+            t.ps[p] = st;
+        }
+    }
+}
+
 // One pick of one candidate list, the whole of it (scoring, reduction, commit), as the device function that both kernels
-// are made of.  G says which of the list's workgroups this one is: the launch's own grid for k_mi_exact_iter (ExactGridOwn:
-// the kernel compiles to what it was before the function existed), a slice of the launch's grid for k_mi_exact_iter_multi
-// (ExactGridSlice).  A chunk's picks therefore cannot depend on which of the two ran it.
+// are made of.  G says which of the list's workgroups this one is: the launch's own grid for k_mi_exact_iter (ExactGridOwn),
+// a slice of the launch's grid for k_mi_exact_iter_multi (ExactGridSlice).  A chunk's picks therefore cannot depend on
+// which of the two ran it.
 struct ExactGridOwn {
     __device__ __forceinline__ unsigned blk() const { return blockIdx.x; }
     __device__ __forceinline__ unsigned nblk() const { return gridDim.x; }
@@ -770,48 +849,24 @@ struct ExactGridSlice {
 };
 template <bool PAIR, bool W, class G>
 __device__ __forceinline__ void exact_iter(
-    const G grid,
-    const int *__restrict__ asg, int D, int C, int P, const int *__restrict__ pairs, const int *__restrict__ A, int L,
-    unsigned char *__restrict__ removed, int *__restrict__ Nc, int *__restrict__ ac, int *__restrict__ bc,
-    double *__restrict__ SN, double *__restrict__ Sa, double *__restrict__ Sb, const double *__restrict__ phi,
-    MiScalars *__restrict__ sc, ExactBest *__restrict__ blockbest, unsigned *__restrict__ ticket,
-    long long *__restrict__ S_out, double *__restrict__ G_out, const int *__restrict__ forced,
-    double *__restrict__ trace_scores, int *__restrict__ trace_argmax, int measure, const double *__restrict__ lnk,
-    const double *__restrict__ lf, int avg, PairStat *__restrict__ ps, const float *__restrict__ pw)
+    const G grid, const MiTables &c, const int *__restrict__ A, int L, unsigned char *__restrict__ removed,
+    ExactBest *__restrict__ blockbest, unsigned *__restrict__ ticket, long long *__restrict__ S_out,
+    double *__restrict__ G_out, const int *__restrict__ forced, double *__restrict__ trace_scores,
+    int *__restrict__ trace_argmax)
 {
-    // measure 0: calc_MI ('mi' / 'mem_mi'); 1: calc_AMI ('ami'); 2: calc_NMI (mi.py:262-271); 3: ConstantMeasure (mi.py:274-281:
-    // every candidate scores 1, the first remaining one is taken); 4 / 5 / 6: Fowlkes-Mallows / Rand / adjusted Rand
-    // (efficient_pair.py; ps holds their per-pair sums).  avg: average_method of 1 and 2
-    auto pair_score = [&](int p, int id, long long n) -> double {
-        if constexpr (PAIR) {
-            return pair_count_score(asg, D, C, p, pairs, id, Nc, ac, bc, ps, n, measure);
-        } else if constexpr (W) {
-            return mi_pair_score(asg, D, C, p, pairs, id, Nc, ac, bc, SN, Sa, Sb, phi, n) * (double)pw[p];
-        } else {
-            if (measure == 1) return ami_pair_score(asg, D, C, p, pairs, id, Nc, ac, bc, SN, Sa, Sb, phi, lnk, lf, n, avg);
-            if (measure == 2) return nmi_pair_score(asg, D, C, p, pairs, id, Nc, ac, bc, SN, Sa, Sb, phi, lnk, n, avg);
-            if (measure == 3) return 1.0;
-            return mi_pair_score(asg, D, C, p, pairs, id, Nc, ac, bc, SN, Sa, Sb, phi, n);
-        }
-    };
-    auto pair_mean = [&](double tot, long long n) -> double {  // scores.mean(-1); Rand's shared denominator joins the division
-        if constexpr (PAIR)
-            if (measure == 5) return tot / ((double)P * (double)(n * (n + 1) / 2));
-        return tot / (double)P;
-    };
     __shared__ double sS[4];
     __shared__ int sP[4];
     __shared__ int sLast;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int w = grid.blk() * 256 + tid;
-    const long long nc = sc->nc;
+    const long long nc = c.sc->nc;
     double s = -INFINITY;
     int pos = 0x7fffffff;
     if (w < L && !removed[w]) {
         const int id = A[w];
         double tot = 0.0;
-        for (int p = 0; p < P; ++p) tot = tot + pair_score(p, id, nc);
-        s = pair_mean(tot, nc);
+        for (int p = 0; p < c.P; ++p) tot = tot + cand_pair_score<PAIR, W>(c, p, id, nc);
+        s = cand_pair_mean<PAIR>(c, tot, nc);
         pos = w;
     }
     if (trace_scores && w < L) trace_scores[w] = pos == w ? s : (double)NAN;
@@ -856,41 +911,23 @@ __device__ __forceinline__ void exact_iter(
         if (forced) {
             pos = *forced;
             double tot = 0.0;
-            for (int p = 0; p < P; ++p) tot = tot + pair_score(p, A[pos], nc);
-            s = pair_mean(tot, nc);
+            for (int p = 0; p < c.P; ++p) tot = tot + cand_pair_score<PAIR, W>(c, p, A[pos], nc);
+            s = cand_pair_mean<PAIR>(c, tot, nc);
         }
         sP[0] = pos;
         *S_out = (long long)A[pos];
         *G_out = s;
         removed[pos] = 1;
         *ticket = 0u;
-        sc->nc = nc + 1;
+        c.sc->nc = nc + 1;
     }
     __syncthreads();
-    const int id = A[sP[0]];
-    for (int p = tid; p < P; p += 256) {  // update_cache: one pick
-        const int *row = asg + (size_t)id * D;
-        const int i = row[pairs[2 * p]], j = row[pairs[2 * p + 1]];
-        const size_t cell = ((size_t)p * C + i) * C + j;
-        const int cN = Nc[cell], ca = ac[(size_t)p * C + j], cb = bc[(size_t)p * C + i];
-        PairStat st{};
-        if constexpr (PAIR) st = ps[p];  // loaded beside the counts: the commit is on the critical path of every pick
-        Nc[cell] = cN + 1;
-        ac[(size_t)p * C + j] = ca + 1;
-        bc[(size_t)p * C + i] = cb + 1;
-        SN[p] = SN[p] - phi[cN] + phi[cN + 1];
-        Sa[p] = Sa[p] - phi[ca] + phi[ca + 1];
-        Sb[p] = Sb[p] - phi[cb] + phi[cb + 1];
-        if constexpr (PAIR) {  // the running pair sums (update_cache, efficient_pair.py:74-81: cache += the pick's deltas)
-            st.tab += cN, st.ta += ca, st.tb += cb;
-            st.rtp = st.tab ? 0 : st.rtp + 1;
-            st.rfp = st.ta - st.tab ? 0 : st.rfp + (ca == 0 ? C - 1 : 0);
-            st.rfn = st.tb - st.tab ? 0 : st.rfn + (cb == 0 ? C - 1 : 0);
-            ps[p] = st;
-        }
-    }
+    commit_pick<PAIR>(c, A[sP[0]], tid);
 }
 
+// The tables arrive member by member and the view is formed here: only a kernel's own pointer parameters can be __restrict__,
+// and without it this kernel is slower (measured with the view as the argument: ami + 9 %, the others + 0.5 to 2 %;
+// profiles/exact_fold_ab.txt)
 template <bool PAIR, bool W = false>
 __global__ __launch_bounds__(256) void k_mi_exact_iter(
     const int *__restrict__ asg, int D, int C, int P, const int *__restrict__ pairs, const int *__restrict__ A, int L,
@@ -901,46 +938,37 @@ __global__ __launch_bounds__(256) void k_mi_exact_iter(
     double *__restrict__ trace_scores, int *__restrict__ trace_argmax, int measure, const double *__restrict__ lnk,
     const double *__restrict__ lf, int avg, PairStat *__restrict__ ps, const float *__restrict__ pw)
 {
-    exact_iter<PAIR, W>(ExactGridOwn(), asg, D, C, P, pairs, A, L, removed, Nc, ac, bc, SN, Sa, Sb, phi, sc,
-                        blockbest, ticket, S_out, G_out, forced, trace_scores, trace_argmax, measure, lnk, lf, avg, ps, pw);
+    const MiTables c{asg, D, C, P, pairs, Nc, ac, bc, SN, Sa, Sb, phi, sc, measure, lnk, lf, avg, ps, pw};
+    exact_iter<PAIR, W>(ExactGridOwn(), c, A, L, removed, blockbest, ticket, S_out, G_out, forced, trace_scores, trace_argmax);
 }
 
 // ------------------------------------------------------------------- exact greedy, several chunks in lockstep
 // acav_mi_run_exact_multi: ONE launch serves one pick of every chunk that still has picks to make.  A workgroup belongs to one
 // chunk: block_chunk[blockIdx.x] names its descriptor, and block0 of the descriptor makes it the (blockIdx.x - block0)-th of
-// the chunk's nblk workgroups.  Everything after that is exact_iter on the chunk's own pointers, blockbest slice and ticket:
+// the chunk's nblk workgroups.  Everything after that is exact_iter on the chunk's own tables, list, blockbest slice and ticket:
 // nothing crosses chunks on the device.  The host orders the descriptors by their number of picks, descending, so the chunks
 // alive at pick `it` are a prefix and the grid of that launch is the prefix's block count -- a finished chunk has no
 // workgroup.  The descriptor and the table entry are read through uniform addresses (scalar loads); the per-candidate path
 // is the single-chunk kernel's.  No forced positions and no traces here.
 struct ExactChunk {
-    const int *asg;
-    const int *pairs;
+    MiTables tables;
     const int *A;
     unsigned char *removed;
-    int *Nc, *ac, *bc;
-    double *SN, *Sa, *Sb;
-    const double *phi;
-    MiScalars *sc;
     ExactBest *blockbest;
     unsigned *ticket;
     long long *S_out;
     double *G_out;
-    const double *lnk, *lf;
-    PairStat *ps;
-    const float *pw;
-    int D, C, P, L;
+    int L;
     int block0, nblk;
 };
 
 template <bool PAIR, bool W = false>
 __global__ __launch_bounds__(256) void k_mi_exact_iter_multi(const ExactChunk *__restrict__ cd, const int *__restrict__ block_chunk,
-                                                             int it, int measure, int avg)
+                                                             int it)
 {
     const ExactChunk d = cd[block_chunk[blockIdx.x]];
-    exact_iter<PAIR, W>(ExactGridSlice{blockIdx.x - (unsigned)d.block0, (unsigned)d.nblk}, d.asg, d.D, d.C, d.P, d.pairs, d.A, d.L, d.removed, d.Nc, d.ac, d.bc,
-                        d.SN, d.Sa, d.Sb, d.phi, d.sc, d.blockbest, d.ticket, d.S_out + it, d.G_out + it, nullptr, nullptr,
-                        nullptr, measure, d.lnk, d.lf, avg, d.ps, d.pw);
+    exact_iter<PAIR, W>(ExactGridSlice{blockIdx.x - (unsigned)d.block0, (unsigned)d.nblk}, d.tables, d.A, d.L, d.removed, d.blockbest,
+                        d.ticket, d.S_out + it, d.G_out + it, nullptr, nullptr, nullptr);
 }
 
 // ------------------------------------------------------------------- CELF lazy greedy (acav_mi_run_celf)
@@ -956,20 +984,6 @@ __global__ __launch_bounds__(256) void k_mi_exact_iter_multi(const ExactChunk *_
 // kept current from pick to pick).  One workgroup per pick: it stages the block keys in LDS, extracts the next stale
 // entries in order from them (a block gives its first and second key; a block that gave both is an upper BOUND until it is
 // rescanned), scores them lanes-over-pairs, replays, and rescans the blocks it consumed from.
-struct CelfCtx {
-    const int *asg;
-    int D, C, P;
-    const int *pairs;
-    int *Nc, *ac, *bc;
-    double *SN, *Sa, *Sb;
-    const double *phi;
-    MiScalars *sc;
-    int measure;
-    const double *lnk, *lf;
-    int avg;
-    PairStat *ps;
-    const float *pw;
-};
 struct CelfState {
     double gain;   // EfficientMI.gain: the accumulated gain of the CELF phase
     long long t;   // lookups of the run so far
@@ -978,31 +992,6 @@ constexpr int CELF_NBMAX = 1024;  // block keys staged in LDS; the block size gr
 constexpr int CELF_MMAX = 64;     // widest batch of speculatively scored entries
 constexpr int CELF_PCH = 32;      // pairs scored per pass (LDS: CELF_MMAX * CELF_PCH doubles)
 constexpr long long CELF_ALL = 0x7fffffffffffffffLL;
-
-// the score of k_mi_exact_iter's pair_score / pair_mean, for the same template arguments
-template <bool PAIR, bool W>
-__device__ __forceinline__ double celf_pair_score(const CelfCtx &c, int p, int id, long long n)
-{
-    if constexpr (PAIR) {
-        return pair_count_score(c.asg, c.D, c.C, p, c.pairs, id, c.Nc, c.ac, c.bc, c.ps, n, c.measure);
-    } else if constexpr (W) {
-        return mi_pair_score(c.asg, c.D, c.C, p, c.pairs, id, c.Nc, c.ac, c.bc, c.SN, c.Sa, c.Sb, c.phi, n) * (double)c.pw[p];
-    } else {
-        if (c.measure == 1)
-            return ami_pair_score(c.asg, c.D, c.C, p, c.pairs, id, c.Nc, c.ac, c.bc, c.SN, c.Sa, c.Sb, c.phi, c.lnk, c.lf, n, c.avg);
-        if (c.measure == 2)
-            return nmi_pair_score(c.asg, c.D, c.C, p, c.pairs, id, c.Nc, c.ac, c.bc, c.SN, c.Sa, c.Sb, c.phi, c.lnk, n, c.avg);
-        if (c.measure == 3) return 1.0;
-        return mi_pair_score(c.asg, c.D, c.C, p, c.pairs, id, c.Nc, c.ac, c.bc, c.SN, c.Sa, c.Sb, c.phi, n);
-    }
-}
-template <bool PAIR>
-__device__ __forceinline__ double celf_pair_mean(const CelfCtx &c, double tot, long long n)
-{
-    if constexpr (PAIR)
-        if (c.measure == 5) return tot / ((double)c.P * (double)(n * (n + 1) / 2));
-    return tot / (double)c.P;
-}
 
 // queue order: key (va, sa) sorts before key (vb, sb)
 __device__ __forceinline__ bool celf_key_gt(double va, long long sa, double vb, long long sb)
@@ -1059,37 +1048,10 @@ __device__ __forceinline__ CelfTop2 celf_block_top2(int b, int bs, int L, const 
     return t;
 }
 
-// update_cache_celf (efficient.py:188-196): the accepted clip joins the tables, as k_mi_exact_iter's tail does (one workgroup)
-template <bool PAIR>
-__device__ __forceinline__ void celf_commit_tables(const CelfCtx &c, int id, int tid)
-{
-    for (int p = tid; p < c.P; p += 256) {
-        const int *row = c.asg + (size_t)id * c.D;
-        const int i = row[c.pairs[2 * p]], j = row[c.pairs[2 * p + 1]];
-        const size_t cell = ((size_t)p * c.C + i) * c.C + j;
-        const int cN = c.Nc[cell], ca = c.ac[(size_t)p * c.C + j], cb = c.bc[(size_t)p * c.C + i];
-        PairStat st{};
-        if constexpr (PAIR) st = c.ps[p];
-        c.Nc[cell] = cN + 1;
-        c.ac[(size_t)p * c.C + j] = ca + 1;
-        c.bc[(size_t)p * c.C + i] = cb + 1;
-        c.SN[p] = c.SN[p] - c.phi[cN] + c.phi[cN + 1];
-        c.Sa[p] = c.Sa[p] - c.phi[ca] + c.phi[ca + 1];
-        c.Sb[p] = c.Sb[p] - c.phi[cb] + c.phi[cb + 1];
-        if constexpr (PAIR) {
-            st.tab += cN, st.ta += ca, st.tb += cb;
-            st.rtp = st.tab ? 0 : st.rtp + 1;
-            st.rfp = st.ta - st.tab ? 0 : st.rfp + (ca == 0 ? c.C - 1 : 0);
-            st.rfn = st.tb - st.tab ? 0 : st.rfn + (cb == 0 ? c.C - 1 : 0);
-            c.ps[p] = st;
-        }
-    }
-}
-
 // init_celf_q (efficient.py:169-175): Q_val = the absolute scores of tables + candidate for every remaining candidate,
 // stamp -(position); gain = the last greedy GAIN (prev), or 0
 template <bool PAIR, bool W>
-__global__ __launch_bounds__(256) void k_celf_init(CelfCtx c, const int *__restrict__ A, int L,
+__global__ __launch_bounds__(256) void k_celf_init(MiTables c, const int *__restrict__ A, int L,
                                                    const unsigned char *__restrict__ removed, double *__restrict__ qval,
                                                    long long *__restrict__ qst, CelfState *__restrict__ state,
                                                    const double *__restrict__ prev)
@@ -1105,8 +1067,8 @@ __global__ __launch_bounds__(256) void k_celf_init(CelfCtx c, const int *__restr
     if (removed[w]) return;
     const int id = A[w];
     double tot = 0.0;
-    for (int p = 0; p < c.P; ++p) tot = tot + celf_pair_score<PAIR, W>(c, p, id, nc);
-    qval[w] = celf_pair_mean<PAIR>(c, tot, nc);
+    for (int p = 0; p < c.P; ++p) tot = tot + cand_pair_score<PAIR, W>(c, p, id, nc);
+    qval[w] = cand_pair_mean<PAIR>(c, tot, nc);
 }
 
 // the block keys of every block (one wave per block)
@@ -1125,7 +1087,7 @@ __global__ __launch_bounds__(256) void k_celf_blocks(int L, int bs, int nb, cons
 
 // one CELF pick (one workgroup).  bv / bst / bp: [2][nb] first and second key of every block.  M: widest batch.
 template <bool PAIR, bool W>
-__global__ __launch_bounds__(256) void k_celf_pick(CelfCtx c, const int *__restrict__ A, int L, int bs, int nb,
+__global__ __launch_bounds__(256) void k_celf_pick(MiTables c, const int *__restrict__ A, int L, int bs, int nb,
                                                    unsigned char *removed, double *qval, long long *qst, double *bv,
                                                    long long *bst, int *bp, CelfState *state, int M,
                                                    long long *__restrict__ S_out, double *__restrict__ G_out,
@@ -1201,14 +1163,14 @@ __global__ __launch_bounds__(256) void k_celf_pick(CelfCtx c, const int *__restr
             const int np = min(CELF_PCH, c.P - pc);
             for (int q = tid; q < m * np; q += 256) {
                 const int j = q / np, p = q - j * np;
-                sc[j * CELF_PCH + p] = celf_pair_score<PAIR, W>(c, pc + p, A[eP[j]], nc);
+                sc[j * CELF_PCH + p] = cand_pair_score<PAIR, W>(c, pc + p, A[eP[j]], nc);
             }
             __syncthreads();
             if (tid < m)
                 for (int p = 0; p < np; ++p) tot = tot + sc[tid * CELF_PCH + p];
             __syncthreads();
         }
-        if (tid < m) eD[tid] = celf_pair_mean<PAIR>(c, tot, nc) - gain0;
+        if (tid < m) eD[tid] = cand_pair_mean<PAIR>(c, tot, nc) - gain0;
         __syncthreads();
         // ---- the sequential walk over the batch
         if (tid == 0) {
@@ -1280,7 +1242,7 @@ __global__ __launch_bounds__(256) void k_celf_pick(CelfCtx c, const int *__restr
             bv[nb + b] = t2.v2, bst[nb + b] = t2.s2, bp[nb + b] = t2.p2;
         }
     }
-    celf_commit_tables<PAIR>(c, A[sWin], tid);
+    commit_pick<PAIR>(c, A[sWin], tid);
 }
 
 // ---- the dense form of a pick (a pick that re-scores most of the queue: the first one after the queue was filled against
@@ -1306,7 +1268,7 @@ struct CelfMaxOp {  // the better of two fresh values in walk order: the later o
 };
 
 template <bool PAIR, bool W>
-__global__ __launch_bounds__(256) void k_celf_dense_prep(CelfCtx c, const int *__restrict__ A, int L,
+__global__ __launch_bounds__(256) void k_celf_dense_prep(MiTables c, const int *__restrict__ A, int L,
                                                          const unsigned char *__restrict__ removed,
                                                          const long long *__restrict__ qst, const CelfState *__restrict__ state,
                                                          double *__restrict__ fresh, long long *__restrict__ key_stamp,
@@ -1324,8 +1286,8 @@ __global__ __launch_bounds__(256) void k_celf_dense_prep(CelfCtx c, const int *_
     const long long nc = c.sc->nc;
     const int id = A[w];
     double tot = 0.0;
-    for (int p = 0; p < c.P; ++p) tot = tot + celf_pair_score<PAIR, W>(c, p, id, nc);
-    fresh[w] = celf_pair_mean<PAIR>(c, tot, nc) - state->gain;
+    for (int p = 0; p < c.P; ++p) tot = tot + cand_pair_score<PAIR, W>(c, p, id, nc);
+    fresh[w] = cand_pair_mean<PAIR>(c, tot, nc) - state->gain;
 }
 __global__ __launch_bounds__(256) void k_celf_dense_valkey(int L, const int *__restrict__ idx, const unsigned char *__restrict__ removed,
                                                            const double *__restrict__ qval, unsigned long long *__restrict__ key)
@@ -1379,7 +1341,7 @@ __global__ __launch_bounds__(256) void k_celf_dense_apply(int n, const int *__re
 }
 // acceptance: one more lookup of the accepted entry unless it was the last one re-scored; outputs, state, tables
 template <bool PAIR>
-__global__ __launch_bounds__(256) void k_celf_dense_commit(CelfCtx c, const int *__restrict__ A, const int *__restrict__ order,
+__global__ __launch_bounds__(256) void k_celf_dense_commit(MiTables c, const int *__restrict__ A, const int *__restrict__ order,
                                                            const double *__restrict__ d, const CelfDense *__restrict__ dn,
                                                            CelfState *state, unsigned char *removed,
                                                            long long *__restrict__ S_out, double *__restrict__ G_out,
@@ -1410,7 +1372,7 @@ __global__ __launch_bounds__(256) void k_celf_dense_commit(CelfCtx c, const int 
         *LK_out = lk;
         c.sc->nc = nc + 1;
     }
-    celf_commit_tables<PAIR>(c, A[pos], tid);
+    commit_pick<PAIR>(c, A[pos], tid);
 }
 
 // queue values by original position at the end of a run (-inf: the entry has left the queue)
@@ -3298,10 +3260,6 @@ ACAV_EXPORT int acav_mi_run_greedy_multi(acav_mi **mis, int nchunks, const int64
     return ACAV_OK;
 }
 
-// which score the exact greedy (acav_mi_run_exact) maximises: 0 = calc_MI ('mi', 'mem_mi'; mi.py:85-91), 1 = calc_AMI ('ami',
-// mi.py:212-259), 2 = calc_NMI (EfficientNMI, mi.py:262-271), 3 = ConstantMeasure (mi.py:274-281), 4 / 5 / 6 = Fowlkes-Mallows /
-// Rand / adjusted Rand (correspondence_retrieval efficient_pair.py).  The adjusted and normalised scores read two more host-built
-// tables, ln k and ln k! for k <= V + 1.
 // The device draw stream on its own (tests): `n_words` raw MT19937 words (before tempering) that follow the host state
 // state[624] + idx (0 <= idx <= 624) -> out (host), generated exactly as the greedy loops generate theirs -- an MtStream of W
 // lanes with lane blocks of `blk` words, read back through acquire() / release() in spans of half a slot, so that the ring
@@ -3359,6 +3317,10 @@ static int mi_ensure_log_tables(acav_mi *mi, int64_t kmax)
     return ACAV_OK;
 }
 
+// which score the exact greedy (acav_mi_run_exact) maximises: 0 = calc_MI ('mi', 'mem_mi'; mi.py:85-91), 1 = calc_AMI ('ami',
+// mi.py:212-259), 2 = calc_NMI (EfficientNMI, mi.py:262-271), 3 = ConstantMeasure (mi.py:274-281), 4 / 5 / 6 = Fowlkes-Mallows /
+// Rand / adjusted Rand (correspondence_retrieval efficient_pair.py).  The adjusted and normalised scores read two more host-built
+// tables, ln k and ln k! for k <= V + 1.
 ACAV_EXPORT int acav_mi_set_measure(acav_mi *mi, int measure)
 {
     ACAV_REQUIRE(mi, ACAV_EINVAL, "handle is NULL");
@@ -3439,6 +3401,89 @@ ACAV_EXPORT int acav_mi_get_pair_stats(acav_mi *mi, int64_t *TP, int64_t *FP, in
     return ACAV_OK;
 }
 
+// ---- what acav_mi_run_exact, acav_mi_run_exact_multi and acav_mi_run_celf share on the host
+// range(len(start_indices), subset_size - 1) (mi.py:161): the picks of one call, the whole list at the most
+static int64_t exact_iters(int64_t subset, int ns, int64_t L)
+{
+    const int64_t iters = subset - 1 - ns;
+    return iters < 0 ? 0 : iters > L ? L : iters;
+}
+
+// every candidate is a clip of the handle (c < 0: the single-chunk calls, which name no chunk)
+static int check_candidates(int c, const acav_mi *mi, const int64_t *candidates, int64_t L)
+{
+    char at[24] = "";
+    if (c >= 0) snprintf(at, sizeof(at), "chunk %d: ", c);
+    for (int64_t i = 0; i < L; ++i)
+        ACAV_REQUIRE(candidates[i] >= 0 && candidates[i] < mi->V, ACAV_EINVAL, "%scandidate id %lld outside [0, %lld)", at,
+                     (long long)candidates[i], (long long)mi->V);
+    return ACAV_OK;
+}
+
+// fm / rand score against the tables' pair counts: tables of nc = 0 samples are refused (c as above)
+static int check_start_sample(int c, long long nc)
+{
+    char at[24] = "";
+    if (c >= 0) snprintf(at, sizeof(at), "chunk %d: ", c);
+    ACAV_REQUIRE(nc >= 1, ACAV_EINVAL, "%sfm / rand: the tables hold no sample -- add the start clips first "
+                 "(the reference's pair-count check fails on an empty start)", at);
+    return ACAV_OK;
+}
+
+// Readies a handle for `iters` exact picks from `candidates`, everything ordered on `st`: the list on the device with its
+// removed flags, the block results and their ticket, S / GAIN, and the pair sums.  sampled: the caller has read the scalars
+// and checked the start sample already (the lockstep call, for all its chunks before it touches one)
+static int exact_prepare(acav_mi *mi, hipStream_t st, const int64_t *candidates, int64_t L, int64_t iters, bool sampled = false)
+{
+    ACAV_TRY(mi->A0.ensure(sizeof(int) * (size_t)L));
+    ACAV_TRY(ids_to_device32(mi, candidates, L, mi->stage, mi->A0, st));
+    ACAV_TRY(mi->removed.ensure((size_t)L));
+    ACAV_TRY(mi->blockbest.ensure(sizeof(ExactBest) * (size_t)((L + 255) / 256)));
+    ACAV_TRY(mi->ticket.ensure(sizeof(unsigned)));
+    ACAV_TRY(mi->S.ensure(sizeof(long long) * (size_t)iters));
+    ACAV_TRY(mi->G.ensure(sizeof(double) * (size_t)iters));
+    ACAV_HIP_TRY(hipMemsetAsync(mi->removed.p, 0, (size_t)L, st));
+    ACAV_HIP_TRY(hipMemsetAsync(mi->ticket.p, 0, sizeof(unsigned), st));
+    if (mi->measure < 4) {
+        mi->pst_valid = false;  // the commits of these measures do not maintain pst
+        return ACAV_OK;
+    }
+    if (mi->measure != 6 && !sampled) {
+        MiScalars s{};
+        ACAV_HIP_TRY(hipMemcpyAsync(&s, mi->scalars.p, sizeof(s), hipMemcpyDeviceToHost, st));
+        ACAV_HIP_TRY(hipStreamSynchronize(st));
+        ACAV_TRY(check_start_sample(-1, s.nc));
+    }
+    return pair_stats_init(mi, st);  // the pair-counting scores: their sums start from the tables as they are (init_pair_stats)
+}
+
+// the handle's tables as the exact-greedy and CELF kernels take them
+static MiTables mi_tables(acav_mi *mi)
+{
+    const bool wt = mi->weighted && mi->measure == 0;  // the reference weights calc_MI only (the others override _calc_score)
+    return MiTables{mi->asg.as<int>(), mi->D, mi->C, mi->P, mi->pairs.as<int>(), mi->Nc.as<int>(), mi->ac.as<int>(),
+                    mi->bc.as<int>(), mi->SN.as<double>(), mi->Sa.as<double>(), mi->Sb.as<double>(), mi->phi.as<double>(),
+                    mi->scalars.as<MiScalars>(), mi->measure, mi->lnk.as<double>(), mi->lf.as<double>(), mi->avg,
+                    mi->pst.as<PairStat>(), wt ? mi_weights(mi) : nullptr};
+}
+
+// Enqueues the first n picks of the prepared list (exact_prepare) on the handle's stream, one launch of k_mi_exact_iter each.
+// forced / trace_scores / trace_argmax: device arrays by pick (trace_scores: L doubles per pick), or NULL
+static int exact_enqueue(acav_mi *mi, int64_t L, int64_t n, const int *forced, double *trace_scores, int *trace_argmax)
+{
+    const MiTables t = mi_tables(mi);
+    const auto kernel = t.measure >= 4 ? k_mi_exact_iter<true> : t.pw ? k_mi_exact_iter<false, true> : k_mi_exact_iter<false>;
+    for (int64_t it = 0; it < n; ++it)
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, mi->ctx.stream, t.asg, t.D, t.C, t.P, t.pairs,
+                           mi->A0.as<int>(), (int)L, mi->removed.as<unsigned char>(), t.Nc, t.ac, t.bc, t.SN, t.Sa, t.Sb, t.phi, t.sc,
+                           mi->blockbest.as<ExactBest>(), mi->ticket.as<unsigned>(), mi->S.as<long long>() + it,
+                           mi->G.as<double>() + it, forced ? forced + it : nullptr,
+                           trace_scores ? trace_scores + (size_t)it * (size_t)L : nullptr, trace_argmax ? trace_argmax + it : nullptr,
+                           t.measure, t.lnk, t.lf, t.avg, t.ps, t.pw);
+    ACAV_HIP_TRY(hipGetLastError());
+    return ACAV_OK;
+}
+
 ACAV_EXPORT int acav_mi_run_exact(acav_mi *mi, const int64_t *candidates, int64_t L, int ns, int64_t subset,
                                   int64_t *S_out, double *GAIN_out, int64_t *n_selected, const int64_t *forced_pos,
                                   double *trace_scores, int64_t *trace_argmax)
@@ -3447,27 +3492,14 @@ ACAV_EXPORT int acav_mi_run_exact(acav_mi *mi, const int64_t *candidates, int64_
     ACAV_REQUIRE(L > 0 && L < 0x7fffffff && ns >= 0, ACAV_EINVAL, "bad candidate count %lld", (long long)L);
     ACAV_HIP_TRY(hipSetDevice(mi->ctx.device));
     hipStream_t st = mi->ctx.stream;
-    int64_t iters = subset - 1 - ns;  // range(len(start_indices), subset_size - 1)   (mi.py:161)
-    if (iters < 0) iters = 0;
-    if (iters > L) iters = L;
+    const int64_t iters = exact_iters(subset, ns, L);
     *n_selected = iters;
     if (iters == 0) return ACAV_OK;
-    for (int64_t i = 0; i < L; ++i)
-        ACAV_REQUIRE(candidates[i] >= 0 && candidates[i] < mi->V, ACAV_EINVAL, "candidate id %lld outside [0, %lld)",
-                     (long long)candidates[i], (long long)mi->V);
+    ACAV_TRY(check_candidates(-1, mi, candidates, L));
     if (forced_pos)
         for (int64_t i = 0; i < iters; ++i)
             ACAV_REQUIRE(forced_pos[i] >= 0 && forced_pos[i] < L, ACAV_EINVAL, "forced position out of range");
-    const unsigned grid = (unsigned)((L + 255) / 256);
-    ACAV_TRY(mi->A0.ensure(sizeof(int) * (size_t)L));
-    ACAV_TRY(ids_to_device32(mi, candidates, L, mi->stage, mi->A0));
-    ACAV_TRY(mi->removed.ensure((size_t)L));
-    ACAV_TRY(mi->blockbest.ensure(sizeof(ExactBest) * grid));
-    ACAV_TRY(mi->ticket.ensure(sizeof(unsigned)));
-    ACAV_TRY(mi->S.ensure(sizeof(long long) * (size_t)iters));
-    ACAV_TRY(mi->G.ensure(sizeof(double) * (size_t)iters));
-    ACAV_HIP_TRY(hipMemsetAsync(mi->removed.p, 0, (size_t)L, st));
-    ACAV_HIP_TRY(hipMemsetAsync(mi->ticket.p, 0, sizeof(unsigned), st));
+    ACAV_TRY(exact_prepare(mi, st, candidates, L, iters));
     if (forced_pos) {
         std::vector<int> f32((size_t)iters);
         for (int64_t i = 0; i < iters; ++i) f32[(size_t)i] = (int)forced_pos[i];
@@ -3477,32 +3509,8 @@ ACAV_EXPORT int acav_mi_run_exact(acav_mi *mi, const int64_t *candidates, int64_
     }
     if (trace_scores) ACAV_TRY(mi->tr_sc.ensure(sizeof(double) * (size_t)iters * (size_t)L));
     if (trace_argmax) ACAV_TRY(mi->tr_am.ensure(sizeof(int) * (size_t)iters));
-    if (mi->measure < 4) mi->pst_valid = false;  // the commits below do not maintain pst
-    if (mi->measure >= 4) {  // the pair-counting scores: their sums start from the tables as they are (init_pair_stats)
-        if (mi->measure != 6) {
-            MiScalars s{};
-            ACAV_HIP_TRY(hipMemcpyAsync(&s, mi->scalars.p, sizeof(s), hipMemcpyDeviceToHost, st));
-            ACAV_HIP_TRY(hipStreamSynchronize(st));
-            ACAV_REQUIRE(s.nc >= 1, ACAV_EINVAL, "fm / rand: the tables hold no sample -- add the start clips first "
-                         "(the reference's pair-count check fails on an empty start)");
-        }
-        ACAV_TRY(pair_stats_init(mi));
-    }
-    const bool pair = mi->measure >= 4;
-    const bool wt = mi->weighted && mi->measure == 0;  // the reference weights calc_MI only (the others override _calc_score)
-    const auto exact_kernel = pair ? k_mi_exact_iter<true> : wt ? k_mi_exact_iter<false, true> : k_mi_exact_iter<false>;
-    for (int64_t it = 0; it < iters; ++it) {
-        hipLaunchKernelGGL(exact_kernel, dim3(grid), dim3(256), 0, st, mi->asg.as<int>(), mi->D, mi->C, mi->P,
-                           mi->pairs.as<int>(), mi->A0.as<int>(), (int)L, mi->removed.as<unsigned char>(), mi->Nc.as<int>(),
-                           mi->ac.as<int>(), mi->bc.as<int>(), mi->SN.as<double>(), mi->Sa.as<double>(), mi->Sb.as<double>(),
-                           mi->phi.as<double>(), mi->scalars.as<MiScalars>(), mi->blockbest.as<ExactBest>(),
-                           mi->ticket.as<unsigned>(), mi->S.as<long long>() + it, mi->G.as<double>() + it,
-                           forced_pos ? mi->forced.as<int>() + it : nullptr,
-                           trace_scores ? mi->tr_sc.as<double>() + (size_t)it * (size_t)L : nullptr,
-                           trace_argmax ? mi->tr_am.as<int>() + it : nullptr, mi->measure, mi->lnk.as<double>(), mi->lf.as<double>(),
-                           mi->avg, mi->pst.as<PairStat>(), wt ? mi_weights(mi) : nullptr);
-    }
-    ACAV_HIP_TRY(hipGetLastError());
+    ACAV_TRY(exact_enqueue(mi, L, iters, forced_pos ? mi->forced.as<int>() : nullptr, trace_scores ? mi->tr_sc.as<double>() : nullptr,
+                           trace_argmax ? mi->tr_am.as<int>() : nullptr));
     ACAV_HIP_TRY(hipMemcpyAsync(S_out, mi->S.p, sizeof(long long) * (size_t)iters, hipMemcpyDeviceToHost, st));
     ACAV_HIP_TRY(hipMemcpyAsync(GAIN_out, mi->G.p, sizeof(double) * (size_t)iters, hipMemcpyDeviceToHost, st));
     if (trace_scores)
@@ -3550,13 +3558,9 @@ ACAV_EXPORT int acav_mi_run_exact_multi(acav_mi **mis, int nchunks, const int64_
                      mi->avg);
         ACAV_REQUIRE(mi->weighted == lead->weighted, ACAV_EINVAL, "chunks 0 and %d differ: one has pair weights, the other has none",
                      c);
-        int64_t itc = subset[c] - 1 - ns[c];  // range(len(start_indices), subset_size - 1)   (mi.py:161)
-        itc = itc < 0 ? 0 : itc > L[c] ? L[c] : itc;
-        iters[(size_t)c] = itc;
-        if (itc == 0) continue;  // as the single-chunk call: nothing selected, nothing looked at
-        for (int64_t i = 0; i < L[c]; ++i)
-            ACAV_REQUIRE(candidates[c][i] >= 0 && candidates[c][i] < mi->V, ACAV_EINVAL,
-                         "chunk %d: candidate id %lld outside [0, %lld)", c, (long long)candidates[c][i], (long long)mi->V);
+        iters[(size_t)c] = exact_iters(subset[c], ns[c], L[c]);
+        if (iters[(size_t)c] == 0) continue;  // as the single-chunk call: nothing selected, nothing looked at
+        ACAV_TRY(check_candidates(c, mi, candidates[c], L[c]));
         total_blocks += (L[c] + 255) / 256;
     }
     ACAV_REQUIRE(total_blocks < (1 << 23), ACAV_EINVAL, "%lld candidates in all: too many for one lockstep call",
@@ -3568,21 +3572,18 @@ ACAV_EXPORT int acav_mi_run_exact_multi(acav_mi **mis, int nchunks, const int64_
     std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return iters[(size_t)x] > iters[(size_t)y]; });
     const int nlive = (int)order.size();
     ACAV_HIP_TRY(hipSetDevice(lead->ctx.device));
-    const int measure = lead->measure;
-    const bool pair = measure >= 4;
-    const bool wt = lead->weighted && measure == 0;  // the reference weights calc_MI only
     // whatever a handle was doing on its own stream is over; fm / rand: its tables hold a sample (read, nothing written yet)
+    const bool need_sample = lead->measure == 4 || lead->measure == 5;
     std::vector<MiScalars> sc0((size_t)nchunks);
     for (int c = 0; c < nchunks; ++c) {
         if (iters[(size_t)c] == 0) continue;
-        if (pair && measure != 6)
+        if (need_sample)
             ACAV_HIP_TRY(hipMemcpyAsync(&sc0[(size_t)c], mis[c]->scalars.p, sizeof(MiScalars), hipMemcpyDeviceToHost, mis[c]->ctx.stream));
         ACAV_HIP_TRY(hipStreamSynchronize(mis[c]->ctx.stream));
     }
-    if (pair && measure != 6)
+    if (need_sample)
         for (int c = 0; c < nchunks; ++c)
-            ACAV_REQUIRE(iters[(size_t)c] == 0 || sc0[(size_t)c].nc >= 1, ACAV_EINVAL, "chunk %d: fm / rand: the tables hold no sample -- "
-                         "add the start clips first (the reference's pair-count check fails on an empty start)", c);
+            if (iters[(size_t)c] > 0) ACAV_TRY(check_start_sample(c, sc0[(size_t)c].nc));
     for (int c = 0; c < nchunks; ++c) n_selected[c] = iters[(size_t)c];
     if (nlive == 0) return ACAV_OK;
     hipStream_t st = lead->ctx.stream;
@@ -3593,32 +3594,15 @@ ACAV_EXPORT int acav_mi_run_exact_multi(acav_mi **mis, int nchunks, const int64_
     for (int q = 0; q < nlive; ++q) {
         const int c = order[(size_t)q];
         acav_mi *mi = mis[c];
-        const int64_t itc = iters[(size_t)c];
         const int nblk = (int)((L[c] + 255) / 256);
         if (nchunks > 1) mi->lockstep_member = true;
-        ACAV_TRY(mi->A0.ensure(sizeof(int) * (size_t)L[c]));
-        ACAV_TRY(ids_to_device32(mi, candidates[c], L[c], mi->stage, mi->A0, st));
-        ACAV_TRY(mi->removed.ensure((size_t)L[c]));
-        ACAV_TRY(mi->blockbest.ensure(sizeof(ExactBest) * (size_t)nblk));
-        ACAV_TRY(mi->ticket.ensure(sizeof(unsigned)));
-        ACAV_TRY(mi->S.ensure(sizeof(long long) * (size_t)itc));
-        ACAV_TRY(mi->G.ensure(sizeof(double) * (size_t)itc));
-        ACAV_HIP_TRY(hipMemsetAsync(mi->removed.p, 0, (size_t)L[c], st));
-        ACAV_HIP_TRY(hipMemsetAsync(mi->ticket.p, 0, sizeof(unsigned), st));
-        if (pair) ACAV_TRY(pair_stats_init(mi, st));  // their sums start from the tables as they are (init_pair_stats)
-        else mi->pst_valid = false;                   // the commits below do not maintain pst
+        ACAV_TRY(exact_prepare(mi, st, candidates[c], L[c], iters[(size_t)c], true));
         ExactChunk &d = desc[(size_t)q];
-        d.asg = mi->asg.as<int>(), d.pairs = mi->pairs.as<int>(), d.A = mi->A0.as<int>();
-        d.removed = mi->removed.as<unsigned char>();
-        d.Nc = mi->Nc.as<int>(), d.ac = mi->ac.as<int>(), d.bc = mi->bc.as<int>();
-        d.SN = mi->SN.as<double>(), d.Sa = mi->Sa.as<double>(), d.Sb = mi->Sb.as<double>();
-        d.phi = mi->phi.as<double>(), d.sc = mi->scalars.as<MiScalars>();
+        d.tables = mi_tables(mi);
+        d.A = mi->A0.as<int>(), d.removed = mi->removed.as<unsigned char>();
         d.blockbest = mi->blockbest.as<ExactBest>(), d.ticket = mi->ticket.as<unsigned>();
         d.S_out = mi->S.as<long long>(), d.G_out = mi->G.as<double>();
-        d.lnk = mi->lnk.as<double>(), d.lf = mi->lf.as<double>();
-        d.ps = mi->pst.as<PairStat>(), d.pw = wt ? mi_weights(mi) : nullptr;
-        d.D = mi->D, d.C = mi->C, d.P = mi->P, d.L = (int)L[c];
-        d.block0 = block0, d.nblk = nblk;
+        d.L = (int)L[c], d.block0 = block0, d.nblk = nblk;
         for (int b = 0; b < nblk; ++b) block_chunk[(size_t)(block0 + b)] = q;
         block0 += nblk;
         grid_of[(size_t)q] = (unsigned)block0;
@@ -3627,13 +3611,14 @@ ACAV_EXPORT int acav_mi_run_exact_multi(acav_mi **mis, int nchunks, const int64_
     ACAV_TRY(lead->chunk_blocks.ensure(sizeof(int) * block_chunk.size()));
     ACAV_HIP_TRY(hipMemcpyAsync(lead->chunk_desc.p, desc.data(), sizeof(ExactChunk) * (size_t)nlive, hipMemcpyHostToDevice, st));
     ACAV_HIP_TRY(hipMemcpyAsync(lead->chunk_blocks.p, block_chunk.data(), sizeof(int) * block_chunk.size(), hipMemcpyHostToDevice, st));
-    const auto kernel = pair ? k_mi_exact_iter_multi<true> : wt ? k_mi_exact_iter_multi<false, true> : k_mi_exact_iter_multi<false>;
+    const MiTables &t0 = desc[0].tables;  // measure, average method and weightedness are the lead's in every chunk
+    const auto kernel = t0.measure >= 4 ? k_mi_exact_iter_multi<true> : t0.pw ? k_mi_exact_iter_multi<false, true> : k_mi_exact_iter_multi<false>;
     const int64_t iters_max = iters[(size_t)order[0]];
     int alive = nlive;
     for (int64_t it = 0; it < iters_max; ++it) {
         while (iters[(size_t)order[(size_t)(alive - 1)]] <= it) --alive;  // order[0] lasts until iters_max
         hipLaunchKernelGGL(kernel, dim3(grid_of[(size_t)(alive - 1)]), dim3(256), 0, st, lead->chunk_desc.as<ExactChunk>(),
-                           lead->chunk_blocks.as<int>(), (int)it, measure, lead->avg);
+                           lead->chunk_blocks.as<int>(), (int)it);
     }
     ACAV_HIP_TRY(hipGetLastError());
     for (int q = 0; q < nlive; ++q) {
@@ -3659,14 +3644,10 @@ ACAV_EXPORT int acav_mi_run_celf(acav_mi *mi, const int64_t *candidates, int64_t
                  "bad trace capacity");
     ACAV_HIP_TRY(hipSetDevice(mi->ctx.device));
     hipStream_t st = mi->ctx.stream;
-    int64_t iters = subset - 1 - ns;
-    if (iters < 0) iters = 0;
-    if (iters > L) iters = L;
+    const int64_t iters = exact_iters(subset, ns, L);
     *n_selected = iters;
     if (iters == 0) return ACAV_OK;
-    for (int64_t i = 0; i < L; ++i)
-        ACAV_REQUIRE(candidates[i] >= 0 && candidates[i] < mi->V, ACAV_EINVAL, "candidate id %lld outside [0, %lld)",
-                     (long long)candidates[i], (long long)mi->V);
+    ACAV_TRY(check_candidates(-1, mi, candidates, L));
     // round() of the reference is Python's: half to even, on the same double product
     int64_t greedy = (int64_t)std::nearbyint((double)iters * (1.0 - celf_ratio));
     if (greedy < 0) greedy = 0;
@@ -3678,39 +3659,8 @@ ACAV_EXPORT int acav_mi_run_celf(acav_mi *mi, const int64_t *candidates, int64_t
     const unsigned grid = (unsigned)((L + 255) / 256);
     const int bs = 256 * (int)((L + 256LL * CELF_NBMAX - 1) / (256LL * CELF_NBMAX));
     const int nb = (int)((L + bs - 1) / bs);
-    ACAV_TRY(mi->A0.ensure(sizeof(int) * (size_t)L));
-    ACAV_TRY(ids_to_device32(mi, candidates, L, mi->stage, mi->A0));
-    ACAV_TRY(mi->removed.ensure((size_t)L));
-    ACAV_TRY(mi->blockbest.ensure(sizeof(ExactBest) * grid));
-    ACAV_TRY(mi->ticket.ensure(sizeof(unsigned)));
-    ACAV_TRY(mi->S.ensure(sizeof(long long) * (size_t)iters));
-    ACAV_TRY(mi->G.ensure(sizeof(double) * (size_t)iters));
-    ACAV_HIP_TRY(hipMemsetAsync(mi->removed.p, 0, (size_t)L, st));
-    ACAV_HIP_TRY(hipMemsetAsync(mi->ticket.p, 0, sizeof(unsigned), st));
-    if (mi->measure < 4) mi->pst_valid = false;
-    if (mi->measure >= 4) {
-        if (mi->measure != 6) {
-            MiScalars s{};
-            ACAV_HIP_TRY(hipMemcpyAsync(&s, mi->scalars.p, sizeof(s), hipMemcpyDeviceToHost, st));
-            ACAV_HIP_TRY(hipStreamSynchronize(st));
-            ACAV_REQUIRE(s.nc >= 1, ACAV_EINVAL, "fm / rand: the tables hold no sample -- add the start clips first "
-                         "(the reference's pair-count check fails on an empty start)");
-        }
-        ACAV_TRY(pair_stats_init(mi));
-    }
-    const bool pair = mi->measure >= 4;
-    const bool wt = mi->weighted && mi->measure == 0;
-    const auto exact_kernel = pair ? k_mi_exact_iter<true> : wt ? k_mi_exact_iter<false, true> : k_mi_exact_iter<false>;
-    for (int64_t it = 0; it < greedy; ++it) {
-        hipLaunchKernelGGL(exact_kernel, dim3(grid), dim3(256), 0, st, mi->asg.as<int>(), mi->D, mi->C, mi->P,
-                           mi->pairs.as<int>(), mi->A0.as<int>(), (int)L, mi->removed.as<unsigned char>(), mi->Nc.as<int>(),
-                           mi->ac.as<int>(), mi->bc.as<int>(), mi->SN.as<double>(), mi->Sa.as<double>(), mi->Sb.as<double>(),
-                           mi->phi.as<double>(), mi->scalars.as<MiScalars>(), mi->blockbest.as<ExactBest>(),
-                           mi->ticket.as<unsigned>(), mi->S.as<long long>() + it, mi->G.as<double>() + it, nullptr, nullptr,
-                           nullptr, mi->measure, mi->lnk.as<double>(), mi->lf.as<double>(), mi->avg, mi->pst.as<PairStat>(),
-                           wt ? mi_weights(mi) : nullptr);
-    }
-    ACAV_HIP_TRY(hipGetLastError());
+    ACAV_TRY(exact_prepare(mi, st, candidates, L, iters));
+    ACAV_TRY(exact_enqueue(mi, L, greedy, nullptr, nullptr, nullptr));
     const size_t cap = (size_t)trace_cap;
     if (celf > 0) {
         ACAV_TRY(mi->celf_val.ensure(sizeof(double) * (size_t)L));
@@ -3728,10 +3678,8 @@ ACAV_EXPORT int acav_mi_run_celf(acav_mi *mi, const int64_t *candidates, int64_t
             ACAV_TRY(mi->tr_sc.ensure(sizeof(double) * (size_t)celf * cap));
             ACAV_HIP_TRY(hipMemsetAsync(mi->tr_sc.p, 0xFF, sizeof(double) * (size_t)celf * cap, st));  // NaN
         }
-        const CelfCtx cx{mi->asg.as<int>(), mi->D, mi->C, mi->P, mi->pairs.as<int>(), mi->Nc.as<int>(), mi->ac.as<int>(),
-                         mi->bc.as<int>(), mi->SN.as<double>(), mi->Sa.as<double>(), mi->Sb.as<double>(), mi->phi.as<double>(),
-                         mi->scalars.as<MiScalars>(), mi->measure, mi->lnk.as<double>(), mi->lf.as<double>(), mi->avg,
-                         mi->pst.as<PairStat>(), wt ? mi_weights(mi) : nullptr};
+        const MiTables cx = mi_tables(mi);
+        const bool pair = cx.measure >= 4, wt = cx.pw != nullptr;
         const auto init_kernel = pair ? k_celf_init<true, false> : wt ? k_celf_init<false, true> : k_celf_init<false, false>;
         const auto pick_kernel = pair ? k_celf_pick<true, false> : wt ? k_celf_pick<false, true> : k_celf_pick<false, false>;
         hipLaunchKernelGGL(init_kernel, dim3(grid), dim3(256), 0, st, cx, mi->A0.as<int>(), (int)L,

@@ -2,6 +2,7 @@
 numpy restatement (tests/_pair_measures.py, bit for bit), the reference's goldens (tests/golden/gen_golden_pair.py) and
 sklearn's pair-counting scores."""
 import csv
+import ctypes as C
 import itertools
 import json
 import os
@@ -195,6 +196,74 @@ def test_errors_are_loud(env):
         _lib.check(_lib._lib.acav_mi_set_average_method(m._h, 3))
     with pytest.raises(ValueError, match="no sample"):
         _measure("fm", a, 4, [(0, 1)], range(50)).run_greedy(10, [])
+
+
+# ------------------------------------------------------------------ an empty start, through the three entry points
+def _empty_start_case(measure, seeds=((),)):
+    """V = 64, D = 3, C = 4, all 3 pairs, every id a candidate; one handle per entry of `seeds`, holding those start clips"""
+    a = _correlated(7, 64, 3, 4)
+    pairs = list(itertools.combinations(range(3), 2))
+    ms = [_measure(measure, a, 4, pairs, range(64)) for _ in seeds]
+    for m, s in zip(ms, seeds):
+        m.add_samples(list(s))
+    return ms
+
+
+def _table_n(m):
+    from acav100m_amd import _lib
+    n = C.c_int64(-1)
+    _lib.check(_lib._lib.acav_mi_get_counts(m._h, None, None, None, C.byref(n)))
+    return n.value
+
+
+def _raw_exact_multi(ms, subset):
+    """acav_mi_run_exact_multi on the handles' own candidate lists, ns = 0, outputs pre-filled: rc, S, G, n_selected"""
+    from acav100m_amd import _lib
+    n = len(ms)
+    S = [np.full(subset, -7, np.int64) for _ in ms]
+    G = [np.full(subset, -7.0, np.float64) for _ in ms]
+    nsel = np.full(n, -7, np.int64)
+    parr = lambda xs: (C.c_void_p * n)(*[x.value if isinstance(x, C.c_void_p) else x for x in xs])  # noqa: E731
+    cands = [np.ascontiguousarray(m.candidate_ids, np.int64) for m in ms]
+    rc = _lib._lib.acav_mi_run_exact_multi(parr([m._h for m in ms]), n, parr([_lib.ptr(c) for c in cands]),
+                                           _lib.ptr(np.array([len(c) for c in cands], np.int64)), _lib.ptr(np.zeros(n, np.int32)),
+                                           _lib.ptr(np.full(n, subset, np.int64)), parr([_lib.ptr(x) for x in S]),
+                                           parr([_lib.ptr(x) for x in G]), _lib.ptr(nsel))
+    return rc, S, G, nsel
+
+
+@pytest.mark.parametrize("measure", ["fm", "rand"])
+def test_empty_start_is_refused_by_every_entry_point(env, measure):
+    """fm / rand on tables that hold no sample: acav_mi_run_exact, acav_mi_run_celf and acav_mi_run_exact_multi (chunk 0 holds
+    one start clip, chunk 1 none) refuse, and the tables keep the n they had; the lockstep call names the chunk and leaves
+    its pre-filled outputs alone"""
+    from acav100m_amd import _lib
+    for kw in ({}, {"celf_ratio": 0.5}):
+        m, = _empty_start_case(measure)
+        with pytest.raises(ValueError, match="hold no sample"):
+            m.run_greedy(4, [], **kw)
+        assert _table_n(m) == 0
+    ms = _empty_start_case(measure, seeds=((5,), ()))
+    rc, S, G, nsel = _raw_exact_multi(ms, 4)
+    assert _lib._lib.acav_last_error().decode().startswith("chunk 1: ")
+    with pytest.raises(ValueError, match="hold no sample"):
+        _lib.check(rc)
+    assert [_table_n(m) for m in ms] == [1, 0]
+    assert (nsel == -7).all() and all((s == -7).all() for s in S) and all((g == -7.0).all() for g in G)
+
+
+def test_arand_runs_from_an_empty_start_the_same_everywhere(env):
+    """arand needs no start sample: 3 picks for a subset of 4, the same three through the plain call, the CELF call at
+    celf_ratio 0.5 and the lockstep call"""
+    plain, = _empty_start_case("arand")
+    S_plain = plain.run_greedy(4, [])[0]
+    lazy, = _empty_start_case("arand")
+    S_lazy = lazy.run_greedy(4, [], celf_ratio=0.5)[0]
+    ms = _empty_start_case("arand", seeds=((), ()))
+    rc, S, _, nsel = _raw_exact_multi(ms, 4)
+    assert rc == 0 and nsel.tolist() == [3, 3]
+    assert len(S_plain) == 3 and S_plain == S_lazy == S[0][:3].tolist() == S[1][:3].tolist()
+    assert [_table_n(m) for m in (plain, lazy, *ms)] == [3, 3, 3, 3]
 
 
 # ------------------------------------------------------------------ CLI

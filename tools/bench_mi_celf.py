@@ -6,7 +6,7 @@ included).  The library call alone is timed (median of 3), for all picks and for
 whole call over its picks, `*_us_per_pick_steady` the difference of the two over the remaining picks.  One JSON line per
 shape, with mean / median / p99 / max LOOKUPS.
 
-    python tools/bench_mi_celf.py [--v 200000] [--picks 2000] [--prefix 200] [--limit 600]
+    python tools/bench_mi_celf.py [--v 200000] [--picks 2000] [--prefix 200] [--limit 600] [--measure mi]
 
 Every shape runs in a child process under --limit seconds."""
 import argparse
@@ -21,7 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def one(v, c, d, picks, prefix, reps=3):
+def one(v, c, d, picks, prefix, measure, reps=3):
     import ctypes as C
     import numpy as np
     import acav100m_amd
@@ -32,11 +32,11 @@ def one(v, c, d, picks, prefix, reps=3):
     comp = rs.randint(0, c, size=v)
     a = np.stack([np.where(rs.rand(v) < 0.5, comp, rs.randint(0, c, size=v)) for _ in range(d)], 1).astype(np.int64)
     pairs = list(itertools.combinations(range(d), 2))
-    res = dict(V=v, C=c, P=len(pairs), picks=picks, prefix=prefix, reps=reps)
+    res = dict(measure=measure, V=v, C=c, P=len(pairs), picks=picks, prefix=prefix, reps=reps)
 
     def call(ratio, n):
         """seconds of ONE library call (n picks, from the table state after the greedy prefix), and its LOOKUPS"""
-        m = get_measure("mi")(a, ncentroids=c, device="cuda:0")
+        m = get_measure(measure)(a, ncentroids=c, device="cuda:0")
         m.init(pairs, list(range(1, v)))
         m.run_greedy(prefix + 2, [0])
         cand = np.ascontiguousarray(m.candidate_ids, np.int64)
@@ -71,13 +71,14 @@ if __name__ == "__main__":
     ap.add_argument("--picks", type=int, default=2000)
     ap.add_argument("--prefix", type=int, default=200)
     ap.add_argument("--limit", type=int, default=600)
+    ap.add_argument("--measure", default="mi")  # any exact-greedy measure of the registry
     ap.add_argument("--child", type=int, default=0)
     args = ap.parse_args()
     if args.child:
-        one(args.v, args.c, args.child, args.picks, args.prefix)
+        one(args.v, args.c, args.child, args.picks, args.prefix, args.measure)
     else:
         for d in (3, 10):  # P = 3, P = 45
             rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", str(d), "--v", str(args.v), "--c", str(args.c),
-                                 "--picks", str(args.picks), "--prefix", str(args.prefix)], timeout=args.limit).returncode
+                                 "--picks", str(args.picks), "--prefix", str(args.prefix), "--measure", args.measure], timeout=args.limit).returncode
             if rc != 0:
                 sys.exit(rc)
