@@ -9,7 +9,10 @@ import time
 from pathlib import Path
 
 from ..config import SUBSET_DEFAULTS, merge, parse_cli
-from .run import compare_measures, merge_all_csvs, reduce_all_pkls, run_chunks, run_single
+from .run import compare_measures, lockstep_supported, merge_all_csvs, reduce_all_pkls, run_chunks, run_single
+from .run_contrastive import merge_contrastive, run_chunks_contrastive, run_single_contrastive
+from .run_greedy import check_celf_ratio, check_weight_type
+from .run_pca import is_pca_measure, run_chunks_pca, run_single_pca
 
 
 def get_args(**kwargs):
@@ -47,40 +50,45 @@ def prepare(**kwargs):
     return args
 
 
+def check_run(args):
+    """what a run cannot combine, refused once, before any shard is read (the drivers below do not check again)"""
+    pca = is_pca_measure(args.measure_name)
+    check_weight_type(args.measure_name, args.clustering.weight_type)
+    check_celf_ratio(args.measure_name, args.get('celf_ratio', 0))
+    # a lockstep width means something to a chunked run only; the pca measures refuse it without a chunk_size too
+    if int(args.computation.concurrent_chunks or 1) > 1 and (args.chunk_size is not None or pca):
+        lockstep_supported(args.measure_name, args.get('celf_ratio', 0))
+    dim = args.pca.dim if pca and args.pca else None
+    if dim is not None and (isinstance(dim, bool) or not isinstance(dim, int) or dim < 1):
+        raise ValueError("pca.dim={!r} must be a positive integer or None".format(dim))
+
+
 def run(args):
     """cli.py:90-100"""
-    from .run_greedy import check_celf_ratio, check_weight_type
-    check_weight_type(args.measure_name, args.clustering.weight_type)  # before any shard is read
-    check_celf_ratio(args.measure_name, args.get('celf_ratio', 0))
-    from .run_pca import is_pca_measure
+    check_run(args)
     if is_pca_measure(args.measure_name):  # pca, pca_ip, pca_cs, pca_l1, pca_l2: they read feature shards (run_pca.py)
-        from .run_pca import check_pca_run, run_chunks_pca, run_single_pca
-        check_pca_run(args)  # a lockstep width is refused here too, before any shard is read
         return run_single_pca(args) if args.chunk_size is None else run_chunks_pca(args)
     if args.measure_name == 'contrastive':
-        from .run_contrastive import run_chunks_contrastive, run_single_contrastive
         return run_single_contrastive(args) if args.chunk_size is None else run_chunks_contrastive(args)
     return run_single(args) if args.chunk_size is None else run_chunks(args)
 
 
+def _timed(verb, kwargs):
+    start = time.time()
+    out = verb(prepare(**kwargs))
+    print('done. total time elasped: {}'.format(datetime.timedelta(seconds=time.time() - start)))
+    return out
+
+
 class Cli:
     def run(self, **kwargs):
-        start = time.time()
-        out = run(prepare(**kwargs))
-        print('done. total time elasped: {}'.format(datetime.timedelta(seconds=time.time() - start)))
-        return out
+        return _timed(run, kwargs)
 
     def reduce_csvs(self, **kwargs):
-        start = time.time()
-        out = merge_all_csvs(prepare(**kwargs))
-        print('done. total time elasped: {}'.format(datetime.timedelta(seconds=time.time() - start)))
-        return out
+        return _timed(merge_all_csvs, kwargs)
 
     def reduce_pkls(self, **kwargs):
-        start = time.time()
-        out = reduce_all_pkls(prepare(**kwargs))
-        print('done. total time elasped: {}'.format(datetime.timedelta(seconds=time.time() - start)))
-        return out
+        return _timed(reduce_all_pkls, kwargs)
 
     def reduce(self, **kwargs):
         """cli.py:69-78: csv caches or pickle caches, whichever the run wrote"""
@@ -98,7 +106,6 @@ class Cli:
         return evaluate(prepare(**kwargs))
 
     def merge_contrastive(self, **kwargs):
-        from .run_contrastive import merge_contrastive
         return merge_contrastive(prepare(**kwargs))
 
 
@@ -114,23 +121,13 @@ def main(argv=None):
     from ..parallel import launch
     if launch.env_world() is None:
         if command == 'run' and kwargs.get('chunk_size') is not None:
-            import torch
-            want = kwargs.get('computation.num_gpus')
-            have = torch.cuda.device_count()
-            if os.environ.get('ACAV_OVERSUBSCRIBE') == '1':  # tests: several processes share a GPU
-                have = max(have, int(want or have))
-            want = have if want is None else min(int(want), have)
+            want = _spawn_count(kwargs)
             if want > 1:
                 launch.spawn_per_gpu('acav100m_amd.subset_selection.cli', argv, want, {'ACAV_NO_GROUP': '1'})
                 return None
         elif command == 'run' and _contrastive_ddp(kwargs):
             # run_contrastive.py:118-152: the unchunked contrastive run trains and scores with one worker per GPU
-            import torch
-            want = kwargs.get('computation.num_gpus')
-            have = torch.cuda.device_count()
-            if os.environ.get('ACAV_OVERSUBSCRIBE') == '1':
-                have = max(have, int(want or have))
-            want = have if want is None else min(int(want), have)
+            want = _spawn_count(kwargs)
             if want > 1:
                 launch.spawn_per_gpu('acav100m_amd.subset_selection.cli', argv, want)
                 return None
@@ -143,6 +140,16 @@ def main(argv=None):
     return getattr(Cli(), command)(**kwargs)
 
 
+def _spawn_count(kwargs):
+    """how many processes a plainly started run becomes: computation.num_gpus, at most one per GPU"""
+    import torch
+    want = kwargs.get('computation.num_gpus')
+    have = torch.cuda.device_count()
+    if os.environ.get('ACAV_OVERSUBSCRIBE') == '1':  # tests: several processes share a GPU
+        have = max(have, int(want or have))
+    return have if want is None else min(int(want), have)
+
+
 def _contrastive_ddp(kwargs):
     use = kwargs.get('computation.use_distributed')
     use = SUBSET_DEFAULTS['computation']['use_distributed'] if use is None else use
@@ -152,7 +159,6 @@ def _contrastive_ddp(kwargs):
 def _seed_from_env():
     """ACAV_SEED=<int>: seed the torch-stream generator and Python's `random` in this process (the reference's CLIs
     never seed -- `computation.random_seed` is unused there; every process of a spawned run gets the same seed)."""
-    import os
     seed = os.environ.get('ACAV_SEED')
     if seed is not None:
         import random

@@ -5,18 +5,15 @@ Chunks are independent (no collective anywhere on this path): with several GPUs 
 contiguous block of ceil(num_chunks / num_gpus) chunks (utils.split_chunks) and writes per-chunk CSVs
 to caches/, merged later by `cli.py reduce_csvs`.
 """
-import copy
-import math
-import os
 from collections import defaultdict
 from pathlib import Path
 
 import numpy as np
 
 from .. import shards as io
-from ..parallel import world
+from .chunks import plan_chunks, save_chunk
 from .measures import get_measure
-from .run_greedy import _prepare, run_greedy
+from .run_greedy import _prepare, _run_greedy, run_greedy
 
 
 def load_data(shard_paths, metas_path, verbose=False):
@@ -36,12 +33,21 @@ def load_data(shard_paths, metas_path, verbose=False):
     return dict(grouped), io.load_metas(paths, metas_path)
 
 
+def greedy_options(args):
+    """the keywords of run_greedy / _run_greedy / _prepare that come from the configuration"""
+    return dict(measure_name=args.measure_name, cluster_pairing=args.clustering.pairing,
+                shuffle_candidates=args.shuffle_candidates, verbose=args.verbose, weight_type=args.clustering.weight_type,
+                celf_ratio=args.get('celf_ratio', 0))
+
+
 def run_partition(args, shard_paths):
-    assignments, clustering_types, shard_names, filenames = io.load_assignment_shards(shard_paths)
-    return run_greedy(args, assignments, shard_names, filenames, clustering_types, args.subset.size,
-                      args.subset.ratio, measure_name=args.measure_name, cluster_pairing=args.clustering.pairing,
-                      shuffle_candidates=args.shuffle_candidates, verbose=args.verbose, weight_type=args.clustering.weight_type,
-                      celf_ratio=args.get('celf_ratio', 0))
+    return _select_partition(args, io.load_assignment_shards(shard_paths))
+
+
+def _select_partition(args, loaded):
+    assignments, clustering_types, shard_names, filenames = loaded
+    return run_greedy(args, assignments, shard_names, filenames, clustering_types, args.subset.size, args.subset.ratio,
+                      **greedy_options(args))
 
 
 def _load(args, path):
@@ -53,13 +59,9 @@ def _load(args, path):
 
 def _select(args, data):
     results = []
-    for k, (assignments, clustering_types, shard_names, filenames) in data:
+    for k, loaded in data:
         print('running partition {}/{}'.format(k, len(data)))
-        results.append(run_greedy(args, assignments, shard_names, filenames, clustering_types, args.subset.size,
-                                  args.subset.ratio, measure_name=args.measure_name,
-                                  cluster_pairing=args.clustering.pairing, shuffle_candidates=args.shuffle_candidates,
-                                  verbose=args.verbose, weight_type=args.clustering.weight_type,
-                                  celf_ratio=args.get('celf_ratio', 0)))
+        results.append(_select_partition(args, loaded))
     return results
 
 
@@ -97,23 +99,11 @@ def lockstep_supported(measure_name, celf_ratio=0):
 
 def run_chunks(args):
     """chunk.py:21-53 + run_chunks_node :115-131 for THIS process's rank (one process per GPU)."""
-    args.parent_pid = str(args.parent_pid or os.environ.get('ACAV_PARENT_PID') or os.getpid())  # chunk.py:22
-    paths = [p for p in sorted(io.brace_expand(args.data.path)) if Path(p).is_file()]
-    chunks = list(enumerate(io.chunked(paths, int(args.chunk_size))))
-    num_chunks = len(chunks)
-    rank, w = world()
-    gpus = max(1, min(w, num_chunks))
-    chunk_args = copy.deepcopy(args)
-    if isinstance(chunk_args.subset.size, int):
-        chunk_args.subset.size = math.ceil(chunk_args.subset.size / num_chunks)
-    per = math.ceil(num_chunks / gpus)
-    mine = chunks[rank * per:(rank + 1) * per] if rank < gpus else []
-    print("running {} chunks in {} gpus".format(num_chunks, gpus))
-    chunk_args.node_rank = rank
+    plan, chunk_args = plan_chunks(args)
+    mine = plan.mine
     width = int(chunk_args.computation.concurrent_chunks or 1)
     if width > 1:
-        lockstep_supported(chunk_args.measure_name, chunk_args.get('celf_ratio', 0))  # before any shard is read
-        return _run_chunks_lockstep(args, chunk_args, mine, rank, width)
+        return _run_chunks_lockstep(args, chunk_args, plan, width)
     written = []
     # computation.load_async (chunk.py:119-120,197-226): the next chunk's shards are read and parsed by a host
     # thread while the GPU selects from the current one.  Chunks are still consumed in order, so the cache files
@@ -132,24 +122,10 @@ def run_chunks(args):
         else:
             results, metas = _run(chunk_args, chunk)
         res = results[0] if results else []  # a chunk is assumed to be a single partition (chunk.py:152)
-        name = "cache_{}_{}_{}".format(chunk_args.parent_pid, rank, i)
-        written.append(_save_chunk(args, name, res, metas))
+        written.append(save_chunk(args, plan, i, res, metas))
     if pool:
         pool.shutdown()
     return written
-
-
-def _save_chunk(args, name, res, metas):
-    """chunk.py:125-131: the chunk's selection as caches/{name}_output.csv, or -- save_cache_as_csvs=False -- as the
-    pickle caches/{name}.pkl = {'res', 'metas'} that `cli.py reduce_pkls` turns into the csv later"""
-    cache_dir = Path(args.data.output.path).parent / 'caches'
-    if args.save_cache_as_csvs or args.save_cache_as_csvs is None:
-        out_path, _ = io.append_output_csv(res, metas, cache_dir / Path(args.data.output.path).name, name + '_')
-        return out_path
-    cache_dir.mkdir(parents=True, exist_ok=True)
-    out_path = cache_dir / (name + '.pkl')
-    io.dump_pickle({'res': res, 'metas': metas}, out_path)
-    return out_path
 
 
 def reduce_all_pkls(args):
@@ -181,7 +157,6 @@ def reduce_all_pkls(args):
 def compare_measures(args):
     """tests.py:10-46: run several measures on every partition and report how far their selections agree (the
     reference's version stops in a debugger; this one prints and returns the figures)."""
-    from .run_greedy import _run_greedy
     names = args.measure_names or ['mem_mi', 'mi']
     partitions, _ = load_data(args.data.path, args.data.meta.path, args.verbose)
     report = []
@@ -189,9 +164,8 @@ def compare_measures(args):
         assignments, clustering_types, _, _ = io.load_assignment_shards(partitions[k])
         runs = {}
         for name in names:
-            runs[name] = _run_greedy(args, assignments, clustering_types, args.subset.size, args.subset.ratio, measure_name=name,
-                                     cluster_pairing=args.clustering.pairing, shuffle_candidates=False, verbose=False,
-                                     weight_type=args.clustering.weight_type, celf_ratio=args.get('celf_ratio', 0))
+            options = dict(greedy_options(args), measure_name=name, shuffle_candidates=False, verbose=False)
+            runs[name] = _run_greedy(args, assignments, clustering_types, args.subset.size, args.subset.ratio, **options)
         keys = list(runs)
         for a in range(len(keys)):
             for b in range(a + 1, len(keys)):
@@ -205,7 +179,7 @@ def compare_measures(args):
     return report
 
 
-def _run_chunks_lockstep(args, chunk_args, mine, rank, width):
+def _run_chunks_lockstep(args, chunk_args, plan, width):
     """computation.concurrent_chunks = width > 1: `width` chunks at a time share ONE set of kernel launches per
     greedy iteration (the measure class's run_greedy_multi: acav_mi_run_greedy_multi for batch_mi,
     acav_mi_run_exact_multi for the exact-greedy and pair-counting measures) -- the loop of a single chunk is a chain of
@@ -231,15 +205,12 @@ def _run_chunks_lockstep(args, chunk_args, mine, rank, width):
                 continue
             k, (assignments, clustering_types, shard_names, filenames) = data[0]  # single partition (chunk.py:152)
             measure, start, subset = _prepare(chunk_args, assignments, clustering_types, chunk_args.subset.size,
-                                              chunk_args.subset.ratio, chunk_args.measure_name,
-                                              chunk_args.clustering.pairing, chunk_args.shuffle_candidates,
-                                              chunk_args.verbose, generator=Generator(base_seed + 1 + num),
-                                              weight_type=chunk_args.clustering.weight_type,
-                                              celf_ratio=chunk_args.get('celf_ratio', 0))
+                                              chunk_args.subset.ratio, generator=Generator(base_seed + 1 + num),
+                                              **greedy_options(chunk_args))
             prepared.append((measure, start, subset, shard_names, filenames, metas))
         return prepared
 
-    groups = [mine[g0:g0 + width] for g0 in range(0, len(mine), width)]
+    groups = [plan.mine[g0:g0 + width] for g0 in range(0, len(plan.mine), width)]
     pool = ThreadPoolExecutor(1)
     nxt = pool.submit(prepare_group, groups[0]) if groups else None
     for gi, group in enumerate(groups):
@@ -252,17 +223,13 @@ def _run_chunks_lockstep(args, chunk_args, mine, rank, width):
                                    verbose=chunk_args.verbose) if live else []
         ri = 0
         for j, (num, chunk) in enumerate(group):
-            i = g0 + j
             res, metas = [], {}
             if prepared[j] is not None:
                 S = sorted(results[ri][0])
                 ri += 1
                 _, _, _, shard_names, filenames, metas = prepared[j]
                 res = [{'filename': filenames[s], 'shard_name': shard_names[s]} for s in S]
-            name = "cache_{}_{}_{}".format(chunk_args.parent_pid, rank, i)
-            cache_out = Path(args.data.output.path).parent / 'caches' / Path(args.data.output.path).name
-            out_path, _ = io.append_output_csv(res, metas, cache_out, name + '_')
-            written.append(out_path)
+            written.append(save_chunk(args, plan, g0 + j, res, metas))
     pool.shutdown()
     return written
 

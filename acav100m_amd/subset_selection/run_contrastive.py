@@ -2,13 +2,15 @@
 train the audio-visual InfoNCE model on the feature shards, score every clip, write the per-process inference cache;
 `merge_contrastive` sorts the caches by score and writes output.csv.  Host orchestration around
 measures/contrastive.Contrastive; single process per run like the reference's non-distributed path."""
-import os
+import copy
 import shutil
 from pathlib import Path
 
 import numpy as np
 
 from .. import shards as io
+from ..parallel import world
+from .chunks import plan_chunks, resolve_parent_pid, shard_paths
 from .measures.contrastive import Contrastive
 
 VIDEO_KEY, AUDIO_KEY, LAYER = ('SLOWFAST_8x8_R50', 'kinetics-400'), ('VGGish', 'YouTube-8M'), 'layer_4'
@@ -89,7 +91,6 @@ def _train(args, paths, batches, sizes, measure=None):
     print("training contrastive loss" + (" with distributed" if measure.distributed else ""))
     measure.train(args, paths, batches, args.log_every, args.verbose)
     if measure.distributed:  # _train_distributed (:156-168): the master leaves the trained model for the parent to load
-        from ..parallel import world
         if world()[0] == 0:
             import torch
             cache_dir = Path(args.data.output.path).parent / 'caches'
@@ -131,7 +132,6 @@ def _run(args, paths):
         measure = _train(args, paths, batches, sizes)
     scorer = copy_measure(_new_measure(args, sizes), measure)  # _infer (:97-103)
     if scorer.distributed:
-        from ..parallel import world
         args.node_rank = world()[0]  # the inference cache of this process (contrastive.py:243-246: du.get_rank())
         print("inferring with distributed")
     print("(node {}) running inference".format(args.node_rank or 0))
@@ -146,13 +146,12 @@ def _run(args, paths):
 def run_single_contrastive(args):
     """run_contrastive.py:236-247: the whole dataset is scored (subset.size = None, ratio = 1); the selection is made
     afterwards by `merge_contrastive` from the inference caches"""
-    args.parent_pid = str(args.parent_pid or os.environ.get('ACAV_PARENT_PID') or os.getpid())  # one name for all workers
+    resolve_parent_pid(args)  # one name for all workers
     args.node_rank = 0 if args.node_rank is None else args.node_rank
     args.chunk_num = 0 if args.chunk_num is None else args.chunk_num
-    paths = [p for p in sorted(io.brace_expand(args.data.path)) if Path(p).is_file()]
     args.subset.size = None
     args.subset.ratio = 1.0
-    out = _run(args, paths)
+    out = _run(args, shard_paths(args))
     print("done")
     return out
 
@@ -165,27 +164,9 @@ def run_chunks_contrastive(args):
     Deviation, on purpose: the reference cannot finish this mode -- its run_chunk unpacks the `None` that run_contrastive._run
     returns (chunk_contrastive.py:146-148 vs run_contrastive.py:45-51: the `return` sits inside a string literal) and raises
     after the first chunk of every rank.  Here every chunk is processed; the files written per chunk are the reference's."""
-    import copy
-    import math
-    from ..parallel import world
-    args.parent_pid = str(args.parent_pid or os.environ.get('ACAV_PARENT_PID') or os.getpid())
-    paths = [p for p in sorted(io.brace_expand(args.data.path)) if Path(p).is_file()]
-    chunks = list(enumerate(io.chunked(paths, int(args.chunk_size))))
-    num_chunks = len(chunks)
-    rank, w = world()
-    gpus = max(1, min(w, num_chunks))
-    if w > num_chunks:
-        print("num_gpus ({}) exceeds num_chunks ({})".format(w, num_chunks))
-        print("thresholding num_gpus to be equal to num_chunks")
-    chunk_args = copy.deepcopy(args)
-    if isinstance(chunk_args.subset.size, int):
-        chunk_args.subset.size = math.ceil(chunk_args.subset.size / num_chunks)
-    print("running {} chunks in {} gpus".format(num_chunks, gpus))
-    per = math.ceil(num_chunks / gpus)
-    mine = chunks[rank * per:(rank + 1) * per] if rank < gpus else []
-    chunk_args.node_rank = rank
+    plan, chunk_args = plan_chunks(args, announce_excess=True)
     done = []
-    for i, (num, chunk) in enumerate(mine):
+    for i, (num, chunk) in enumerate(plan.mine):
         print("running chunk {}".format(num))
         one = copy.deepcopy(chunk_args)
         one.chunk_num = i

@@ -9,28 +9,12 @@ width; a view narrower than dim, or V <= dim, raises ValueError before any kerne
 clustering.pairing over the keys; PCAOptim; k = subset.size or round(subset.ratio * V); the rows {'filename', 'shard_name'} of
 sorted(S) appended to output.csv.  Chunked: every chunk fits its own PCA and selects from its own clips, one process per GPU,
 into the cache files `reduce_csvs` / `reduce_pkls` merge (run.run_chunks)."""
-import copy
-import math
-import os
 from pathlib import Path
 
 from .. import shards as io
-from ..parallel import world
+from .chunks import plan_chunks, save_chunk, shard_paths
 from .measures import PCA_MEASURES, get_measure
 from .pairing import get_cluster_pairing
-
-
-def check_pca_run(args):
-    """what a pca measure cannot be combined with, refused before any shard is read"""
-    from .run import lockstep_supported
-    from .run_greedy import check_celf_ratio, check_weight_type
-    check_weight_type(args.measure_name, args.clustering.weight_type)
-    check_celf_ratio(args.measure_name, args.get('celf_ratio', 0))
-    if int(args.computation.concurrent_chunks or 1) > 1:
-        lockstep_supported(args.measure_name, args.get('celf_ratio', 0))
-    dim = args.pca.dim if args.pca else None
-    if dim is not None and (isinstance(dim, bool) or not isinstance(dim, int) or dim < 1):
-        raise ValueError("pca.dim={!r} must be a positive integer or None".format(dim))
 
 
 def projected_views(args, table):
@@ -82,13 +66,8 @@ def _run(args, paths):
     return select(args, table)[1], metas
 
 
-def _paths(args):
-    return [p for p in sorted(io.brace_expand(args.data.path)) if Path(p).is_file()]
-
-
 def run_single_pca(args):
-    check_pca_run(args)
-    rows, metas = _run(args, _paths(args))
+    rows, metas = _run(args, shard_paths(args))
     out_path, count = io.append_output_csv(rows, metas, args.data.output.path)
     if args.verbose:
         print("Saved Results: added {} lines to {}".format(count, out_path))
@@ -97,25 +76,12 @@ def run_single_pca(args):
 
 def run_chunks_pca(args):
     """run.run_chunks for THIS process's rank (one process per GPU): chunk after chunk, the same cache file names"""
-    from .run import _save_chunk
-    check_pca_run(args)
-    args.parent_pid = str(args.parent_pid or os.environ.get('ACAV_PARENT_PID') or os.getpid())
-    chunks = list(enumerate(io.chunked(_paths(args), int(args.chunk_size))))
-    num_chunks = len(chunks)
-    rank, w = world()
-    gpus = max(1, min(w, num_chunks))
-    chunk_args = copy.deepcopy(args)
-    if isinstance(chunk_args.subset.size, int):
-        chunk_args.subset.size = math.ceil(chunk_args.subset.size / num_chunks)
-    per = math.ceil(num_chunks / gpus)
-    mine = chunks[rank * per:(rank + 1) * per] if rank < gpus else []
-    print("running {} chunks in {} gpus".format(num_chunks, gpus))
-    chunk_args.node_rank = rank
+    plan, chunk_args = plan_chunks(args)
     written = []
-    for i, (num, chunk) in enumerate(mine):
+    for i, (num, chunk) in enumerate(plan.mine):
         print("running chunk {}".format(num))
         rows, metas = _run(chunk_args, chunk)
-        written.append(_save_chunk(args, "cache_{}_{}_{}".format(chunk_args.parent_pid, rank, i), rows, metas))
+        written.append(save_chunk(args, plan, i, rows, metas))
     return written
 
 

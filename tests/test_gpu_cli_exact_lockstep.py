@@ -61,3 +61,28 @@ def test_lockstep_chunks_equal_sequential_chunks(workdir, measure):
     assert outs[2] == outs[1]
     # 40 per chunk: the start clip + 38 picks each (range(len(start), subset_size - 1))
     assert len(outs[2].splitlines()) == 2 * 39
+
+
+def test_lockstep_chunks_write_pkl_caches_when_asked(workdir):
+    """save_cache_as_csvs=False: the lockstep path writes the pickle caches sequential chunk mode writes, and `reduce_pkls` turns
+    them into the output.csv of the csv route (which equals sequential chunk mode's: the test above)."""
+    from acav100m_amd.subset_selection.cli import Cli
+    root, glob = workdir
+    outs = {}
+    for as_csv in (True, False):
+        out_csv = os.path.join(root, "mem_mi_caches_{}".format("csv" if as_csv else "pkl"), "output.csv")
+        os.makedirs(os.path.dirname(out_csv), exist_ok=True)
+        random.seed(1)
+        Cli().run(shards_path=glob, meta_path=os.path.join(root, "videos"), out_path=out_csv, chunk_size=2, measure_name="mem_mi",
+                  save_cache_as_csvs=as_csv, **{"computation.concurrent_chunks": 2, "computation.random_seed": 7,
+                                                "subset.size": 80})
+        caches = sorted(os.listdir(os.path.join(os.path.dirname(out_csv), "caches")))
+        assert len(caches) == 2 and all(c.startswith("cache_") for c in caches)
+        assert all(c.endswith("_output.csv" if as_csv else ".pkl") for c in caches), caches
+        if as_csv:
+            Cli().reduce_csvs(out_path=out_csv)
+        else:
+            assert Cli().reduce_pkls(out_path=out_csv, save_cache_as_csvs=False) == 2 * 39
+        outs[as_csv] = open(out_csv, "rb").read()
+    assert outs[False] == outs[True]
+    assert len(outs[False].splitlines()) == 2 * 39
