@@ -17,7 +17,7 @@ the rows finds (KMeans.quality, acav_kmeans_quality: float64 distances on the GP
 
     python -m acav100m_amd.clustering.cli evaluate --feature_path=<brace glob .pkl> --meta_path=<dir> \\
         --out_path=<dir of a cluster run> --clustering.cached_epoch=<e | [e0,e1,...]> \\
-        [--evaluate.out_path=quality.json] [--evaluate.rows_path=<dir>]
+        [--evaluate.out_path=quality.json] [--evaluate.rows_path=<dir>] [--evaluate.silhouette_sample=M [--evaluate.silhouette_seed=S]]
 
 Reads cache_epoch_{e}_{name} like a resumed `cluster` run (cache.py: locate, read, find), reads the rows once per row group
 (row_groups.py, data.resident_bytes) and evaluates every listed epoch on them while they are on the device.  Writes no assignment
@@ -30,6 +30,14 @@ after the division: the view is judged in projected space and its report carries
 "pca_explained_variance_ratio" (the kept share of the total variance).  Epochs that disagree on a view's projection are refused.
 evaluate.rows_path: one <shard>.quality.npz per shard with `filename`, `epochs` and, per view, "<model_key>/<layer>" ->
 float64 [epochs, rows, 2] = (a2, b2) -- an outlier or low-margin filter downstream.  One process, one GPU.
+evaluate.silhouette_sample=M (default: off) adds the exact silhouette on a seeded sample (silhouette.py, acav_rows_silhouette):
+the rows sample_indices(total rows, M, evaluate.silhouette_seed) -- sklearn's silhouette_score(sample_size=M, random_state=seed)
+draw, in the global row order the row groups deliver, one set for all views and epochs -- are gathered after the front-end while
+the one pass goes by; afterwards every (epoch, view) labels them with calc_best (a row's label is a pure function of the row and
+the state: these are the labels the pass gave them) and the report gains silhouette_sampled, silhouette_sample,
+silhouette_negative_share and silhouette_by_cluster (silhouette_undefined with the reason, and nan, when the sample has fewer
+than two non-empty clusters).  Neither a centre nor a scale enters: it is the figure to compare runs that differ in whiten,
+pca_dim, algorithm, init or K.  Without the key the report is what it was.
 """
 import json
 from collections import OrderedDict
@@ -87,12 +95,14 @@ def compose(cluster_stats, centers, counts, count, reinit=(.7, 5.0)):
 def format_report(report):
     head = "{:<32}{:>6}{:>10}{:>6}{:>7}{:>11}{:>14}{:>14}{:>11}{:>10}{:>10}".format(
         'view', 'epoch', 'n', 'K', 'empty', 'underused', 'inertia', 'nearest', 'displaced', 'silh', 'DB')
-    lines = [head]
+    sampled = any('silhouette_sampled' in rep for per_epoch in report['views'].values() for rep in per_epoch.values())
+    lines = [head + ("{:>13}".format('silh_sampled') if sampled else '')]  # one more column with evaluate.silhouette_sample
     for name, per_epoch in report['views'].items():
         for epoch, rep in per_epoch.items():
             lines.append("{:<32}{:>6}{:>10}{:>6}{:>7}{:>11}{:>14.6g}{:>14.6g}{:>10.2f}%{:>10.4f}{:>10.4f}".format(
                 name, epoch, rep['n'], rep['K'], rep['empty'], rep['underused'], rep['inertia'], rep['nearest_inertia'],
-                100.0 * rep['displaced_share'], rep['silhouette'], rep['davies_bouldin']))
+                100.0 * rep['displaced_share'], rep['silhouette'], rep['davies_bouldin'])
+                + ("{:>13.4f}".format(rep['silhouette_sampled']) if sampled else ''))
     return '\n'.join(lines)
 
 
@@ -143,7 +153,9 @@ def evaluate(args):
     from .. import shards as io
     from .row_groups import current_device, open_row_groups, probe_shards
     from .sgd_clustering import KMeans
+    from . import silhouette
     opts = args.get('evaluate') or {}
+    sil_m, sil_seed = silhouette.check_options(opts)  # refused before any cache or shard is read
     epochs = _epochs(args.clustering.cached_epoch)
     states = load_states(args, epochs)
     out_path, rows_path = opts.get('out_path'), opts.get('rows_path')
@@ -175,7 +187,24 @@ def evaluate(args):
     acc = OrderedDict((key, np.zeros((km.centers.shape[0], QUALITY_COLS), np.float64)) for key, km in cl.items())
     if rows_path is not None:
         Path(rows_path).mkdir(parents=True, exist_ok=True)
+    if sil_m is not None:  # the sample: one set of global row numbers for all views and epochs, gathered while the pass goes by
+        import torch
+        n_total = sum(int(sizes[p.stem]) for p in paths) if groups.streamed else len(groups.resident_table())
+        picks = silhouette.sample_indices(n_total, sil_m, sil_seed)
+        if len(picks) < 2:
+            raise ValueError("evaluate.silhouette_sample: the shards hold {} rows, a silhouette needs two".format(n_total))
+        sample, base = OrderedDict(), 0
     for _gi, table, rows in groups.iterate():
+        if sil_m is not None:
+            n_g = next(iter(rows.values())).shape[0]
+            lo, hi = (int(i) for i in np.searchsorted(picks, (base, base + n_g)))
+            for v in view_dims:
+                x = rows[v]
+                if v not in sample:
+                    sample[v] = torch.empty((len(picks), x.shape[1]), dtype=torch.float32, device=x.device)
+                if hi > lo:
+                    sample[v][lo:hi] = x[torch.from_numpy(picks[lo:hi] - base).to(x.device)]
+            base += n_g
         per_row = {}
         for (e, v), km in cl.items():  # every epoch's centres on the rows while they are on the device
             labels, _ = km.calc_best(rows[v], need_mean=False)
@@ -192,6 +221,9 @@ def evaluate(args):
                 np.savez(Path(rows_path) / (shard + '.quality.npz'), filename=np.array([table.filename[i] for i in ids]),
                          epochs=np.asarray(epochs, np.int64), **arrays)
 
+    if sil_m is not None and base != n_total:
+        raise RuntimeError("the shards delivered {} rows, their metadata states {}: fix the metadata or drop the unreadable shards "
+                           "from the list".format(base, n_total))
     report = {'feature_path': str(args.data.path), 'clusters_path': str(args.data.output.path), 'epochs': epochs,
               'views': OrderedDict()}
     for (e, v), km in cl.items():
@@ -205,6 +237,15 @@ def evaluate(args):
             tv = float(fit['total_variance'])
             rep['pca_dim'] = int(fit['components'].shape[0])
             rep['pca_explained_variance_ratio'] = float(fit['explained_variance'].sum() / tv) if tv > 0 else float('nan')
+        if sil_m is not None:  # the sample's labels in this state, then every pairwise distance of it
+            K = km.centers.shape[0]
+            labels, _ = km.calc_best(sample[v], need_mean=False)
+            A, B, s = silhouette.silhouette_samples(sample[v], labels, k=K)
+            sil = silhouette.summarise(A, B, s, labels.cpu().numpy(), K)
+            if 'silhouette_undefined' not in sil and not np.isfinite(sil['silhouette_sampled']):
+                raise ValueError("view {}, epoch {}: the sampled silhouette is {!r}: the rows of the sample are not all "
+                                 "finite".format('/'.join(v[1:]), e, sil['silhouette_sampled']))
+            rep.update(sil)
         report['views'].setdefault('/'.join(v[1:]), OrderedDict())[str(e)] = rep
     print(format_report(report))
     if out_path is not None:

@@ -300,6 +300,16 @@ class KMeans:
         _lib.check(_lib._lib.acav_kmeans_quality(h, xp, b, _lib.ptr(lab), _lib.ptr(cluster_stats), _lib.ptr(row_stats)))
         return (cluster_stats, row_stats) if rows else cluster_stats
 
+    def silhouette(self, batch, labels=None):
+        """The exact silhouette of labelled rows (clustering/silhouette.py, acav_rows_silhouette: every pairwise distance of the
+        batch in float64 -- a sample, not all rows) -> (A, B, s), float64 [b] each.  labels=None: calc_best(batch,
+        need_mean=False)'s, as for quality.  The centres enter through the labels alone."""
+        from .silhouette import silhouette_samples
+        self._require_handle()
+        if labels is None:
+            labels, _ = self.calc_best(batch, need_mean=False)
+        return silhouette_samples(batch, labels, k=self._shape[0], device="cuda:{}".format(self._device))
+
     def train_stats(self):
         """(bulk training calls that ran as one persistent launch, launches that gave up and were re-run per step)"""
         a, b = C.c_int64(0), C.c_int64(0)
