@@ -52,6 +52,7 @@ SIGNATURES = {
     "acav_rows_absmax": [i32, vp, i64, i32, C.POINTER(f32), vp],
     "acav_lloyd_accumulate": [i32, vp, i64, i32, vp, i32, i32, vp, vp, vp],
     "acav_lloyd_accumulate_plan": [vp, i32, i32, i32, C.POINTER(i64), vp, i64],
+    "acav_lloyd_centers": [i32, vp, vp, i32, i32, i32, vp, vp, C.POINTER(i64), vp],
     "acav_kmeanspp_weights": [i32, vp, i64, i32, vp, i32, i32, vp, vp],
     "acav_kmeanspp_seed": [i32, vp, i64, i32, i32, i32, vp, i32, vp, vp, vp],
     "acav_rows_silhouette": [i32, vp, i64, i32, vp, i32, vp, vp],
@@ -139,7 +140,7 @@ _lib = None
 _FIRST_DEVICE_CALLS = ("acav_device_count", "acav_device_info", "acav_kmeans_create", "acav_mi_create",
                        "acav_contrastive_create", "acav_comm_init", "acav_mt_stream_fill", "acav_colstats", "acav_rows_scale",
                        "acav_rows_scatter", "acav_rows_project", "acav_pair_scores", "acav_rank_desc", "acav_rows_absmax",
-                       "acav_lloyd_accumulate", "acav_kmeanspp_weights", "acav_kmeanspp_seed", "acav_rows_silhouette",
+                       "acav_lloyd_accumulate", "acav_lloyd_centers", "acav_kmeanspp_weights", "acav_kmeanspp_seed", "acav_rows_silhouette",
                        "acav_rows_silhouette_range")
 _device_touched = False
 

@@ -10,18 +10,22 @@ Definition of one iteration on rows x [N, d] (fp32, after the whiten / PCA front
   sums     sums[k][j] = sum over the rows labelled k of rint(double(x_ij) * 2^s) in int64, counts[k] = their number
            (acav_lloyd_accumulate), s = fixed_point_shift(absmax of all rows, N): integer sums, so the tables do not depend on the
            summation order, the device, the row groups or resident versus streamed rows
-  centres  np.float32(sums.astype(float64) * 2.0**-s / counts) on the host; then the empty clusters in ascending order
+  centres  np.float32(sums.astype(float64) * 2.0**-s / counts) -- acav_lloyd_centers on device tables, the same three rounded
+           operations, and numpy on the host when a cluster is empty or the tables are host arrays; then the empty clusters in
+           ascending order
            (split_empty, after faiss's split_clusters): the currently largest cluster j (lowest index on ties) is split, c_i = c_j
            with the even columns of c_i times 1 + 1/1024 and of c_j times 1 - 1/1024, the odd columns the other way round, and i
            takes floor(count_j / 2) of j's count.
-The assignment and the sums are GPU sweeps (there is no CPU path); tests/_lloyd_np.py restates the iteration in numpy bit for bit."""
+The assignment and the sums are GPU sweeps (there is no CPU path); tests/_lloyd_np.py restates the iteration in numpy bit for bit.
+Several GPUs with the rows partitioned (clustering.multi_gpu=rows): the tables are integers, so their all-reduced sum is the
+one-GPU run's table whoever added what -- parallel/lloyd_rows.py and run_clustering._train_clusters_lloyd."""
 import ctypes as C
 import math
 
 import numpy as np
 
 from .. import _lib
-from .options import needs_every_row
+from .options import multi_gpu_mode, needs_every_row
 from .sgd_clustering import KMeans, _as_f32_2d, _device_index
 
 ALGORITHMS = ('sgd', 'lloyd')
@@ -29,14 +33,24 @@ CALL_ROWS = 1 << 30        # rows of one acav_lloyd_accumulate call (its positio
 SPLIT_EPS = np.float32(1.0 / 1024)
 
 
-def check_algorithm(args, world_size=1):
-    """clustering.algorithm is 'sgd' or 'lloyd'; lloyd over several GPUs needs clustering.multi_gpu=views.  Pure: no device, no
-    file.  -> the algorithm"""
+def check_algorithm(args, world_size=1, merges=()):
+    """clustering.algorithm is 'sgd' or 'lloyd'.  lloyd over several GPUs needs every row of a view on every rank
+    (clustering.multi_gpu=views) unless the caller merges the cluster sums across the ranks: merges names the partitioned modes in
+    which it does.  The clustering stage does in 'rows' (run_clustering.check_options passes merges=('rows',): the int64 tables are
+    all-reduced); 'striped' and 'reference' name batch streams of the SGD chain and are merged by nobody.  A caller that states no
+    merge is refused every partitioned mode, as before.  Pure: no device, no file.  -> the algorithm"""
     algo = 'sgd' if args.clustering.algorithm is None else args.clustering.algorithm  # (a hand-built args tree without the key)
     if not isinstance(algo, str) or algo not in ALGORITHMS:
         raise ValueError("clustering.algorithm must be 'sgd' or 'lloyd', not {!r}".format(algo))
     if algo == 'lloyd':
-        needs_every_row(args, world_size, "clustering.algorithm=lloyd", "cluster sums")
+        mode = multi_gpu_mode(args)
+        if int(world_size) > 1 and mode in ('striped', 'reference'):
+            raise ValueError("clustering.algorithm=lloyd with clustering.multi_gpu={} on {} GPUs: the rows are partitioned over the "
+                             "ranks and the cluster sums are not merged across them in a mode that names a batch stream of the SGD "
+                             "chain (lloyd partitions its rows with clustering.multi_gpu=rows); use clustering.multi_gpu=views or one "
+                             "GPU".format(mode, world_size))
+        if mode not in merges:
+            needs_every_row(args, world_size, "clustering.algorithm=lloyd", "cluster sums")
         if isinstance(args.clustering.epochs, bool) or int(args.clustering.epochs) < 1:
             raise ValueError("clustering.epochs={!r}: lloyd needs at least one iteration".format(args.clustering.epochs))
     return algo
@@ -150,6 +164,26 @@ def centers_from_sums(sums, counts, s):
     return centers, counts, splits
 
 
+def centers_on_device(sums, counts, s):
+    """(sums int64 [K, d], counts int64 [K]: contiguous tensors on one GPU, s) -> (centers fp32 [K, d], sizes fp32 [K], both
+    tensors on that GPU, number of empty clusters): acav_lloyd_centers -- centers_from_sums before the empty-cluster rule, an
+    empty cluster a row of zeros"""
+    import torch
+    if not (hasattr(sums, "is_cuda") and sums.is_cuda and counts.is_cuda and sums.dtype == torch.int64 and counts.dtype == torch.int64
+            and sums.is_contiguous() and counts.is_contiguous() and sums.dim() == 2 and sums.device == counts.device):
+        raise ValueError("sums and counts must be contiguous int64 tensors on one GPU")
+    k, d = int(sums.shape[0]), int(sums.shape[1])
+    if tuple(counts.shape) != (k,):
+        raise ValueError("counts has shape {}, sums {}".format(tuple(counts.shape), tuple(sums.shape)))
+    centers = torch.empty((k, d), dtype=torch.float32, device=sums.device)
+    sizes = torch.empty(k, dtype=torch.float32, device=sums.device)
+    torch.cuda.current_stream(sums.device).synchronize()  # the library runs on its own stream
+    empty = C.c_int64(0)
+    _lib.check(_lib.load_library().acav_lloyd_centers(sums.device.index, _lib.ptr(sums), _lib.ptr(counts), k, d, int(s), _lib.ptr(centers),
+                                                      _lib.ptr(sizes), C.byref(empty), None))
+    return centers, sizes, int(empty.value)
+
+
 def lloyd_update(km, x, s, sums=None, counts=None):
     """The two sweeps of one iteration over the rows x [n, d] (on the GPU) of one row group: labels of km's current centres
     (calc_best, need_mean=False), their fixed-point sums and counts added into sums / counts (int64 tensors on x's device,
@@ -168,7 +202,15 @@ def lloyd_update(km, x, s, sums=None, counts=None):
 
 def finish_iteration(km, sums, counts, s):
     """centres <- mean of their rows (+ the empty-cluster rule), counts <- the cluster sizes, count += the rows of the
-    iteration -> number of splits"""
+    iteration -> number of splits.  Tables on the device (torch tensors) take acav_lloyd_centers: the centres go from device
+    to device into km's handle and no table crosses the bus; when it reports an empty cluster, the iteration takes the host path
+    below (split_empty is sequential and rare).  Host tables (numpy) take the host path."""
+    if hasattr(sums, "data_ptr") and sums.is_cuda and km._h is not None:
+        centers, sizes, empty = centers_on_device(sums, counts, s)
+        if empty == 0:
+            n = int(counts.sum())
+            _lib.check(_lib._lib.acav_kmeans_set_state(km._h, _lib.ptr(centers), _lib.ptr(sizes), km.count + n, km.fallback))
+            return 0
     sums_h = sums.cpu().numpy() if hasattr(sums, "cpu") else sums
     counts_h = counts.cpu().numpy() if hasattr(counts, "cpu") else counts
     n = int(counts_h.sum())

@@ -18,9 +18,16 @@ def needs_every_row(args, world_size, option, unmerged):
                          "merged across them; use clustering.multi_gpu=views or one GPU".format(option, mode, world_size, unmerged))
 
 
+def lloyd_rows(args, world_size):
+    """True for the one combination that partitions the rows AND merges across the ranks: clustering.algorithm=lloyd with
+    clustering.multi_gpu=rows on several GPUs (integer cluster sums, all-reduced; run_clustering._train_clusters_lloyd)"""
+    return int(world_size) > 1 and args.clustering.algorithm == 'lloyd' and multi_gpu_mode(args) == 'rows'
+
+
 def check_whiten(args, world_size):
-    """clustering.whiten needs every row of a view on the rank that takes its moments"""
-    if args.clustering.whiten:
+    """clustering.whiten needs every row of a view on the rank that takes its moments -- or lloyd + rows, whose ranks exchange
+    the per-shard moments and merge them in the one-GPU order"""
+    if args.clustering.whiten and not lloyd_rows(args, world_size):
         needs_every_row(args, world_size, "clustering.whiten", "column moments")
 
 

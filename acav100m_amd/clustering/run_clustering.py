@@ -47,7 +47,7 @@ def check_options(args, world_size):
     """the refusals that need no device and no file, before anything is created or read"""
     check_whiten(args, world_size)
     check_pca(args, world_size)
-    check_algorithm(args, world_size)
+    check_algorithm(args, world_size, merges=('rows',))  # (_train_clusters_lloyd all-reduces the tables in that mode)
     check_init(args)
 
 
@@ -202,22 +202,42 @@ def compute_pca(groups, dim):
     return fits
 
 
-def compute_whitening(groups):
+def compute_whitening(groups, shard_stems=None, view_dims=None):
     """The stats pre-pass of clustering.whiten: one pass over the row groups, per view one acav_colstats call per group with
     the group's shards as segments, merged in shard order (whiten.ColumnMoments) -> {view: std fp32 [d]}.  Resident data: the
-    pass uploads the rows training keeps using.  Streamed data: one extra read of every shard."""
+    pass uploads the rows training keeps using.  Streamed data: one extra read of every shard.
+    shard_stems (lloyd + clustering.multi_gpu=rows): the stems of ALL shards in list order, `groups` holding this rank's.  Every
+    rank keeps the (n, mean, M2) of its shards per shard; the ranks exchange them bit for bit (parallel/lloyd_rows.py: one
+    collective for the counts, one per view of view_dims, whatever a rank's rows look like) and replay add_segment in global
+    shard order: the one-GPU run's sequence of Chan merges, hence its std bytes."""
     from .whiten import ColumnMoments
     if groups.streamed:
         print("whitening: the column moments take one extra read of every shard ({} groups stream)".format(len(groups.groups)))
     moments = OrderedDict()
+    index = None if shard_stems is None else {stem: i for i, stem in enumerate(shard_stems)}
+    per_shard, shard_n = OrderedDict(), {}  # partitioned: {view: float64 [S, 2, d]} and {global shard: rows}, this rank's part
+    if index is not None:
+        for v, d in view_dims.items():
+            per_shard[v] = np.zeros((len(index), 2, d), np.float64)
     for _gi, table, rows in groups.iterate():
         prefix = _shard_prefix(table)
+        stems = [stem for stem, ids in table.shard_rows.items() if ids]  # the segments: the non-empty shards, in order
         for v, x in rows.items():
             if v not in moments:
                 moments[v] = ColumnMoments(x.shape[1], x.device)
             if len(prefix) > 1 and x.shape[1] > 0:
-                moments[v].update(x[:prefix[-1]], prefix)
+                seg = moments[v].update(x[:prefix[-1]], prefix)
+                if index is not None:
+                    per_shard[v][[index[stem] for stem in stems]] = seg
+        if index is not None:
+            for si, stem in enumerate(stems):
+                shard_n[index[stem]] = prefix[si + 1] - prefix[si]
         del rows
+    if index is not None:
+        from ..parallel import lloyd_rows
+        counts = lloyd_rows.exchange_counts(shard_n, len(index))
+        for v, d in view_dims.items():
+            moments[v] = lloyd_rows.replay_moments(d, counts, lloyd_rows.exchange_bits(per_shard[v]))
     stds = OrderedDict()
     for v, cm in moments.items():
         stds[v] = cm.std()
@@ -263,7 +283,7 @@ def train_clusters(args, probe, groups, shard_stems=(), cached=None):
     epochs = int(args.clustering.epochs)
     b = int(args.data.batch_size)
     if args.clustering.algorithm == 'lloyd':
-        return _train_clusters_lloyd(args, cl, groups, pre, epochs, loaded)
+        return _train_clusters_lloyd(args, cl, groups, pre, epochs, loaded, shard_stems)
     print("training sgd kmeans for views: {}".format([v[1:] for v in cl]))
     if w > 1 and multi_gpu_mode(args) != 'views':
         return _train_clusters_planned(args, cl, groups, pre, epochs, b, multi_gpu_mode(args), shard_stems)
@@ -330,26 +350,51 @@ def train_clusters(args, probe, groups, shard_stems=(), cached=None):
     return cl
 
 
-def _train_clusters_lloyd(args, cl, groups, pre, iters, resumed):
+def _local_shard_counts(groups):
+    """{stem: rows} of the shards `groups` holds, as the run numbers them: the rows that loaded (resident) or that the metadata
+    states (streamed)"""
+    if groups.streamed:
+        return {p.stem: int(groups.sizes[p.stem]) for p in groups.paths}
+    table = groups.resident_table()
+    return {p.stem: len(table.shard_rows.get(p.stem) or ()) for p in groups.paths}
+
+
+def _train_clusters_lloyd(args, cl, groups, pre, iters, resumed, shard_stems=(), force_partitioned=False):
     """clustering.algorithm=lloyd: `iters` iterations of batch k-means per view (clustering/lloyd.py), each one pass over the row
     groups with two sweeps per view -- the assign sweep and acav_lloyd_accumulate into int64 tables on the device -- and the centre
-    update on the host.  Before the first one, one read-once pass takes every view's largest magnitude (the scale of the fixed
+    update on the device too (acav_lloyd_centers; on the host in an iteration that has an empty cluster to split).  Before the first one, one read-once pass takes every view's largest magnitude (the scale of the fixed
     point) and, for a fresh run, the initial centres: the rows generator.randperm(N)[:K], drawn view by view, read as the
     front-ends deliver them -- or, with clustering.init=kmeans++, k-means++ seeds drawn from a sample of the rows that the same
     pass gathers (clustering/kmeanspp.py).  The tables are integer sums, so resident and streamed rows give the same bytes.
     N comes from the metadata when the rows stream (like the batch plan of the SGD loop) and is checked against what the shards
     deliver.
-    Several GPUs (clustering.multi_gpu=views): every rank runs every view -- the result is a pure function of the rows, the ranks
-    end in the same state without an exchange -- and rank 0 writes the caches."""
+    Several GPUs, clustering.multi_gpu=views: every rank runs every view -- the result is a pure function of the rows, the ranks
+    end in the same state without an exchange -- and rank 0 writes the caches.
+    Several GPUs, clustering.multi_gpu=rows (parallel/lloyd_rows.py): `groups` holds THIS rank's shards (rank::world).  The ranks
+    exchange their per-shard row counts once, so that every rank numbers the rows as the one-GPU run does; every rank draws every
+    permutation, fills the picked rows it owns, and the picks are exchanged bit for bit; the magnitudes are all-reduced with MAX;
+    per iteration and live view the int64 tables are all-reduced with SUM, and the changed-label counts once for all views.  Every
+    rank then moves its own copy of the centres from the same tables: equal states without a broadcast, the files of the one-GPU
+    run.  The sequence of collectives is the same on every rank whatever its rows look like; a rank-local failure of the pre-pass
+    travels as a non-finite magnitude and rises on every rank.  force_partitioned: that path with one rank (the test of the
+    collectives on the device)."""
     import torch
     from . import kmeanspp, lloyd
-    rank, _w = world()
+    from ..parallel import lloyd_rows
+    rank, w = world()
+    part = force_partitioned or (w > 1 and multi_gpu_mode(args) != 'views')
     K = int(args.clustering.ncentroids)
     print("training lloyd kmeans for views: {}".format([v[1:] for v in cl]))
-    if groups.streamed:
-        n_total = sum(int(groups.sizes[p.stem]) for p in groups.paths)
+    local = _local_shard_counts(groups)
+    n_local = sum(local.values())
+    if part:
+        index = {stem: i for i, stem in enumerate(shard_stems)}
+        shard_counts = lloyd_rows.exchange_counts({index[stem]: n for stem, n in local.items()}, len(shard_stems))
+        n_total = int(shard_counts.sum())
+        print("lloyd: clustering.multi_gpu=rows: the rows are partitioned over {} ranks, rank {} holds {} of {} rows in {} of {} "
+              "shards".format(w, rank, n_local, n_total, len(local), len(shard_stems)))
     else:
-        n_total = len(groups.resident_table())
+        n_total = n_local if groups.streamed else len(groups.resident_table())
     if K > n_total:
         raise ValueError("clustering.algorithm=lloyd: clustering.ncentroids={} initial centres cannot be {} distinct rows".format(K, n_total))
     # clustering.init=kmeans++ (a fresh run only; a resumed one ignores the keys as it ignores the picks): the same pass gathers,
@@ -367,11 +412,30 @@ def _train_clusters_lloyd(args, cl, groups, pre, iters, resumed):
             picks[v] = np.sort(perm[:M]) if plus else perm[:K]
     absmax = OrderedDict((v, 0.0) for v in cl)
     init = OrderedDict((v, np.zeros(km._shape, np.float32)) for v, km in cl.items())
-    base = 0
+    if part and not resumed:  # the picks this rank owns: (position among the picks, local row), by ascending local row
+        owned = OrderedDict()
+        for v in cl:
+            pos, owner, loc = lloyd_rows.locate_rows(picks[v], shard_counts, w)
+            mine = np.flatnonzero(owner == rank)
+            mine = mine[np.argsort(loc[mine], kind='stable')]
+            owned[v] = (pos[mine], loc[mine])
+        got = OrderedDict((v, np.zeros((len(picks[v]), km._shape[1]), np.float32)) for v, km in cl.items())
+    base, failure = 0, None
     for _gi, _table, rows in groups.iterate():
         n_g = next(iter(rows.values())).shape[0] if rows else 0
         for v in cl:
             x = rows[v]
+            if part:
+                try:
+                    absmax[v] = max(absmax[v], lloyd.rows_absmax(x))
+                except ValueError as exc:  # (a value that is not finite: every rank has to learn of it)
+                    absmax[v], failure = float('inf'), failure or "view {}: {}".format('/'.join(v[1:]), exc)
+                if not resumed:
+                    pos, loc = owned[v]
+                    lo, hi = (int(i) for i in np.searchsorted(loc, (base, base + n_g)))
+                    if hi > lo:
+                        got[v][pos[lo:hi]] = x[torch.from_numpy(loc[lo:hi] - base).to(x.device)].cpu().numpy()
+                continue
             absmax[v] = max(absmax[v], lloyd.rows_absmax(x))
             if plus:
                 lo, hi = (int(i) for i in np.searchsorted(picks[v], (base, base + n_g)))
@@ -385,7 +449,29 @@ def _train_clusters_lloyd(args, cl, groups, pre, iters, resumed):
                     init[v][sel] = x[torch.from_numpy(picks[v][sel] - base).to(x.device)].cpu().numpy()
         base += n_g
         del rows
-    if base != n_total:
+    if part:
+        # one MAX over the views' magnitudes and this rank's verdict on its own rows, then the picks view by view: the same
+        # collectives on every rank, and a failure anywhere rises everywhere
+        if base != n_local:
+            failure = failure or "the shards of rank {} delivered {} rows, their metadata states {}".format(rank, base, n_local)
+        if failure:
+            print("lloyd: rank {}: {}".format(rank, failure))
+        merged = lloyd_rows.allreduce_max([absmax[v] for v in cl] + [1.0 if failure else 0.0])
+        for v, a in zip(cl, merged):
+            absmax[v] = a
+        if not resumed:
+            dev = _device(args)
+            for v in cl:
+                rows_v = lloyd_rows.exchange_bits(got[v])
+                if plus:
+                    sample[v] = torch.from_numpy(rows_v).to(dev)
+                else:
+                    init[v] = rows_v
+            del got
+        if merged[-1] != 0:
+            raise RuntimeError("clustering.multi_gpu=rows: the pre-pass failed on a rank ({}): fix the metadata or drop the unreadable "
+                               "shards from the list".format(failure or "see that rank's log"))
+    elif base != n_total:
         raise RuntimeError("the shards delivered {} rows, their metadata states {}: fix the metadata or drop the unreadable shards "
                            "from the list".format(base, n_total))
     if plus:
@@ -426,6 +512,14 @@ def _train_clusters_lloyd(args, cl, groups, pre, iters, resumed):
                 changed[v] += int(labels.numel()) if old is None else int((labels != old).sum())
                 prev[v][gi] = labels
             del rows
+        if part:
+            dev = _device(args)
+            for v in live:
+                if tables[v][0] is None:  # a rank whose shards hold no row still takes part in every collective
+                    tables[v] = (torch.zeros(cl[v]._shape, dtype=torch.int64, device=dev), torch.zeros(K, dtype=torch.int64, device=dev))
+                lloyd_rows.allreduce_tables(*tables[v])
+            for v, c in zip(live, lloyd_rows.allreduce_sum([changed[v] for v in live])):
+                changed[v] = c
         for v in live:
             splits = lloyd.finish_iteration(cl[v], tables[v][0], tables[v][1], shift[v])
             print("lloyd {}: iteration {}: {} labels changed, {} empty clusters split".format('/'.join(v[1:]), epoch, changed[v], splits))
@@ -587,8 +681,10 @@ def run_clustering(args):
     groups = open_row_groups(args, paths[rank::w] if partitioned else paths, sizes, view_dims)
     groups.all_sizes = sizes  # metadata sizes of ALL shards (the loader length of a partitioned run is computed over all of them)
     if cache_file is not None:  # the space the cached centres were trained in; nothing is recomputed
+        # (a whitened Lloyd cache with rows: applying a cached std is a per-row function, and the run merges across the ranks)
+        lloyd_cache = multi_gpu_mode(args) == 'rows' and all((dt.get('algorithm') or 'sgd') == 'lloyd' for dt in cached[1].values())
         for what, found in (('whitened', cached_std), ('projected', cached_pca)):
-            if found and partitioned:
+            if found and partitioned and not (what == 'whitened' and lloyd_cache):
                 raise ValueError("the clustering cache {} is {}: clustering.multi_gpu={} partitions the rows, use views".format(
                     cache_file, what, multi_gpu_mode(args)))
         fronts = OrderedDict((v, FrontEnd.from_attrs(cache.find(cached[1], v))) for v in view_dims)
@@ -601,7 +697,8 @@ def run_clustering(args):
         groups.add_front_ends(fronts)
     else:  # a fresh run: the std, then the scatter matrices of the whitened rows, then the projection
         if args.clustering.whiten:
-            groups.add_front_ends({v: FrontEnd(std=s) for v, s in compute_whitening(groups).items()})
+            stds = compute_whitening(groups, [p.stem for p in paths], view_dims) if partitioned else compute_whitening(groups)
+            groups.add_front_ends({v: FrontEnd(std=s) for v, s in stds.items()})
         if args.clustering.pca_dim is not None:
             groups.add_front_ends({v: FrontEnd(pca=f) for v, f in compute_pca(groups, int(args.clustering.pca_dim)).items()})
     cl = train_clusters(args, probe, groups, [p.stem for p in paths], cached)

@@ -124,12 +124,18 @@ CLUSTERING_DEFAULTS = {
         #   batch_size, N * rows / batch_size steps per epoch.
         # 'rows': a LARGE-BATCH operating point, not the reference's run: batch_size rows of every GPU's own shards per step
         #   (global batch N x batch_size), ceil(epochs / N) epochs -- N x N fewer SGD steps than 'reference' (64 x at N = 8).
+        # With clustering.algorithm=lloyd, 'rows' means something else and 'striped' / 'reference' are refused (they name SGD batch
+        #   streams): the ROWS are partitioned (rank r reads, holds and labels the shards r::N), the int64 cluster sums are
+        #   all-reduced once per view and iteration, clustering.epochs stays the number of iterations, and the N-GPU run writes
+        #   the one-GPU run's files bit for bit (parallel/lloyd_rows.py).  clustering.whiten and clustering.init=kmeans++ go with
+        #   it; clustering.pca_dim does not.
         'multi_gpu': 'views',
         # ours: divide every feature column by its standard deviation over all rows before clustering (scipy.cluster.vq.whiten,
         # which every clusterer of the reference's correspondence_retrieval/code/clustering.py:54-63 runs first; no centring).
         # One stats pass over the rows before the first epoch (streamed data: one extra read of every shard); the cache file keeps
         # the divisors as 'whiten_std', and a cached run (clustering.cached_epoch) uses the cache's, whatever this switch says.
-        # Several GPUs: clustering.multi_gpu=views only.  False (default): every file stays what it is without the switch.
+        # Several GPUs: clustering.multi_gpu=views, or rows with algorithm=lloyd.  False (default): every file stays what it is
+        # without the switch.
         'whiten': False,
         # ours: project every view onto its pca_dim leading principal components before clustering (after the whitening, if on):
         # sklearn.decomposition.PCA(n_components=pca_dim).fit_transform, the second half of the front-end of the reference's
@@ -147,7 +153,7 @@ CLUSTERING_DEFAULTS = {
         # written after every iteration, and the loop stops early when an iteration changes no label.  The cached state carries
         # 'algorithm': 'lloyd' with initial_rounds = 0 and reinit = (.7, 1.0): a cached run, the assign stage and `evaluate` then
         # label every row with its plainly nearest centre.  resume_training from a cache of the other algorithm is refused.
-        # Several GPUs: clustering.multi_gpu=views only.
+        # Several GPUs: clustering.multi_gpu=views (every rank runs every row) or rows (the rows partitioned, see multi_gpu above).
         'algorithm': 'sgd',
         # ours (algorithm=lloyd only): how the initial centres are chosen.  'random' (default: the rows randperm(N)[:ncentroids],
         # every file and every generator draw stays what it is without the key) or 'kmeans++': D^2 sampling (scipy's
@@ -155,7 +161,7 @@ CLUSTERING_DEFAULTS = {
         # gathered on the device during the pass that reads the initial rows today; every pick is one read-once sweep over the
         # sample (clustering/kmeanspp.py, acav_kmeanspp_seed), the result a pure function of the rows and the seed.  What to turn
         # when `evaluate` reports empty or under-used clusters, or `cluster` reports splits.  A resumed run ignores the three
-        # keys.  Several GPUs: clustering.multi_gpu=views only (every rank computes the same seeds).
+        # keys.  Several GPUs: clustering.multi_gpu=views or rows (every rank computes the same seeds from the same sample).
         'init': 'random',
         # local trials per k-means++ pick: 1 (default, the classical algorithm), 'auto' = min(16, 2 + floor(ln ncentroids))
         # (sklearn's greedy variant: of the trials' rows the one that lowers the potential most is kept) or an integer in [1, 16]

@@ -20,6 +20,12 @@
 //                           read per row, summed in registers; the partial goes into sums with one 64-bit integer add per column.
 //                           A cluster is never one wave's job: a cluster holding half the rows is n / 1024 chunks like any other.
 // Every feature byte is read once.
+//
+// acav_lloyd_centers: the centre update that follows, on the device.  centers[c][j] = (float)(((double)sums[c][j] * 2^-s) /
+// (double)counts[c]) -- an int64 -> double conversion (round to nearest even), an exact scaling by a power of two, one IEEE double
+// division and one rounding to fp32, each its own operation (the build has -ffp-contract=off and no fast-math): what
+// clustering/lloyd.py:centers_from_sums computes in numpy, bit for bit.  One streaming kernel (k_lloyd_centers) over the
+// [k][d] table as one flat array: 8 bytes read and 4 written per element, no LDS, one integer atomic per empty cluster.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -220,6 +226,56 @@ __global__ __launch_bounds__(256) void k_lloyd_sum(const float *__restrict__ x, 
     }
 }
 
+// The flat table of k * d elements in quads: a thread loads two 16-byte pairs of sums and stores one 16-byte quad of centres
+// (vec: both tables start on a 16-byte boundary; a quad's place in the flat array is then aligned whatever the row pitch d).
+// A quad may cross rows: the row c and column r of its first element come from one division, the others by stepping.  The last
+// total % 4 elements, and every element when !vec, go one by one through the same arithmetic (ll_center).  The thread that
+// holds column 0 of row c writes sizes[c] and counts the row when it is empty.
+__device__ __forceinline__ float ll_center(long long sum, long long count, double inv_scale)
+{
+    if (count == 0) return 0.f;
+    const double scaled = (double)sum * inv_scale;  // exact: a power of two
+    return (float)(scaled / (double)count);
+}
+
+__global__ __launch_bounds__(256) void k_lloyd_centers(const long long *__restrict__ sums, const long long *__restrict__ counts,
+                                                       unsigned total, unsigned d, double inv_scale, int vec,
+                                                       float *__restrict__ centers, float *__restrict__ sizes, unsigned *__restrict__ empty)
+{
+    const unsigned quads = vec ? total / 4 : 0;
+    const unsigned stride = gridDim.x * 256;
+    for (unsigned q = blockIdx.x * 256 + threadIdx.x; q < quads; q += stride) {
+        const unsigned e = 4 * q;
+        const longlong2 a = reinterpret_cast<const longlong2 *>(sums)[2 * q], b = reinterpret_cast<const longlong2 *>(sums)[2 * q + 1];
+        const long long v[4] = {a.x, a.y, b.x, b.y};
+        unsigned c = e / d, r = e - c * d;
+        long long n = counts[c];
+        float out[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (r == 0) {
+                sizes[c] = (float)n;
+                if (n == 0) atomicAdd(empty, 1u);
+            }
+            out[u] = ll_center(v[u], n, inv_scale);
+            if (++r == d && u < 3 && e + u + 1 < total) {
+                r = 0;
+                n = counts[++c];
+            }
+        }
+        reinterpret_cast<float4 *>(centers)[q] = make_float4(out[0], out[1], out[2], out[3]);
+    }
+    for (unsigned e = 4 * quads + blockIdx.x * 256 + threadIdx.x; e < total; e += stride) {
+        const unsigned c = e / d, r = e - c * d;
+        const long long n = counts[c];
+        if (r == 0) {
+            sizes[c] = (float)n;
+            if (n == 0) atomicAdd(empty, 1u);
+        }
+        centers[e] = ll_center(sums[e], n, inv_scale);
+    }
+}
+
 int use_device(int device, int *cus)
 {
     int n = 0;
@@ -372,5 +428,35 @@ ACAV_EXPORT int acav_lloyd_accumulate(int device, const float *x, int64_t n, int
         ACAV_HIP_TRY(hipMemcpyAsync(counts, dcounts, sizeof(int64_t) * (size_t)k, hipMemcpyDeviceToHost, st));
     }
     ACAV_HIP_TRY(hipStreamSynchronize(st));
+    return ACAV_OK;
+}
+
+ACAV_EXPORT int acav_lloyd_centers(int device, const int64_t *sums_dev, const int64_t *counts_dev, int k, int d, int s,
+                                   float *centers_dev, float *sizes_dev, int64_t *empty_host, void *stream)
+{
+    ACAV_REQUIRE(sums_dev && counts_dev && centers_dev && sizes_dev && empty_host, ACAV_EINVAL, "NULL argument");
+    ACAV_REQUIRE(d >= 1 && d <= LL_MAX_D, ACAV_EINVAL, "d=%d must be in [1, %d]", d, LL_MAX_D);
+    ACAV_REQUIRE(k >= 1 && (int64_t)k * d <= ((int64_t)1 << 30), ACAV_EINVAL, "k=%d: k * d must be in [1, 2^30]", k);
+    ACAV_REQUIRE(s >= -LL_MAX_SHIFT && s <= LL_MAX_SHIFT, ACAV_EINVAL, "s=%d must be in [-%d, %d]", s, LL_MAX_SHIFT, LL_MAX_SHIFT);
+    int cus = 0;
+    ACAV_TRY(use_device(device, &cus));
+    ACAV_REQUIRE(is_device_ptr(sums_dev) && is_device_ptr(counts_dev) && is_device_ptr(centers_dev) && is_device_ptr(sizes_dev),
+                 ACAV_EINVAL, "sums, counts, centers and sizes are device tables: a host table takes the host path of the caller");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    DevBuf flag;
+    StreamDrain drain = {st};
+    ACAV_TRY(flag.ensure(sizeof(unsigned)));
+    ACAV_HIP_TRY(hipMemsetAsync(flag.p, 0, sizeof(unsigned), st));
+    const unsigned total = (unsigned)((int64_t)k * d);
+    const int vec = ((reinterpret_cast<uintptr_t>(sums_dev) | reinterpret_cast<uintptr_t>(centers_dev)) & 15) == 0;
+    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(((int64_t)total / (vec ? 4 : 1) + 255) / 256, (int64_t)cus * LL_PER_CU));
+    hipLaunchKernelGGL(k_lloyd_centers, dim3(grid), dim3(256), 0, st, reinterpret_cast<const long long *>(sums_dev),
+                       reinterpret_cast<const long long *>(counts_dev), total, (unsigned)d, ldexp(1.0, -s), vec, centers_dev, sizes_dev,
+                       flag.as<unsigned>());
+    ACAV_HIP_TRY(hipGetLastError());
+    unsigned h = 0;
+    ACAV_HIP_TRY(hipMemcpyAsync(&h, flag.p, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    ACAV_HIP_TRY(hipStreamSynchronize(st));
+    *empty_host = (int64_t)h;
     return ACAV_OK;
 }

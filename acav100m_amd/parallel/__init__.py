@@ -16,6 +16,9 @@
                          ceil(epochs / N) epochs): N x N fewer SGD steps than `reference`; NOT the reference's run.
                      distributed_add(): one add() step with an all-gather of the local rows and labels (the per-step form,
                      kept for KMeans.add() under is_distributed)
+  Lloyd k-means      `clustering.algorithm=lloyd` with `clustering.multi_gpu=rows` (lloyd_rows.py): the rows stay on the rank
+                     that owns their shards; per view and iteration one all-reduce (SUM, int64) of the cluster sums and counts --
+                     integer sums, so the N-GPU run writes the one-GPU run's files bit for bit
   k-means assign     none: shards are strided rank::world (mps/distributed.py:439)
   MI selection       none: chunks are independent (chunk.py:21-53)
 """

@@ -9,7 +9,9 @@ Prints one JSON line.  Per K and label shape ("even": the labels a Gaussian mixt
   assign_ms       acav_kmeans_assign with mean_dist == NULL between acav_kmeans_timer_begin / _end (lloyd hyper-parameters)
   accumulate_ms   acav_lloyd_accumulate into int64 tables on the device: wall time of a call, which returns when the tables are
                   up to date (histogram, host scan, index, chunked sums)
-  host_ms         the tables to the host, centres in float64, empty-cluster rule, upload (lloyd.finish_iteration)
+  host_ms         the centre step, wall time of lloyd.finish_iteration: acav_lloyd_centers on the device tables and a device-to-
+                  device copy into the handle (with an empty cluster: the tables to the host, centres in float64, the
+                  empty-cluster rule, upload);  host_ms_min / host_ms_max: the extremes of the same --repeat calls
   iteration_ms    their sum;  accumulate_of_colstats: the ratio the accumulate sweep is judged by;  *_GBps: n d 4 bytes over the time
   absmax_ms       the read-once sweep before the first iteration (acav_rows_absmax), once per run
 Every shape is warmed up with three calls first; medians of --repeat calls."""
@@ -53,6 +55,7 @@ def main():
             t0 = time.perf_counter()
             fn()
             times.append((time.perf_counter() - t0) * 1e3)
+        median_ms.last = times
         return statistics.median(times)
 
     gen = torch.Generator(device="cuda").manual_seed(7)
@@ -99,10 +102,11 @@ def main():
             acc()
             state = km.state_arrays()
             host_ms = median_ms(lambda: finish_iteration(km, sums, counts, shift))
+            host_min, host_max = min(median_ms.last), max(median_ms.last)
             km.load_state_arrays(*state)
             sizes = counts.cpu().numpy()
             row["runs"]["K%d_%s" % (K, name)] = {
-                "assign_ms": assign_ms, "accumulate_ms": acc_ms, "host_ms": host_ms, "iteration_ms": assign_ms + acc_ms + host_ms,
+                "assign_ms": assign_ms, "accumulate_ms": acc_ms, "host_ms": host_ms, "host_ms_min": host_min, "host_ms_max": host_max, "iteration_ms": assign_ms + acc_ms + host_ms,
                 "accumulate_of_colstats": acc_ms / row["colstats_ms"], "accumulate_GBps": nbytes / acc_ms / 1e6,
                 "assign_GBps": nbytes / assign_ms / 1e6, "largest_cluster": int(sizes.max()), "median_cluster": float(np.median(sizes))}
         del km
