@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "acav_common.h"
+#include "acav_mi_form.h"  // the greedy loop's constants (SEL_*, FY_*, GS_*), pure helpers and launch plan
 #include "acav_score.h"
 #include <rocprim/rocprim.hpp>
 #include <vector>
@@ -289,11 +290,7 @@ __device__ __forceinline__ double pair_count_score(const int *__restrict__ asg, 
     return pair_value(tpI + tnI, tpR);
 }
 
-
-constexpr int SEL_MAXB = 64;      // batch sizes up to here: the NARROW selection (one wave ranks the batch, lane = batch position)
-constexpr int SEL_WIDEB = 1024;   // batch sizes up to here: the WIDE selection (the workgroup ranks the batch out of LDS)
-constexpr int SEL_MAXBP = 8192;
-
+// (SEL_* limits, SelShared / SelSharedW, SelLayout, sel_mode, sel_layout, sel_smem_bytes: acav_mi_form.h)
 // One workgroup per greedy iteration: score the B candidates (mean over P pairs), pick the top k
 // (descending, ties -> lower batch position), commit them, emit S/GAIN, and append the
 // unselected ids in ascending order to the new candidate array (batch.py:132-171).
@@ -310,51 +307,8 @@ constexpr int SEL_MAXBP = 8192;
 //     of the same iteration touched pays a level for the phi of its adjusted counts.  Beyond the staged sizes (SEL_FAST*)
 //     it re-reads (3 levels per pick)
 //   * few registers: the gather workgroups of the same launch inherit the kernel's allocation
-constexpr int SEL_LDSP = 256;     // pairs (and their running sums) staged in LDS
-constexpr int SEL_FASTBP = 2048;  // B * P up to which the scoring's labels / counts are kept for the commit ...
-constexpr int SEL_FASTKP = 512;   // ... and k * P up to which the commit's phi values are staged (both: SEL_FAST)
-constexpr int SEL_PHIBP = 256;    // B * P up to which the scoring's phi values are kept too (SEL_KEEPPHI)
-constexpr int SEL_FAST = 1, SEL_KEEPPHI = 2;
-
-struct SelShared {
-    double score[SEL_MAXB];
-    double SN[SEL_LDSP], Sa[SEL_LDSP], Sb[SEL_LDSP];
-    long long nc;
-    unsigned long long used;
-    int id[SEL_MAXB], pos[SEL_MAXB], pick[SEL_MAXB];
-    int pairs[2 * SEL_LDSP];
-};
-// the weighted selection (W: acav_mi_set_pair_weights) stages the fp32 pair weights beside the pairs; the unweighted kernels
-// keep the LDS footprint of SelShared
-struct SelSharedW : SelShared {
-    float w[SEL_LDSP];
-};
 template <bool W>
 using SelSharedOf = std::conditional_t<W, SelSharedW, SelShared>;
-
-// Dynamic LDS of a selection launch:  scores [B P] f64 | labels + counts 5 x [B P] i32 (SEL_FAST) | scoring's phi [B P][6] f64
-// (SEL_KEEPPHI) | commit's phi [k P][6] f64 (SEL_FAST) | label rows [B D] i32.  The mode is decided on the host for the
-// largest P and D of the launch; every chunk lays its own sizes out in the same order.
-struct SelLayout {
-    unsigned off_c, off_phi, off_phik, off_lab, total;
-};
-__host__ __device__ inline int sel_mode(int B, int P, int k)
-{
-    const long long bp = (long long)B * P, kp = (long long)k * P;
-    const int fast = bp <= SEL_FASTBP && kp <= SEL_FASTKP ? SEL_FAST : 0;
-    return fast | (fast && bp <= SEL_PHIBP ? SEL_KEEPPHI : 0);
-}
-__host__ __device__ inline SelLayout sel_layout(int B, int P, int D, int k, int mode)
-{
-    const unsigned bp = (unsigned)B * (unsigned)P, kp = (unsigned)k * (unsigned)P;
-    SelLayout l;
-    l.off_c = 8u * bp;
-    l.off_phi = l.off_c + ((mode & SEL_FAST) ? 20u * bp + 4u * (bp & 1u) : 0u);
-    l.off_phik = l.off_phi + ((mode & SEL_KEEPPHI) ? 48u * bp : 0u);
-    l.off_lab = l.off_phik + ((mode & SEL_FAST) ? 48u * kp : 0u);
-    l.total = l.off_lab + 4u * (unsigned)B * (unsigned)D;
-    return l;
-}
 
 // The WIDE selection (SEL_MAXB < B <= SEL_WIDEB) keeps what SelShared holds per batch position in dynamic LDS instead, behind the
 // launch's SelLayout:  score, key [B] f64 | id, pos, used, req [B] i32  (req: the re-queued ids of the fused gather + selection
@@ -363,7 +317,6 @@ struct SelWide {
     double *score, *key;
     int *id, *pos, *used, *req;
 };
-__host__ __device__ inline unsigned sel_wide_off(const SelLayout &l) { return (l.total + 7u) & ~7u; }
 __host__ __device__ inline SelWide sel_wide(unsigned char *smem, const SelLayout &l, int B)
 {
     SelWide w;
@@ -372,12 +325,6 @@ __host__ __device__ inline SelWide sel_wide(unsigned char *smem, const SelLayout
     w.id = reinterpret_cast<int *>(w.key + B);
     w.pos = w.id + B, w.used = w.pos + B, w.req = w.used + B;
     return w;
-}
-// dynamic LDS of a selection launch, narrow or wide
-__host__ __device__ inline size_t sel_smem_bytes(int B, int P, int D, int k, int mode)
-{
-    const SelLayout l = sel_layout(B, P, D, k, mode);
-    return B > SEL_MAXB ? (size_t)sel_wide_off(l) + 32u * (size_t)B : (size_t)l.total;
 }
 
 // workgroup barrier that orders LDS traffic only: __syncthreads() also waits for every outstanding global store to be
@@ -1686,15 +1633,7 @@ __global__ __launch_bounds__(256) void k_fy_apply(const int *__restrict__ A, int
 // the first iteration bounds every later one.  A tile is closed when it is `wcap` positions wide or its expected load
 // reaches 70 % of the LDS entry capacity; a (never expected) overload is handled by sub-ranging the tile, a bucket or
 // sub-range overflow raises the error flag and the run is refused -- never a wrong permutation.
-#ifndef ACAV_FYA_CH
-#define ACAV_FYA_CH 8192
-#endif
-#ifndef ACAV_FYT_THREADS
-#define ACAV_FYT_THREADS 1024
-#endif
-constexpr int FYA_CH = ACAV_FYA_CH;  // steps per k_fy_part workgroup
-constexpr int FYA_THREADS = 1024;
-constexpr int64_t FY_TILED_MAX = 16 << 20;
+// (FYA_*, FYT_THREADS, FY_GROUP, FY_DEPTH, FY_NBUF, FY_SHARDS, FY_PACK_MAX, FY_TILED_MAX, GS_*: acav_mi_form.h)
 constexpr unsigned FY_EREF = 0x80000000u;
 // store flavours of the two scattered write streams of the position kernels (experiments: -DACAV_FY_BUCKET_NT, -DACAV_FY_SRC_NT,
 // -DACAV_FY_SRC_SC1; measured in tools/exp/NOTES_r03.md)
@@ -1710,33 +1649,7 @@ constexpr unsigned FY_EREF = 0x80000000u;
 #else
 #define FY_ST_SRC(p, v) (*(p) = (v))
 #endif
-#ifndef ACAV_FY_GROUP
-#define ACAV_FY_GROUP 16
-#endif
-constexpr int FY_GROUP = ACAV_FY_GROUP;  // iterations per launch of the position kernels and per cross-stream hand-off (an event
-                                         // wait + record on the content stream costs it ~10 us per group even when long satisfied)
-#ifndef ACAV_FY_DEPTH
-#define ACAV_FY_DEPTH 3
-#endif
-constexpr int FY_DEPTH = ACAV_FY_DEPTH;     // groups of perm buffers in flight: the position kernels run up to FY_DEPTH - 1 groups ahead
-constexpr int FY_NBUF = FY_DEPTH * FY_GROUP;  // of the gathers (a cross-stream hand-off costs 15-45 us: two deep, both hand-offs
-                                              // of a group sat on the critical cycle and left a ~30 us bubble per group)
-constexpr int GS_EPT = 4;          // outputs per thread of the gather
-// defaults of the gather's XCD subset (gs_block_map; ACAV_GS_XCDS / ACAV_GS_XCD_ROT / ACAV_GS_XCD_MIN_L override them per call).
-// Loop at L = 10^6, enqueue + drain us per iteration: 8 XCDs 28.5-29.4, 4 rotating 27.36, 4 fixed 32.38, 2 rotating 34.71, 1
-// rotating 51.81.  Crossover, 8 -> 4 rotating: L = 5 10^5 14.5 -> 15.0 / 15.3 and 2.5 10^5
-// 11.6 -> 11.9, 6.5 10^5 17.3 -> 18.4 (slower: a list well below an L2 stays resident on all eight), 8 10^5 (the list runs down
-// to 7.2 10^5 in the 20 000 iterations measured) 21.97 -> 22.14 / 22.19: the crossover is at about 8 10^5
-constexpr int GS_XCDS_DEFAULT = 4;
-constexpr bool GS_XCD_ROT_DEFAULT = true;
-constexpr long long GS_XCD_MIN_L_DEFAULT = 800000;
-constexpr int FY_SHARDS = 8;       // sub-buckets per tile (capg entries each), filled by workgroups b with b % 8 == shard
-constexpr int FYT_THREADS = ACAV_FYT_THREADS;  // k_fy_tile: the list walks are chains of dependent LDS reads -- many waves hide them
-// Bucket entries in 4 bytes instead of an int2 (step, target) -- half of the bucket stream that k_fy_part writes and k_fy_tile reads
-// back (8 of the 16 MB per iteration at L = 10^6).  A part workgroup bx appends to shard bx & 7 only, so the entry only needs
-//   [31:26] bx >> 3   [25:13] step - bx * FYA_CH   [12:0] target - q_lo (the tile-local position: tiles are at most 8192 wide)
-// which holds for lists of at most 512 part workgroups; longer lists (and ACAV_FY_PACK=0) keep the int2 form.
-constexpr int64_t FY_PACK_MAX = FYA_CH <= 8192 ? (int64_t)512 * FYA_CH : 0;
+// the 4-byte bucket entry of lists up to FY_PACK_MAX
 __device__ __forceinline__ unsigned fy_pack(int bx, int off, int p)
 {
     return ((unsigned)(bx >> 3) << 26) | ((unsigned)off << 13) | (unsigned)p;
@@ -2038,19 +1951,11 @@ __device__ __forceinline__ const unsigned *chunk_draw_ptr(const TileChunk &c, in
 // The grid is padded to 8 nx ceil(items / 8) workgroups; a padding workgroup has no work.  With fewer than 8 items whole XCDs
 // would idle: the 1-D grid then runs in the old x-fastest order.  Nothing crosses workgroups in the two kernels, so a wrong
 // placement guess costs speed only.  Plain C++ on both sides: acav_fy_block_map() exposes it to the tests without a device.
-constexpr int FY_XCDS = 8;
-struct FyGrid {
-    unsigned nx, ny, gz;  // the 3-D grid that the 1-D launch stands for; nx == 0: the launch IS that 3-D grid (ACAV_FY_XCD_AFFINE=0)
-};
+// (FyGrid, fy_affine_blocks and the launch grid fy_launch_grid: acav_mi_form.h)
 struct FyBlock {
     int x, y, z;
     bool work;
 };
-__host__ __device__ inline long long fy_affine_blocks(unsigned nx, unsigned ny, unsigned gz)
-{
-    const unsigned items = ny * gz;
-    return items < (unsigned)FY_XCDS ? (long long)nx * items : (long long)FY_XCDS * nx * ((items + FY_XCDS - 1) / FY_XCDS);
-}
 __host__ __device__ inline FyBlock fy_block_map(unsigned b, unsigned nx, unsigned ny, unsigned gz)
 {
     const unsigned items = ny * gz;
@@ -2070,17 +1975,6 @@ __device__ __forceinline__ FyBlock fy_this_block(const FyGrid &gr)
     if (gr.nx == 0) return {(int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, true};
     return fy_block_map(blockIdx.x, gr.nx, gr.ny, gr.gz);
 }
-// the launch grid of one of the two kernels: 1-D when `affine` and the 1-D grid fits a launch of `threads`-wide workgroups
-static dim3 fy_launch_grid(bool affine, unsigned nx, unsigned ny, unsigned gz, unsigned threads, FyGrid *gr)
-{
-    const long long nb = fy_affine_blocks(nx, ny, gz);
-    if (affine && nx > 0 && nb > 0 && nb <= 0x7fffffffll && nb * threads < (1ll << 32)) {
-        *gr = {nx, ny, gz};
-        return dim3((unsigned)nb);
-    }
-    *gr = {0u, ny, gz};
-    return dim3(nx, ny, gz);
-}
 
 // XCD subset of the gather (k_fy_gather_select_multi, single-chunk launches).  The candidate list A is read at uniformly random
 // positions by every gather workgroup, and at 10^6 candidates it is exactly one L2 in size: every XCD that runs gather workgroups
@@ -2091,19 +1985,11 @@ static dim3 fy_launch_grid(bool affine, unsigned nx, unsigned ny, unsigned gz, u
 // returns at once.  n_xcd = 8: g = b - 1 and no padding, the grid as it was.  As with fy_block_map the placement is observed,
 // not promised, and nothing crosses workgroups that did not before: a wrong guess costs speed only.  Plain C++ on both sides:
 // acav_gs_block_map() exposes it to the tests without a device.
-struct GsGrid {
-    unsigned n_xcd, rot;  // rot: the first class of the set, 0..7
-};
+// (GsGrid, the class mask gs_class_mask and the 1-D grid gs_grid_blocks: acav_mi_form.h)
 struct GsBlock {
     int g;  // the gather index, GS_SELECT or GS_NONE
 };
 constexpr int GS_SELECT = -1, GS_NONE = -2;
-// bit c: class c gathers
-__host__ __device__ inline unsigned gs_class_mask(unsigned n_xcd, unsigned rot)
-{
-    const unsigned m = ((1u << n_xcd) - 1u) << rot;  // n_xcd <= 8, rot < 8: 15 bits
-    return (m | (m >> FY_XCDS)) & ((1u << FY_XCDS) - 1u);
-}
 __host__ __device__ inline GsBlock gs_block_map(unsigned b, unsigned n_xcd, unsigned rot)
 {
     if (b == 0) return {GS_SELECT};
@@ -2111,20 +1997,6 @@ __host__ __device__ inline GsBlock gs_block_map(unsigned b, unsigned n_xcd, unsi
     if (!(mask >> c & 1u)) return {GS_NONE};
     // the gathering workgroups below b: n_xcd in every full row of eight, the set's classes below c in this one, less workgroup 0
     return {(int)(b / FY_XCDS * n_xcd + (unsigned)__builtin_popcount(mask & ((1u << c) - 1u)) - (mask & 1u))};
-}
-// the 1-D grid: the selection, and the shortest row behind it that holds gather_blocks gathering workgroups
-__host__ __device__ inline long long gs_grid_blocks(long long gather_blocks, unsigned n_xcd, unsigned rot)
-{
-    if (gather_blocks <= 0) return 1;
-    const unsigned mask = gs_class_mask(n_xcd, rot);
-    const long long t = gather_blocks - 1 + (mask & 1u);  // the last one is the t-th (from 0) workgroup of the set, workgroup 0 counted
-    unsigned r = (unsigned)(t % n_xcd), c = 0;
-    for (;; ++c)
-        if (mask >> c & 1u) {
-            if (r == 0) break;
-            --r;
-        }
-    return t / n_xcd * FY_XCDS + c + 1;
 }
 
 template <bool STAGED, bool PACK>
@@ -2360,9 +2232,8 @@ static const float *mi_weights(acav_mi *mi)
 // may be overwritten) is computed on the host; the two streams meet through events only.
 static int mi_ensure_gen_events(acav_mi *mi);
 struct MtStream {
-    static constexpr int NSLOT = 2;
+    static constexpr int NSLOT = MT_NSLOT;
     static constexpr int64_t PAD = 624;
-    static constexpr int64_t BLK_DEFAULT = 624 * 4096;  // 2.5 M words per lane block: ~0.85 ms of generation per hop
     int64_t T = 0, head = 0, blk = 0, S = 0, nblocks = 0, nsuper = 0, lmax = 0;
     int p0 = 0, W = 1, logW = 0;
     bool wraps = false;
@@ -2373,40 +2244,16 @@ struct MtStream {
     int64_t waited = -1;   // highest superblock `st` has been told to wait for
     int64_t freed = 0;     // superblocks [0, freed) are no longer read by any iteration still to be enqueued
 
-    // L: the longest list (one iteration reads at most L - 1 contiguous draws); span: the most draws one acquire() covers
-    // force_blk / force_W (acav_mt_stream_fill): the caller's lane block length (a multiple of 624) and lane count (a power of
-    // two) instead of the plan's own; with more than NSLOT superblocks it must keep W blk >= 2 span itself
+    // L: the longest list (one iteration reads at most L - 1 contiguous draws); span, force_blk, force_W: mt_pick_lanes
+    // (acav_mi_form.h), which decides the lane blocks, the lanes and the superblocks
     int plan(acav_mi *mi, hipStream_t consumer, const uint32_t *mtbuf, int idx, int64_t total_draws, int64_t L, int64_t span,
              hipStream_t generator = nullptr, int64_t force_blk = 0, int force_W = 0)
     {
         T = total_draws;
         p0 = idx;
-        head = 624 - p0;
         lmax = L;
-        const int64_t gen = T > head ? T - head : 0;  // words that must be generated past the host block
-        if (force_blk > 0) {
-            blk = force_blk;
-            nblocks = (gen + blk - 1) / blk;
-            W = force_W;
-        } else if (gen <= BLK_DEFAULT) {  // a single lane block, cut to size
-            W = 1;
-            blk = 624 * ((gen + 623) / 624);
-            nblocks = gen > 0 ? 1 : 0;
-        } else {
-            blk = BLK_DEFAULT;
-            nblocks = (gen + blk - 1) / blk;
-            W = 1;
-            while (W < 32 && W < nblocks) W *= 2;
-            if ((nblocks + W - 1) / W > NSLOT && (int64_t)W * blk < 2 * span) {  // a slot must hold what one acquire() covers twice over
-                blk = 624 * ((2 * span + 624 * (int64_t)W - 1) / (624 * (int64_t)W));
-                nblocks = (gen + blk - 1) / blk;
-            }
-        }
-        logW = 0;
-        while ((1 << logW) < W) ++logW;
-        S = (int64_t)W * blk;
-        nsuper = nblocks ? (nblocks + W - 1) / W : 0;
-        wraps = nsuper > NSLOT;
+        const MtLanes ml = mt_pick_lanes(total_draws, idx, span, force_blk, force_W);
+        head = ml.head, blk = ml.blk, S = ml.S, nblocks = ml.nblocks, nsuper = ml.nsuper, W = ml.W, logW = ml.logW, wraps = ml.wraps;
         st = consumer;
         smt = generator ? generator : mi->st_mt;
         ACAV_TRY(mi_ensure_gen_events(mi));  // (created on first need: acav_mi_create)
@@ -2515,86 +2362,22 @@ struct MtStream {
     }
 };
 
-// Tiling of the tiled Fisher-Yates for a list of (at most) L0 candidates; see the kernels' header comment.
-struct FyPlan {
-    int gsh = 4, wcap = 256, ecap = 256, ecap_lds = 256, capg = 512, NT = 0;
-    std::vector<unsigned short> table;  // (e >> gsh) -> tile
-    std::vector<int> ebound;            // tile t covers e in [ebound[t], ebound[t+1])
-    void build(int64_t L0)
-    {
-        int cap = 256, cap_max = 8192;
-        if (const char *v = getenv("ACAV_FY_CAP")) {  // experiments: smaller tiles (more workgroups per CU)
-            const int x = atoi(v);
-            if (x >= 256 && x <= 8192 && (x & (x - 1)) == 0) cap_max = x;
-        }
-        // at least ~32 tiles per iteration (the kernels take FY_GROUP iterations per launch: hundreds of workgroups); smaller
-        // tiles only multiply 1024-thread workgroups with a few hundred entries each (8 x 100k chunks in lockstep: 4.85 us per
-        // chunk-iteration at 128 tiles, 4.0 at 32)
-        int tiles_min = 32;
-        if (const char *v = getenv("ACAV_FY_TILES_MIN")) tiles_min = atoi(v) > 0 ? atoi(v) : tiles_min;
-        while (cap < cap_max && (int64_t)cap * tiles_min < L0) cap *= 2;
-        wcap = ecap = cap;
-        // capacity of ONE shard of a tile's bucket: with many k_fy_part workgroups the shards fill evenly (an eighth of
-        // the tile's load each, 4x headroom); with few, one shard may receive everything
-        capg = (L0 + FYA_CH - 1) / FYA_CH >= 64 ? cap / 2 : 2 * cap;
-        gsh = 0;
-        while ((1 << gsh) < cap / 16) ++gsh;
-        const int gran = 1 << gsh;
-        const double limit = 0.7 * ecap, lnL = log((double)L0);
-        table.assign((size_t)((L0 + gran - 1) >> gsh) + 1, 0);
-        ebound.clear();
-        int64_t e = 0;
-        while (e < L0) {
-            int width = 0;
-            double mass = 0.0;
-            do {  // expected pulls on the granule [x, x + gran): at most gran * ln(L0 / (x + 1))
-                const double x = (double)(e + width);
-                const double m = gran * (lnL - log(x + 1.0)) + 1.0;
-                if (width > 0 && mass + (m > 0 ? m : 0) > limit) break;
-                mass += m > 0 ? m : 0;
-                width += gran;
-            } while (width < wcap && e + width < L0);
-            const int t = (int)ebound.size();
-            ebound.push_back((int)e);
-            for (int64_t x = e; x < e + width; x += gran) table[(size_t)(x >> gsh)] = (unsigned short)t;
-            e += width;
-        }
-        ebound.push_back((int)e);
-        NT = (int)ebound.size() - 1;
-        ecap_lds = ecap;
-        if (const char *v = getenv("ACAV_FY_ECAP")) {  // tests: force the sub-ranged overload path
-            const int x = atoi(v);
-            if (x >= 16 && x < ecap) ecap_lds = x;
-        }
-    }
-    size_t tile_smem() const { return (size_t)wcap * 8 + (size_t)ecap_lds * 8; }
-};
-
 // dynamic LDS of a selection launch; a WIDE batch whose label rows [B][D] do not fit one workgroup's LDS beside the rest is
 // refused here (the narrow launches keep leaving that to the runtime)
 static int sel_smem_checked(int B, int P, int D, int k, int mode, size_t *out)
 {
     *out = sel_smem_bytes(B, P, D, k, mode);
-    constexpr size_t lds = 160 * 1024;  // per workgroup on gfx950
-    ACAV_REQUIRE(B <= SEL_MAXB || *out + sizeof(SelSharedW) <= lds, ACAV_EINVAL,
+    ACAV_REQUIRE(sel_smem_fits(B, *out), ACAV_EINVAL,
                  "batch_size %d x %d clusterings (x %d pairs) needs %zu bytes of LDS: more than a workgroup has (%zu); lower batch_size",
-                 B, D, P, *out + sizeof(SelSharedW), lds);
+                 B, D, P, *out + sizeof(SelSharedW), SEL_LDS_PER_WG);
     return ACAV_OK;
 }
 
-static size_t fy_part_smem(int NT, size_t ntab, bool staged, bool pack = false)
+// the handle's buffers for the tiling fp of a list of (at most) L candidates (fy_pick_tiling): table, tile bounds, sharded buckets
+// and their counters (one set per iteration of a group; zeroed), error flag (cleared), src / g (per iteration of a group) and perm
+// (FY_DEPTH groups deep) buffers; uploads are stream-ordered on st (fp must stay alive until st has been synchronised)
+static int fy_setup(acav_mi *mi, int64_t L, int bcap, const FyPlan &fp, hipStream_t st)
 {
-    return sizeof(int) * ((staged ? 3 : 2) + (pack ? 1 : 0)) * (size_t)NT + (staged ? sizeof(int2) * FYA_CH + sizeof(int) * 16 : 0) +
-           sizeof(unsigned short) * ntab;
-}
-
-// tiling of a list of (at most) L candidates and the handle's buffers for it: table, tile bounds, sharded buckets and their
-// counters (one set per iteration of a group; zeroed), error flag (cleared), src / g (per iteration of a group) and perm
-// (two groups deep) buffers; uploads are stream-ordered on st (fp must stay alive
-// until st has been synchronised)
-static int fy_setup(acav_mi *mi, int64_t L, int bcap, FyPlan &fp, hipStream_t st)
-{
-    fp.build(L);
     ACAV_TRY(mi->fy_table.ensure(sizeof(unsigned short) * fp.table.size()));
     ACAV_TRY(mi->fy_bounds.ensure(sizeof(int) * fp.ebound.size()));
     ACAV_TRY(mi->fy_bucket.ensure(sizeof(int2) * (size_t)FY_GROUP * fp.NT * FY_SHARDS * fp.capg));
@@ -2859,26 +2642,6 @@ static int check_chunk_args(int c, const acav_mi *mi, const int64_t *candidates,
     return ACAV_OK;
 }
 
-// The iteration plan of one chunk: how many iterations the greedy loop runs and how many MT19937 draws their
-// permutations take.  Every L_t is known on the host (the list shrinks by dl per iteration: no device feedback).
-struct GreedyPlan {
-    int64_t iters = 0, draws = 0;
-    int64_t short_l = -1;  // >= 0: the list is down to this many candidates, fewer than a batch, with the subset not yet full (ACAV_ERANGE)
-};
-static GreedyPlan greedy_plan(int64_t L, int64_t subset, int B, int k, int64_t dl, int64_t max_iters)
-{
-    GreedyPlan gp;
-    int64_t l = L;
-    for (int64_t nS = 0; nS < subset && (max_iters < 0 || gp.iters < max_iters); nS += k, l -= dl, ++gp.iters) {
-        if (l < B) {
-            gp.short_l = l;
-            break;
-        }
-        gp.draws += l > 1 ? l - 1 : 0;
-    }
-    return gp;
-}
-
 // Enqueues the copies of one chunk's results (S, GAIN, the traces) to the host on `st` and fills its counts.
 static int read_back(acav_mi *mi, hipStream_t st, int64_t iters, int64_t subset, int B, int k, int64_t *S_out, double *GAIN_out,
                      const TiledExtras &ex, int64_t *n_selected, int64_t *n_iters)
@@ -2900,10 +2663,104 @@ static int read_back(acav_mi *mi, hipStream_t st, int64_t iters, int64_t subset,
 }
 
 // The greedy run of ONE chunk on the global-atomic Fisher-Yates kernels (k_fy_build / k_fy_apply) and k_mi_select, on the
-// handle's own streams: lists beyond FY_TILED_MAX, and ACAV_FY_LEGACY=1.
+// handle's own streams: lists beyond FY_TILED_MAX, and ACAV_FY_LEGACY=1.  iters, draws: the chunk's plan (GreedyForm).
 static int run_greedy_legacy(acav_mi *mi, const int64_t *candidates, int64_t L, const int64_t *start, int ns, int64_t subset,
-                             int B, int k, int keep_unselected, acav_rng *rng, int64_t *S_out, double *GAIN_out,
-                             int64_t *n_selected, int64_t *n_iters, const TiledExtras &ex);
+                             int B, int k, int keep_unselected, int64_t iters, int64_t draws, acav_rng *rng, int64_t *S_out,
+                             double *GAIN_out, int64_t *n_selected, int64_t *n_iters, const TiledExtras &ex);
+
+// the experiment switches of the greedy loop (GreedySwitches, acav_mi_form.h), read from the environment in this one place and on
+// EVERY call of an entry point: the tests change them between calls of one process
+static GreedySwitches greedy_switches()
+{
+    auto starts = [](const char *name, char c) {
+        const char *v = getenv(name);
+        return v && v[0] == c;
+    };
+    auto number = [](const char *name, int unset) {
+        const char *v = getenv(name);
+        return v ? atoi(v) : unset;
+    };
+    GreedySwitches sw;
+    sw.legacy = starts("ACAV_FY_LEGACY", '1');
+    sw.pack = !starts("ACAV_FY_PACK", '0');
+    sw.xcd_affine = !starts("ACAV_FY_XCD_AFFINE", '0');
+    sw.gs_xcds_text = getenv("ACAV_GS_XCDS");
+    sw.gs_xcds = number("ACAV_GS_XCDS", GS_XCDS_DEFAULT);
+    if (const char *v = getenv("ACAV_GS_XCD_ROT")) sw.gs_rot = v[0] == '1';
+    if (const char *v = getenv("ACAV_GS_XCD_MIN_L")) sw.gs_min_l = atoll(v);
+    sw.part_direct = getenv("ACAV_FY_PART_DIRECT") != nullptr;
+    sw.fy_cap = number("ACAV_FY_CAP", 0);
+    sw.fy_tiles_min = number("ACAV_FY_TILES_MIN", 0);
+    sw.fy_ecap = number("ACAV_FY_ECAP", 0);
+    sw.share_gen = number("ACAV_MI_SHARE_GEN", 1);
+    sw.queue_probe = !starts("ACAV_MI_QUEUE_PROBE", '0');
+    sw.timing = getenv("ACAV_MI_TIMING") != nullptr;
+    return sw;
+}
+
+// The launch plan of a call of either entry point: the shape from the arguments and the handles, the form from greedy_pick_form.
+static GreedyForm greedy_form(acav_mi *const *mis, int nchunks, const int64_t *L, const int64_t *subset, int B, int k,
+                              int keep_unselected, int64_t max_iters, const GreedySwitches &sw)
+{
+    GreedyShape s{nchunks, L, subset, B, k, keep_unselected != 0, max_iters, 1, 1, false};
+    for (int c = 0; c < nchunks; ++c) {
+        s.pmax = mis[c]->P > s.pmax ? mis[c]->P : s.pmax;
+        s.dmax = mis[c]->D > s.dmax ? mis[c]->D : s.dmax;
+        s.weighted = s.weighted || mis[c]->weighted;
+    }
+    return greedy_pick_form(s, sw);
+}
+
+// The error of a refused form.  `multi`: the call names its chunks (acav_mi_run_greedy_multi on the legacy path).
+static int greedy_refuse(const GreedyForm &f, const GreedySwitches &sw, bool multi)
+{
+    const int c = f.refused_chunk, B = f.B;
+    const long long left = (long long)f.short_l;
+    ACAV_REQUIRE(f.refusal != GREEDY_BAD_XCDS, ACAV_EINVAL, "ACAV_GS_XCDS=%s: 1, 2, 4 or 8", sw.gs_xcds_text);
+    if (f.refusal == GREEDY_SHORT_LIST) {
+        ACAV_REQUIRE(f.path != GREEDY_TILED, ACAV_ERANGE,
+                     "chunk %d: %lld candidates left < batch_size %d: the reference's topk(k=floor(B/k*B')) raises here "
+                     "(batch.py:143-150)", c, left, B);
+        ACAV_REQUIRE(!multi, ACAV_ERANGE, "chunk %d: %lld candidates left < batch_size %d (batch.py:143-150)", c, left, B);
+        ACAV_REQUIRE(false, ACAV_ERANGE,
+                     "%lld candidates left < batch_size %d: the reference's topk(k=floor(B/k*B')) raises here "
+                     "(batch.py:143-150)", left, B);
+    }
+    ACAV_REQUIRE(f.refusal != GREEDY_LDS, ACAV_EINVAL,
+                 "batch_size %d x %d clusterings (x %d pairs) needs %zu bytes of LDS: more than a workgroup has (%zu); lower batch_size",
+                 B, f.dmax, f.pmax, f.sel_smem + sizeof(SelSharedW), SEL_LDS_PER_WG);
+    return ACAV_OK;
+}
+
+static dim3 to_dim3(const Grid3 &g) { return dim3(g.x, g.y, g.z); }
+using clk = std::chrono::steady_clock;
+static double ms_since(clk::time_point a) { return std::chrono::duration<double, std::milli>(clk::now() - a).count(); }
+
+// What both greedy paths set up alike for one chunk on the stream `st` (the two paths order it on different streams): the candidate
+// list as int32 in A0, A1, the batch buffer of `batch_ints`, S / G and the trace buffers of `iters` iterations, and the forced
+// positions, range-checked and uploaded.  t_ids: the time of the id conversion is added to it.
+static int greedy_chunk_buffers(acav_mi *mi, const int64_t *candidates, int64_t L, int B, int k, int64_t iters, size_t batch_ints,
+                                const TiledExtras &ex, hipStream_t st, double *t_ids = nullptr)
+{
+    ACAV_TRY(mi->A0.ensure(sizeof(int) * (size_t)(L + B)));  // before the conversion: ensure() does not copy
+    { const auto t0 = clk::now();
+    ACAV_TRY(ids_to_device32(mi, candidates, L, mi->stage, mi->A0, st));
+    if (t_ids) *t_ids += ms_since(t0); }
+    ACAV_TRY(mi->A1.ensure(sizeof(int) * (size_t)(L + B)));
+    ACAV_TRY(mi->batch.ensure(sizeof(int) * batch_ints));
+    ACAV_TRY(mi->S.ensure(sizeof(long long) * (size_t)(iters * k + 1)));
+    ACAV_TRY(mi->G.ensure(sizeof(double) * (size_t)(iters * k + 1)));
+    if (ex.trace_pos) ACAV_TRY(mi->tr_pos.ensure(sizeof(int) * (size_t)(iters * k + 1)));
+    if (ex.trace_ids) ACAV_TRY(mi->tr_ids.ensure(sizeof(long long) * (size_t)(iters * B + 1)));
+    if (ex.trace_scores) ACAV_TRY(mi->tr_sc.ensure(sizeof(double) * (size_t)(iters * B + 1)));
+    if (ex.forced_pos) {
+        for (int64_t i = 0; i < iters * k; ++i)
+            ACAV_REQUIRE(ex.forced_pos[i] >= 0 && ex.forced_pos[i] < B, ACAV_EINVAL, "forced position out of range");
+        ACAV_TRY(mi->forced.ensure(sizeof(int) * (size_t)(iters * k + 1)));
+        ACAV_HIP_TRY(hipMemcpyAsync(mi->forced.p, ex.forced_pos, sizeof(int) * (size_t)(iters * k), hipMemcpyHostToDevice, st));
+    }
+    return ACAV_OK;
+}
 
 // The greedy run on the lane generator + tiled Fisher-Yates kernels: one chunk (acav_mi_run_greedy) or several independent
 // chunks in lockstep (acav_mi_run_greedy_multi; one handle, candidate list, start set, subset size and generator each;
@@ -2912,12 +2769,186 @@ static int run_greedy_legacy(acav_mi *mi, const int64_t *candidates, int64_t L, 
 // iterations) run on st_fy ahead of the gathers + selections on the main stream; perm is buffered FY_DEPTH groups
 // deep and the streams meet through one event pair per group (a cross-stream hand-off costs ~20 us of latency,
 // an event record / wait a few us of queue time: per iteration they sat on the critical path).
-static int run_greedy_tiled(acav_mi **mis, int nchunks, const int64_t *const *candidates, const int64_t *L,
-                            const int64_t *const *start, const int *ns, const int64_t *subset, int B, int k,
-                            int keep_unselected, acav_rng **rngs, int64_t *const *S_out, double *const *GAIN_out,
-                            int64_t *n_selected, int64_t *n_iters, const TiledExtras &ex)
+// What to launch comes from the GreedyForm (acav_mi_form.h); run_greedy_tiled below runs its three parts: tiled_prepare_chunk per
+// chunk, tiled_enqueue, tiled_finish.
+struct TiledRun {
+    acav_mi *const *mis;
+    const int64_t *L;
+    const GreedyForm &f;
+    const GreedySwitches &sw;
+    const TiledExtras &ex;
+    hipStream_t st, sf;  // the lead's content stream and its position stream
+    std::vector<TileChunk> desc;
+    std::vector<MtStream> streams;
+    double t_ids = 0, t_fy = 0, t_mt = 0, t_add = 0;
+    long long groups_1d = 0, groups_3d = 0;  // launch form of the tile / resolve grids, per group (diagnostics: ACAV_MI_TIMING prints it)
+    long long gs_launches_sub = 0;           // gather launches on a subset of the XCDs (the others ran on all eight)
+};
+
+// One chunk's start samples, buffers, id conversion, tile tables, generator plan and TileChunk descriptor.
+static int tiled_prepare_chunk(TiledRun &r, int c, const int64_t *candidates, const int64_t *start, int ns, acav_rng *rng)
+{
+    acav_mi *mi = r.mis[c];
+    const GreedyForm &f = r.f;
+    const int64_t L = r.L[c], itc = f.iters[(size_t)c];
+    const TiledExtras &ex = r.ex;
+    ACAV_HIP_TRY(hipStreamSynchronize(mi->ctx.stream));  // whatever the handle was doing on its own stream is over
+    if (f.nchunks > 1) mi->lockstep_member = true;
+    // the staging block at its final size BEFORE the start samples use it: growing a DevBuf that is in use synchronises the
+    // device (it cannot know which stream still reads the old block) -- 4.2 ms in a process with a few dozen streams, ten times
+    // per lockstep group = 38 of a group's 41 ms of set-up (what the timers called "ids": the copy itself takes 0.02 ms)
+    if (!is_device_ptr(candidates)) ACAV_TRY(mi->stage.ensure(sizeof(int64_t) * (size_t)L));
+    { const auto t0 = clk::now();
+    if (ns) ACAV_TRY(acav_mi_add_samples(mi, start, ns));  // batch.py:215
+    r.t_add += ms_since(t0); }
+    // the conversion runs on the LEAD's content stream, the one the loop's gathers run on: ordered before them by the stream itself
+    // (on the chunk's own stream the conversion kernel was ordered by nothing but its brevity)
+    ACAV_TRY(greedy_chunk_buffers(mi, candidates, L, f.B, f.k, itc, 2 * (size_t)f.bcap * (size_t)(1 + mi->D), ex, r.st, &r.t_ids));
+    const FyPlan &fp = f.tiling[(size_t)c];
+    { const auto t0 = clk::now();
+    ACAV_TRY(fy_setup(mi, L, f.bcap, fp, r.st));
+    r.t_fy += ms_since(t0); }
+    // hand the host MT19937 stream to the device: W lanes generate it superblock by superblock on their own stream
+    // (MtStream); nothing they do depends on what gets selected (L shrinks by a fixed amount per iteration)
+    unsigned mtbuf[625];
+    int idx = 0;
+    ACAV_TRY(acav_rng_get_state(rng, mtbuf, &idx));
+    MtStream &ms = r.streams[(size_t)c];
+    // Chunks in lockstep: ALL their generators run on the lead handle's generator stream (round 5).  A generator launch is rare
+    // (a superblock of 82 M words lasts ~800 iterations of a 100k-clip chunk) and off the critical path, but ten generator
+    // streams are ten more queues for the runtime to service: with GPU_MAX_HW_QUEUES = 16 (which ten clusterings training
+    // side by side need, acav100m_amd/__init__.py) the lockstep loop ran at 7.4 us per chunk-iteration instead of 3.8;
+    // on one shared stream 3.66 at either setting.  ACAV_MI_SHARE_GEN=0: a stream per chunk again, =n: n streams (A/B).
+    const int nshare = r.sw.share_gen;
+    acav_mi *gen = nshare > 0 ? r.mis[c % nshare] : mi;  // the handle whose generator stream this chunk's generator runs on
+    ACAV_TRY(mi_ensure_streams(gen));
+    ACAV_TRY(mi_ensure_gen_events(mi));
+    { const auto t0 = clk::now();
+    ACAV_TRY(ms.plan(mi, r.sf, mtbuf, idx, f.draws[(size_t)c], L, (int64_t)FY_GROUP * L, nshare > 0 ? gen->st_mt : nullptr));
+    r.t_mt += ms_since(t0); }
+    TileChunk &d = r.desc[(size_t)c];
+    d.ring = ms.ring + MtStream::PAD;
+    d.head = ms.head;
+    d.ring_words = ms.wraps ? MtStream::NSLOT * ms.S : ((long long)1 << 62);
+    d.table = mi->fy_table.as<unsigned short>(), d.ebound = mi->fy_bounds.as<int>();
+    d.bucket = mi->fy_bucket.as<int2>(), d.gcount = mi->fy_count.as<int>(), d.err = mi->fy_err.as<unsigned>();
+    for (int q = 0; q < FY_GROUP; ++q) d.src[q] = mi->fy_src[q].as<unsigned>(), d.g[q] = mi->fy_g[q].as<int>();
+    for (int q = 0; q < FY_NBUF; ++q) d.perm[q] = mi->fy_perm[q].as<unsigned>();
+    d.tailinv = mi->fy_tail.as<int>();
+    d.A[0] = mi->A0.as<int>(), d.A[1] = mi->A1.as<int>();
+    d.asg = mi->asg.as<int>(), d.pairs = mi->pairs.as<int>(), d.batch = mi->batch.as<int>();
+    d.Nc = mi->Nc.as<int>(), d.ac = mi->ac.as<int>(), d.bc = mi->bc.as<int>();
+    d.SN = mi->SN.as<double>(), d.Sa = mi->Sa.as<double>(), d.Sb = mi->Sb.as<double>();
+    d.phi = mi->phi.as<double>(), d.sc = mi->scalars.as<MiScalars>();
+    d.S = mi->S.as<long long>(), d.G = mi->G.as<double>();
+    d.forced = ex.forced_pos ? mi->forced.as<int>() : nullptr;
+    d.tr_pos = ex.trace_pos ? mi->tr_pos.as<int>() : nullptr;
+    d.tr_ids = ex.trace_ids ? mi->tr_ids.as<long long>() : nullptr;
+    d.tr_sc = ex.trace_scores ? mi->tr_sc.as<double>() : nullptr;
+    d.L0 = (int)L, d.iters = (int)itc, d.ntab = (int)fp.table.size(), d.gsh = fp.gsh, d.NT = fp.NT, d.capg = fp.capg;
+    d.ecap = fp.ecap_lds, d.wcap = fp.wcap, d.D = mi->D, d.C = mi->C, d.P = mi->P, d.bcap = f.bcap;
+    d.w = mi_weights(mi);
+    return ACAV_OK;
+}
+
+// The form's kernel instantiations, with the dynamic LDS the form sized for them.
+struct TiledKernels {
+    decltype(&k_fy_part_multi<true, true>) part;
+    decltype(&k_fy_tile_multi<true>) tile;
+    decltype(&k_fy_resolve_multi<true>) resolve;
+    decltype(&k_fy_gather_select_multi<true, true>) gs;
+};
+static int tiled_kernels(const GreedyForm &f, TiledKernels *kn)
+{
+    kn->tile = f.pack ? k_fy_tile_multi<true> : k_fy_tile_multi<false>;
+    ACAV_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kn->tile), hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.tile_smem));
+    kn->part = f.part_staged ? (f.pack ? k_fy_part_multi<true, true> : k_fy_part_multi<true, false>)
+                             : (f.pack ? k_fy_part_multi<false, true> : k_fy_part_multi<false, false>);
+    if (f.part_staged)
+        ACAV_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kn->part), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)f.part_smem));
+    kn->gs = f.wide ? (f.weighted ? k_fy_gather_select_multi<true, true> : k_fy_gather_select_multi<false, true>)
+                    : (f.weighted ? k_fy_gather_select_multi<true, false> : k_fy_gather_select_multi<false, false>);
+    kn->resolve = f.wide ? k_fy_resolve_multi<true> : k_fy_resolve_multi<false>;
+    if (f.sel_smem > 48 * 1024)
+        ACAV_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kn->gs), hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.sel_smem));
+    return ACAV_OK;
+}
+
+// The loop: the form's kernels on greedy_group_grids' grids, group by group -- launches and events only.
+static int tiled_enqueue(TiledRun &r, const TiledKernels &kn)
+{
+    const GreedyForm &f = r.f;
+    acav_mi *lead = r.mis[0];
+    hipStream_t st = r.st, sf = r.sf;
+    const int B = f.B, k = f.k, dl = (int)f.dl, keep = f.keep_unselected ? 1 : 0;
+    const TileChunk *dcd = lead->chunk_desc.as<TileChunk>();
+    std::vector<int64_t> r0((size_t)f.nchunks, 0);  // per chunk: the first draw of the group, counted from the first draw of the run
+    for (int64_t g0 = 0; g0 < f.iters_max; g0 += FY_GROUP) {
+        const GreedyGroup g = greedy_group_grids(f, g0, &r.gs_launches_sub);
+        // ---- st_fy: the positions of the group's iterations (the gathers of the group FY_DEPTH back are done with this buffer set)
+        if (g0 >= FY_DEPTH * FY_GROUP) ACAV_HIP_TRY(hipStreamWaitEvent(sf, lead->ev_gather[g.ge], 0));
+        for (int c = 0; c < f.nchunks; ++c) {
+            const int64_t nd = greedy_group_draws(f, r.L[c], c, g0);
+            if (nd == 0) continue;
+            const unsigned *unused = nullptr;
+            ACAV_TRY(r.streams[(size_t)c].acquire(r0[(size_t)c], nd, &unused));
+            r0[(size_t)c] += nd;
+        }
+        hipLaunchKernelGGL(kn.part, to_dim3(g.part), dim3(FYA_THREADS), f.part_smem, sf, dcd, (int)g0, dl);
+        for (int c = 0; c < f.nchunks; ++c)
+            if (g0 < f.iters[(size_t)c]) ACAV_TRY(r.streams[(size_t)c].release(r0[(size_t)c]));  // k_fy_part is the only reader of the draws
+        ++(g.one_d ? r.groups_1d : r.groups_3d);
+        hipLaunchKernelGGL(kn.tile, to_dim3(g.tile), dim3(FYT_THREADS), f.tile_smem, sf, dcd, (int)g0, dl, g.gr_tile);
+        hipLaunchKernelGGL(kn.resolve, to_dim3(g.resolve), dim3(256), 0, sf, dcd, (int)g0, dl, keep ? B - k : 0, g.gr_res);
+        ACAV_HIP_TRY(hipEventRecord(lead->ev_tile[g.ge], sf));
+        // ---- main stream: the group's gathers (each with the selection of the iteration before it), back to back
+        ACAV_HIP_TRY(hipStreamWaitEvent(st, lead->ev_tile[g.ge], 0));
+        for (unsigned q = 0; q < g.gz; ++q)
+            hipLaunchKernelGGL(kn.gs, to_dim3(g.gather[q]), dim3(256), f.sel_smem, st, dcd, (int)(g0 + q), dl, B, k, f.sel_mode, keep,
+                               g.gr_gs[q]);
+        ACAV_HIP_TRY(hipGetLastError());
+        ACAV_HIP_TRY(hipEventRecord(lead->ev_gather[g.ge], st));
+    }
+    if (f.iters_max > 0)  // the selection of the last iteration
+        hipLaunchKernelGGL(kn.gs, dim3(1u, (unsigned)f.nchunks), dim3(256), f.sel_smem, st, dcd, (int)f.iters_max, dl, B, k,
+                           f.sel_mode, keep, GsGrid{(unsigned)FY_XCDS, 0u});
+    ACAV_HIP_TRY(hipGetLastError());
+    return ACAV_OK;
+}
+
+// Read-back, the generators' states and the overflow flags, chunk by chunk.
+static int tiled_finish(TiledRun &r, const int64_t *subset, acav_rng **rngs, int64_t *const *S_out, double *const *GAIN_out,
+                        int64_t *n_selected, int64_t *n_iters)
+{
+    const GreedyForm &f = r.f;
+    for (int c = 0; c < f.nchunks; ++c) {
+        ACAV_TRY(read_back(r.mis[c], r.st, f.iters[(size_t)c], subset[c], f.B, f.k, S_out[c], GAIN_out[c], r.ex,
+                           n_selected ? n_selected + c : nullptr, n_iters ? n_iters + c : nullptr));
+    }
+    ACAV_HIP_TRY(hipStreamSynchronize(r.st));
+    for (int c = 0; c < f.nchunks; ++c) {  // every generator continues on the host where its chunk stopped drawing
+        ACAV_HIP_TRY(hipStreamSynchronize(r.streams[(size_t)c].smt ? r.streams[(size_t)c].smt : r.mis[c]->st_mt));
+        unsigned mtbuf[625];
+        int idx = 0;
+        ACAV_TRY(acav_rng_get_state(rngs[c], mtbuf, &idx));
+        ACAV_TRY(r.streams[(size_t)c].final_state(mtbuf, &idx));
+        ACAV_TRY(acav_rng_set_state(rngs[c], mtbuf, idx));
+        unsigned ferr = 0;
+        ACAV_HIP_TRY(hipMemcpy(&ferr, r.mis[c]->fy_err.p, sizeof(ferr), hipMemcpyDeviceToHost));
+        ACAV_REQUIRE(ferr == 0, ACAV_ESTATE, "tiled Fisher-Yates: a tile bucket of chunk %d overflowed (flags %u); re-run with "
+                                             "ACAV_FY_LEGACY=1", c, ferr);
+    }
+    return ACAV_OK;
+}
+
+static int run_greedy_tiled(acav_mi **mis, const GreedyForm &f, const GreedySwitches &sw, const int64_t *const *candidates,
+                            const int64_t *L, const int64_t *const *start, const int *ns, const int64_t *subset, acav_rng **rngs,
+                            int64_t *const *S_out, double *const *GAIN_out, int64_t *n_selected, int64_t *n_iters,
+                            const TiledExtras &ex, double t_form)
 {
     acav_mi *lead = mis[0];
+    const int nchunks = f.nchunks;
     // Three streams on three hardware queues (mi_separate_queues): checked once per handle, and only where it matters and cannot
     // hurt -- ONE chunk over a long candidate list (the position and content streams of a 10^6-candidate loop overlap for ~30 us
     // per iteration).  Probing each of the 125 handles of the cfg5 slice at creation cost the slice 0.6 s (2.49 -> 3.15 s of selection),
@@ -2925,249 +2956,43 @@ static int run_greedy_tiled(acav_mi **mis, int nchunks, const int64_t *const *ca
     // group's launches): 3-8 streams replaced over 52 groups and no effect on the lockstep loop's own bimodality -- the cfg5 slice's
     // selection takes 2.46-2.52 s in most processes and 3.3-4.0 s in about one of three, with the probe (3.98 / 2.46) and without
     // (3.53 / 2.48 / 2.50): tools/exp/NOTES_r06.md section 5.
-    if (nchunks == 1 && lead->queue_probe_pending && L[0] >= 250000) {
-        const char *vq = getenv("ACAV_MI_QUEUE_PROBE");
-        if (!(vq && vq[0] == '0')) mi_separate_queues(lead);
+    if (lead->queue_probe_pending && nchunks == 1 && L[0] >= QUEUE_PROBE_MIN_L) {
+        if (f.queue_probe) mi_separate_queues(lead);
         lead->queue_probe_pending = false;
     }
     ACAV_TRY(mi_ensure_streams(lead));
-    hipStream_t st = lead->ctx.stream, sf = lead->st_fy;
-    const bool timing = getenv("ACAV_MI_TIMING") != nullptr;
-    using clk = std::chrono::steady_clock;
-    auto ms_since = [](clk::time_point a) { return std::chrono::duration<double, std::milli>(clk::now() - a).count(); };
+    TiledRun r{mis, L, f, sw, ex, lead->ctx.stream, lead->st_fy, std::vector<TileChunk>((size_t)nchunks), std::vector<MtStream>((size_t)nchunks)};
+    r.t_fy = t_form;  // the tilings were built with the form: their time stays with the tables' and the set-up's
     const auto t_setup0 = clk::now();
-    double t_ids = 0, t_fy = 0, t_mt = 0, t_add = 0;
-    const int64_t dl = B - (keep_unselected ? B - k : 0);  // candidates consumed per iteration
-    const bool wide = B > SEL_MAXB;
-    const int bcap = wide ? B : SEL_MAXB;  // batch capacity of tailinv and the batch buffers: the narrow layout up to SEL_MAXB
-    std::vector<TileChunk> desc((size_t)nchunks);
-    std::vector<int64_t> iters((size_t)nchunks, 0), r0((size_t)nchunks, 0);
-    std::vector<FyPlan> plans((size_t)nchunks);
-    std::vector<MtStream> streams((size_t)nchunks);
-    int64_t iters_max = 0, lmax = 0;
-    for (int c = 0; c < nchunks; ++c) lmax = L[c] > lmax ? L[c] : lmax;
-    const char *vpack = getenv("ACAV_FY_PACK");  // =0: the 8-byte bucket entries (A/B)
-    const bool pack = lmax <= FY_PACK_MAX && !(vpack && vpack[0] == '0');
-    // =0: the 3-D grids of the tile and resolve kernels, every item's workgroups dealt over all XCDs (A/B; see fy_block_map)
-    const char *vaff = getenv("ACAV_FY_XCD_AFFINE");
-    const bool xcd_affine = !(vaff && vaff[0] == '0');
-    // The gather's XCD subset (gs_block_map), single-chunk runs only -- the per-chunk lists of a lockstep launch are a tenth of an
-    // L2 and keep their 2-D grid.  ACAV_GS_XCDS = 1, 2, 4: that many XCDs gather, 8: all of them (no padding); ACAV_GS_XCD_ROT=1
-    // moves the set by its size every launch, =0 keeps it at classes 0..n-1; ACAV_GS_XCD_MIN_L: the list length of a launch from
-    // which the subset form is used (below it the list does not compete for an L2 and fewer CUs only slow the gather down).
-    const char *vgx = getenv("ACAV_GS_XCDS"), *vgr = getenv("ACAV_GS_XCD_ROT"), *vgl = getenv("ACAV_GS_XCD_MIN_L");
-    int gs_xcds = vgx ? atoi(vgx) : GS_XCDS_DEFAULT;
-    ACAV_REQUIRE(gs_xcds == 1 || gs_xcds == 2 || gs_xcds == 4 || gs_xcds == 8, ACAV_EINVAL, "ACAV_GS_XCDS=%s: 1, 2, 4 or 8", vgx);
-    const bool gs_rot = vgr ? vgr[0] == '1' : GS_XCD_ROT_DEFAULT;
-    const long long gs_min_l = vgl ? atoll(vgl) : GS_XCD_MIN_L_DEFAULT;
-    int pmax = 1, dmax = 1, ntmax = 1;
-    bool weighted = false;  // some chunk has pair weights: the weighted selection for the whole launch
-    size_t part_smem = 0, part_smem_staged = 0, tile_smem = 0;
-    for (int c = 0; c < nchunks; ++c) {
-        acav_mi *mi = mis[c];
-        ACAV_HIP_TRY(hipStreamSynchronize(mi->ctx.stream));  // whatever the handle was doing on its own stream is over
-        if (nchunks > 1) mi->lockstep_member = true;
-        // the staging block at its final size BEFORE the start samples use it: growing a DevBuf that is in use synchronises the
-        // device (it cannot know which stream still reads the old block) -- 4.2 ms in a process with a few dozen streams, ten times
-        // per lockstep group = 38 of a group's 41 ms of set-up (what the timers called "ids": the copy itself takes 0.02 ms)
-        if (!is_device_ptr(candidates[c])) ACAV_TRY(mi->stage.ensure(sizeof(int64_t) * (size_t)L[c]));
-        { const auto t0 = clk::now();
-        if (ns[c]) ACAV_TRY(acav_mi_add_samples(mi, start[c], ns[c]));  // batch.py:215
-        t_add += ms_since(t0); }
-        // plan: the number of iterations and every L_t are known on the host (no device feedback)
-        const GreedyPlan gp = greedy_plan(L[c], subset[c], B, k, dl, ex.max_iters);
-        ACAV_REQUIRE(gp.short_l < 0, ACAV_ERANGE,
-                     "chunk %d: %lld candidates left < batch_size %d: the reference's topk(k=floor(B/k*B')) raises here "
-                     "(batch.py:143-150)", c, (long long)gp.short_l, B);
-        const int64_t itc = gp.iters, draws = gp.draws;
-        iters[(size_t)c] = itc;
-        iters_max = itc > iters_max ? itc : iters_max;
-        lmax = L[c] > lmax ? L[c] : lmax;
-        pmax = mi->P > pmax ? mi->P : pmax;
-        dmax = mi->D > dmax ? mi->D : dmax;
-        const size_t Lc = (size_t)L[c];
-        ACAV_TRY(mi->A0.ensure(sizeof(int) * (Lc + B)));  // before the conversion: ensure() does not copy
-        { const auto t0 = clk::now();
-        // on the LEAD's content stream, the one the loop's gathers run on: ordered before them by the stream itself (on the chunk's
-        // own stream the conversion kernel was ordered by nothing but its brevity)
-        ACAV_TRY(ids_to_device32(mi, candidates[c], L[c], mi->stage, mi->A0, st));
-        t_ids += ms_since(t0); }
-        ACAV_TRY(mi->A1.ensure(sizeof(int) * (Lc + B)));
-        ACAV_TRY(mi->batch.ensure(sizeof(int) * 2 * (size_t)bcap * (size_t)(1 + mi->D)));
-        ACAV_TRY(mi->S.ensure(sizeof(long long) * (size_t)(itc * k + 1)));
-        ACAV_TRY(mi->G.ensure(sizeof(double) * (size_t)(itc * k + 1)));
-        if (ex.trace_pos) ACAV_TRY(mi->tr_pos.ensure(sizeof(int) * (size_t)(itc * k + 1)));
-        if (ex.trace_ids) ACAV_TRY(mi->tr_ids.ensure(sizeof(long long) * (size_t)(itc * B + 1)));
-        if (ex.trace_scores) ACAV_TRY(mi->tr_sc.ensure(sizeof(double) * (size_t)(itc * B + 1)));
-        if (ex.forced_pos) {
-            for (int64_t i = 0; i < itc * k; ++i)
-                ACAV_REQUIRE(ex.forced_pos[i] >= 0 && ex.forced_pos[i] < B, ACAV_EINVAL, "forced position out of range");
-            ACAV_TRY(mi->forced.ensure(sizeof(int) * (size_t)(itc * k + 1)));
-            ACAV_HIP_TRY(hipMemcpyAsync(mi->forced.p, ex.forced_pos, sizeof(int) * (size_t)(itc * k), hipMemcpyHostToDevice, st));
-        }
-        FyPlan &fp = plans[(size_t)c];
-        { const auto t0 = clk::now();
-        ACAV_TRY(fy_setup(mi, L[c], bcap, fp, st));
-        t_fy += ms_since(t0); }
-        ntmax = fp.NT > ntmax ? fp.NT : ntmax;
-        const size_t ps = fy_part_smem(fp.NT, fp.table.size(), false, pack), pss = fy_part_smem(fp.NT, fp.table.size(), true, pack);
-        part_smem = ps > part_smem ? ps : part_smem;
-        part_smem_staged = pss > part_smem_staged ? pss : part_smem_staged;
-        tile_smem = fp.tile_smem() > tile_smem ? fp.tile_smem() : tile_smem;
-        // hand the host MT19937 stream to the device: W lanes generate it superblock by superblock on their own stream
-        // (MtStream); nothing they do depends on what gets selected (L shrinks by a fixed amount per iteration)
-        unsigned mtbuf[625];
-        int idx = 0;
-        ACAV_TRY(acav_rng_get_state(rngs[c], mtbuf, &idx));
-        MtStream &ms = streams[(size_t)c];
-        // Chunks in lockstep: ALL their generators run on the lead handle's generator stream (round 5).  A generator launch is rare
-        // (a superblock of 82 M words lasts ~800 iterations of a 100k-clip chunk) and off the critical path, but ten generator
-        // streams are ten more queues for the runtime to service: with GPU_MAX_HW_QUEUES = 16 (which ten clusterings training
-        // side by side need, acav100m_amd/__init__.py) the lockstep loop ran at 7.4 us per chunk-iteration instead of 3.8;
-        // on one shared stream 3.66 at either setting.  ACAV_MI_SHARE_GEN=0: a stream per chunk again, =n: n streams (A/B).
-        const char *vsh = getenv("ACAV_MI_SHARE_GEN");
-        const int nshare = vsh ? atoi(vsh) : 1;
-        if (nshare > 0) ACAV_TRY(mi_ensure_streams(mis[c % nshare]));
-        else ACAV_TRY(mi_ensure_streams(mi));
-        ACAV_TRY(mi_ensure_gen_events(mi));
-        { const auto t0 = clk::now();
-        ACAV_TRY(ms.plan(mi, sf, mtbuf, idx, draws, L[c], (int64_t)FY_GROUP * L[c], nshare > 0 ? mis[c % nshare]->st_mt : nullptr));
-        t_mt += ms_since(t0); }
-        TileChunk &d = desc[(size_t)c];
-        d.ring = ms.ring + MtStream::PAD;
-        d.head = ms.head;
-        d.ring_words = ms.wraps ? MtStream::NSLOT * ms.S : ((long long)1 << 62);
-        d.table = mi->fy_table.as<unsigned short>(), d.ebound = mi->fy_bounds.as<int>();
-        d.bucket = mi->fy_bucket.as<int2>(), d.gcount = mi->fy_count.as<int>(), d.err = mi->fy_err.as<unsigned>();
-        for (int q = 0; q < FY_GROUP; ++q) d.src[q] = mi->fy_src[q].as<unsigned>(), d.g[q] = mi->fy_g[q].as<int>();
-        for (int q = 0; q < FY_NBUF; ++q) d.perm[q] = mi->fy_perm[q].as<unsigned>();
-        d.tailinv = mi->fy_tail.as<int>();
-        d.A[0] = mi->A0.as<int>(), d.A[1] = mi->A1.as<int>();
-        d.asg = mi->asg.as<int>(), d.pairs = mi->pairs.as<int>(), d.batch = mi->batch.as<int>();
-        d.Nc = mi->Nc.as<int>(), d.ac = mi->ac.as<int>(), d.bc = mi->bc.as<int>();
-        d.SN = mi->SN.as<double>(), d.Sa = mi->Sa.as<double>(), d.Sb = mi->Sb.as<double>();
-        d.phi = mi->phi.as<double>(), d.sc = mi->scalars.as<MiScalars>();
-        d.S = mi->S.as<long long>(), d.G = mi->G.as<double>();
-        d.forced = ex.forced_pos ? mi->forced.as<int>() : nullptr;
-        d.tr_pos = ex.trace_pos ? mi->tr_pos.as<int>() : nullptr;
-        d.tr_ids = ex.trace_ids ? mi->tr_ids.as<long long>() : nullptr;
-        d.tr_sc = ex.trace_scores ? mi->tr_sc.as<double>() : nullptr;
-        d.L0 = (int)L[c], d.iters = (int)itc, d.ntab = (int)fp.table.size(), d.gsh = fp.gsh, d.NT = fp.NT, d.capg = fp.capg;
-        d.ecap = fp.ecap_lds, d.wcap = fp.wcap, d.D = mi->D, d.C = mi->C, d.P = mi->P, d.bcap = bcap;
-        d.w = mi_weights(mi);
-        weighted = weighted || mi->weighted;
-    }
+    for (int c = 0; c < nchunks; ++c) ACAV_TRY(tiled_prepare_chunk(r, c, candidates[c], ns[c] ? start[c] : nullptr, ns[c], rngs[c]));
     ACAV_TRY(lead->chunk_desc.ensure(sizeof(TileChunk) * (size_t)nchunks));
-    ACAV_HIP_TRY(hipMemcpyAsync(lead->chunk_desc.p, desc.data(), sizeof(TileChunk) * (size_t)nchunks, hipMemcpyHostToDevice, st));
-    const double t_chunks = ms_since(t_setup0);
-    ACAV_HIP_TRY(hipStreamSynchronize(st));  // tables, counters, candidate lists, forced positions and descriptors are in place
-    const double t_setup = ms_since(t_setup0);
-    const auto tile_kernel = pack ? k_fy_tile_multi<true> : k_fy_tile_multi<false>;
-    ACAV_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(tile_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_smem));
-    // the staged form of k_fy_part wants 64 KB of LDS beside the tile table (which grows with L: 64 KB at 16 Mi candidates)
-    const bool part_staged = part_smem_staged <= 96 * 1024 && !getenv("ACAV_FY_PART_DIRECT");
-    const auto part_kernel = part_staged ? (pack ? k_fy_part_multi<true, true> : k_fy_part_multi<true, false>)
-                                         : (pack ? k_fy_part_multi<false, true> : k_fy_part_multi<false, false>);
-    if (part_staged) {
-        part_smem = part_smem_staged;
-        ACAV_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(part_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)part_smem));
-    }
-    const TileChunk *dcd = lead->chunk_desc.as<TileChunk>();
-    const int sel_f = sel_mode(B, pmax, k);  // one mode for every chunk of the launch: sized for the largest P and D
-    size_t sel_smem = 0;
-    ACAV_TRY(sel_smem_checked(B, pmax, dmax, k, sel_f, &sel_smem));
-    const auto gs_kernel = wide ? (weighted ? k_fy_gather_select_multi<true, true> : k_fy_gather_select_multi<false, true>)
-                                : (weighted ? k_fy_gather_select_multi<true, false> : k_fy_gather_select_multi<false, false>);
-    const auto resolve_kernel = wide ? k_fy_resolve_multi<true> : k_fy_resolve_multi<false>;
-    if (sel_smem > 48 * 1024)
-        ACAV_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(gs_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)sel_smem));
-    const auto t_loop0 = std::chrono::steady_clock::now();
-    long long groups_1d = 0, groups_3d = 0;  // launch form of the tile / resolve grids, per group (diagnostics: ACAV_MI_TIMING prints it)
-    long long gs_launches_sub = 0, gs_launches_all = 0;  // gather launches on a subset of the XCDs / on all eight (the same)
-    for (int64_t g0 = 0; g0 < iters_max; g0 += FY_GROUP) {
-        const int64_t g1 = g0 + FY_GROUP < iters_max ? g0 + FY_GROUP : iters_max;
-        const unsigned gz = (unsigned)(g1 - g0);
-        const int ge = (int)((g0 / FY_GROUP) % FY_DEPTH);  // event pair and buffer set of this group
-        const int64_t lt = lmax - g0 * dl;           // the longest list still in play bounds the grids
-        // ---- st_fy: the positions of the group's iterations (the gathers of the group FY_DEPTH back are done with this buffer set)
-        if (g0 >= FY_DEPTH * FY_GROUP) ACAV_HIP_TRY(hipStreamWaitEvent(sf, lead->ev_gather[ge], 0));
-        for (int c = 0; c < nchunks; ++c) {
-            int64_t nd = 0;
-            for (int64_t it = g0; it < g1 && it < iters[(size_t)c]; ++it) {
-                const int64_t Lc = L[c] - it * dl;
-                nd += Lc > 1 ? Lc - 1 : 0;
-            }
-            if (nd == 0) continue;
-            const unsigned *unused = nullptr;
-            ACAV_TRY(streams[(size_t)c].acquire(r0[(size_t)c], nd, &unused));
-            r0[(size_t)c] += nd;
-        }
-        hipLaunchKernelGGL(part_kernel, dim3((unsigned)((lt + FYA_CH - 1) / FYA_CH), (unsigned)nchunks, gz), dim3(FYA_THREADS), part_smem, sf, dcd,
-                           (int)g0, (int)dl);
-        for (int c = 0; c < nchunks; ++c)
-            if (g0 < iters[(size_t)c]) ACAV_TRY(streams[(size_t)c].release(r0[(size_t)c]));  // k_fy_part is the only reader of the draws
-        FyGrid gr_tile, gr_res;
-        const dim3 grid_tile = fy_launch_grid(xcd_affine, (unsigned)ntmax, (unsigned)nchunks, gz, FYT_THREADS, &gr_tile);
-        const dim3 grid_res = fy_launch_grid(xcd_affine, (unsigned)((lt + 255) / 256), (unsigned)nchunks, gz, 256, &gr_res);
-        ++(gr_tile.nx && gr_res.nx ? groups_1d : groups_3d);
-        hipLaunchKernelGGL(tile_kernel, grid_tile, dim3(FYT_THREADS), tile_smem, sf, dcd, (int)g0, (int)dl, gr_tile);
-        hipLaunchKernelGGL(resolve_kernel, grid_res, dim3(256), 0, sf, dcd, (int)g0, (int)dl, keep_unselected ? B - k : 0, gr_res);
-        ACAV_HIP_TRY(hipEventRecord(lead->ev_tile[ge], sf));
-        // ---- main stream: the group's gathers (each with the selection of the iteration before it), back to back
-        ACAV_HIP_TRY(hipStreamWaitEvent(st, lead->ev_tile[ge], 0));
-        for (int64_t it = g0; it < g1; ++it) {
-            const int64_t lit = lmax - it * dl, gather_blocks = (lit + 256 * GS_EPT - 1) / (256 * GS_EPT);
-            GsGrid gr_gs = {(unsigned)FY_XCDS, 0u};
-            if (nchunks == 1 && gs_xcds < FY_XCDS && lit >= gs_min_l)
-                gr_gs = {(unsigned)gs_xcds, gs_rot ? (unsigned)(gs_launches_sub * gs_xcds % FY_XCDS) : 0u};
-            ++(gr_gs.n_xcd < (unsigned)FY_XCDS ? gs_launches_sub : gs_launches_all);
-            const dim3 grid((unsigned)gs_grid_blocks(gather_blocks, gr_gs.n_xcd, gr_gs.rot), (unsigned)nchunks);
-            hipLaunchKernelGGL(gs_kernel, grid, dim3(256), sel_smem, st, dcd, (int)it, (int)dl, B, k, sel_f, keep_unselected, gr_gs);
-        }
-        ACAV_HIP_TRY(hipGetLastError());
-        ACAV_HIP_TRY(hipEventRecord(lead->ev_gather[ge], st));
-    }
-    if (iters_max > 0)  // the selection of the last iteration
-        hipLaunchKernelGGL(gs_kernel, dim3(1u, (unsigned)nchunks), dim3(256), sel_smem, st, dcd, (int)iters_max, (int)dl, B, k,
-                           sel_f, keep_unselected, GsGrid{(unsigned)FY_XCDS, 0u});
-    ACAV_HIP_TRY(hipGetLastError());
-    const auto t_loop1 = std::chrono::steady_clock::now();
-    ACAV_HIP_TRY(hipStreamSynchronize(sf));
-    if (timing) {
-        ACAV_HIP_TRY(hipStreamSynchronize(st));
-        const auto t_loop2 = std::chrono::steady_clock::now();
+    ACAV_HIP_TRY(hipMemcpyAsync(lead->chunk_desc.p, r.desc.data(), sizeof(TileChunk) * (size_t)nchunks, hipMemcpyHostToDevice, r.st));
+    const double t_chunks = t_form + ms_since(t_setup0);
+    ACAV_HIP_TRY(hipStreamSynchronize(r.st));  // tables, counters, candidate lists, forced positions and descriptors are in place
+    const double t_setup = t_form + ms_since(t_setup0);
+    TiledKernels kn;
+    ACAV_TRY(tiled_kernels(f, &kn));
+    const auto t_loop0 = clk::now();
+    ACAV_TRY(tiled_enqueue(r, kn));
+    const auto t_loop1 = clk::now();
+    ACAV_HIP_TRY(hipStreamSynchronize(r.sf));
+    if (sw.timing) {
+        ACAV_HIP_TRY(hipStreamSynchronize(r.st));
+        const auto t_loop2 = clk::now();
+        const double per = (double)(f.iters_max ? f.iters_max : 1);
         fprintf(stderr, "[acav] greedy loop: %d chunk(s), %lld iterations, host enqueue %.2f us/iteration, enqueue + drain %.2f "
                         "us/iteration (tiles %d, cap %d, lanes %d; tile / resolve grids: 1-D XCD-affine in %lld group(s), 3-D in %lld; "
                         "gather grid: %d XCD(s), rotation %d, subset form in %lld launch(es), all eight in %lld; streams replaced by the queue probe at create: %d)\n",
-                nchunks, (long long)iters_max,
-                std::chrono::duration<double, std::micro>(t_loop1 - t_loop0).count() / (double)(iters_max ? iters_max : 1),
-                std::chrono::duration<double, std::micro>(t_loop2 - t_loop0).count() / (double)(iters_max ? iters_max : 1),
-                plans[0].NT, plans[0].ecap, streams[0].W, groups_1d, groups_3d, gs_xcds, (int)gs_rot, gs_launches_sub, gs_launches_all,
-                mis[0]->queue_probe_replaced);
+                nchunks, (long long)f.iters_max, std::chrono::duration<double, std::micro>(t_loop1 - t_loop0).count() / per,
+                std::chrono::duration<double, std::micro>(t_loop2 - t_loop0).count() / per, f.tiling[0].NT, f.tiling[0].ecap,
+                r.streams[0].W, r.groups_1d, r.groups_3d, f.gs_xcds, (int)f.gs_rot, r.gs_launches_sub,
+                (long long)f.iters_max - r.gs_launches_sub, mis[0]->queue_probe_replaced);
     }
     const auto t_tail0 = clk::now();
-    for (int c = 0; c < nchunks; ++c) {
-        ACAV_TRY(read_back(mis[c], st, iters[(size_t)c], subset[c], B, k, S_out[c], GAIN_out[c], ex, n_selected ? n_selected + c : nullptr,
-                           n_iters ? n_iters + c : nullptr));
-    }
-    ACAV_HIP_TRY(hipStreamSynchronize(st));
-    for (int c = 0; c < nchunks; ++c) {  // every generator continues on the host where its chunk stopped drawing
-        ACAV_HIP_TRY(hipStreamSynchronize(streams[(size_t)c].smt ? streams[(size_t)c].smt : mis[c]->st_mt));
-        unsigned mtbuf[625];
-        int idx = 0;
-        ACAV_TRY(acav_rng_get_state(rngs[c], mtbuf, &idx));
-        ACAV_TRY(streams[(size_t)c].final_state(mtbuf, &idx));
-        ACAV_TRY(acav_rng_set_state(rngs[c], mtbuf, idx));
-        unsigned ferr = 0;
-        ACAV_HIP_TRY(hipMemcpy(&ferr, mis[c]->fy_err.p, sizeof(ferr), hipMemcpyDeviceToHost));
-        ACAV_REQUIRE(ferr == 0, ACAV_ESTATE, "tiled Fisher-Yates: a tile bucket of chunk %d overflowed (flags %u); re-run with "
-                                             "ACAV_FY_LEGACY=1", c, ferr);
-    }
-    if (timing)
+    ACAV_TRY(tiled_finish(r, subset, rngs, S_out, GAIN_out, n_selected, n_iters));
+    if (sw.timing)
         fprintf(stderr, "[acav]   set-up %.1f ms (per-chunk work %.1f: add_samples %.1f, ids %.1f, tables %.1f, generator plan %.1f; then the sync), "
-                        "read-back + generator states %.1f ms\n", t_setup, t_chunks, t_add, t_ids, t_fy, t_mt, ms_since(t_tail0));
+                        "read-back + generator states %.1f ms\n", t_setup, t_chunks, r.t_add, r.t_ids, r.t_fy, r.t_mt, ms_since(t_tail0));
     return ACAV_OK;
 }
 
@@ -3212,6 +3037,66 @@ ACAV_EXPORT int acav_gs_block_map(int64_t b, int n_xcd, int rot, int *role, int6
     return ACAV_OK;
 }
 
+// What a greedy call of this shape launches, without a device and under the call's own environment switches (greedy_pick_form,
+// greedy_group_grids, mt_pick_lanes: acav_mi_form.h).  The layouts of form / group / mt_out: include/acav_hip.h.
+ACAV_EXPORT int acav_mi_greedy_form(int nchunks, const int64_t *L, const int64_t *subset, int B, int k, int keep_unselected,
+                                    int64_t max_iters, int pmax, int dmax, int weighted, int64_t *form, int64_t g0,
+                                    int64_t gs_launches_before, int64_t *group, uint64_t *tiling_hash, const int64_t *mt_in,
+                                    int64_t *mt_out)
+{
+    ACAV_REQUIRE(L && subset && form && nchunks > 0 && (!mt_in == !mt_out), ACAV_EINVAL, "NULL argument");
+    ACAV_REQUIRE(B > 0 && B <= SEL_WIDEB && k > 0 && k <= B && pmax > 0 && dmax > 0 && (int64_t)B * pmax <= SEL_MAXBP, ACAV_EINVAL,
+                 "batch_size %d / selection_size %d / pairs %d / clusterings %d out of range", B, k, pmax, dmax);
+    for (int c = 0; c < nchunks; ++c) ACAV_REQUIRE(L[c] > 0 && subset[c] >= 0, ACAV_EINVAL, "chunk %d: bad sizes", c);
+    const GreedySwitches sw = greedy_switches();
+    const GreedyForm f = greedy_pick_form({nchunks, L, subset, B, k, keep_unselected != 0, max_iters, pmax, dmax, weighted != 0}, sw);
+    const bool tiled = f.path == GREEDY_TILED && !f.refusal;
+    const int64_t head[24] = {f.refusal ? 2 : f.path, f.refusal == GREEDY_OK ? ACAV_OK : f.refusal == GREEDY_SHORT_LIST ? ACAV_ERANGE : ACAV_EINVAL,
+                              f.refusal, f.refused_chunk, f.short_l, f.dl, f.wide, f.bcap, f.iters_max, f.lmax, f.sel_mode, (int64_t)f.sel_smem,
+                              f.pack, f.part_staged, (int64_t)f.part_smem, (int64_t)f.tile_smem, f.ntmax, f.xcd_affine, f.gs_xcds, f.gs_rot,
+                              f.gs_min_l, f.queue_probe, tiled ? f.tiling[0].NT : 0, tiled ? f.tiling[0].ecap : 0};
+    const int64_t consts[8] = {FY_GROUP, FY_DEPTH, FY_PACK_MAX, FY_TILED_MAX, SEL_MAXB, SEL_PHIBP, SEL_FASTBP, SEL_FASTKP};
+    // a refused form says why and nothing else; the legacy path has no tiled fields [12, 24)
+    for (int i = 0; i < 24; ++i) form[i] = i < 5 || (!f.refusal && (i < 12 || tiled)) ? head[i] : 0;
+    for (int i = 0; i < 8; ++i) form[24 + i] = consts[i];
+    for (int c = 0; c < nchunks; ++c)
+        form[32 + c] = f.refusal ? 0 : f.iters[(size_t)c], form[32 + nchunks + c] = f.refusal ? 0 : f.draws[(size_t)c];
+    if (group) {
+        ACAV_REQUIRE(tiled && g0 >= 0 && g0 % FY_GROUP == 0 && g0 < f.iters_max && gs_launches_before >= 0, ACAV_EINVAL,
+                     "no group of a tiled launch starts at iteration %lld", (long long)g0);
+        long long sub = gs_launches_before;
+        const GreedyGroup g = greedy_group_grids(f, g0, &sub);
+        const int64_t v[20] = {g.gz, g.ge, g.part.x, g.part.y, g.part.z, g.tile.x, g.tile.y, g.tile.z, g.gr_tile.nx, g.gr_tile.ny, g.gr_tile.gz,
+                               g.resolve.x, g.resolve.y, g.resolve.z, g.gr_res.nx, g.gr_res.ny, g.gr_res.gz, g.one_d, sub, 0};
+        for (int i = 0; i < 20; ++i) group[i] = v[i];
+        for (unsigned q = 0; q < (unsigned)FY_GROUP; ++q) {
+            const int64_t w[4] = {g.gather[q].x, g.gather[q].y, g.gr_gs[q].n_xcd, g.gr_gs[q].rot};
+            for (int i = 0; i < 4; ++i) group[20 + 4 * q + i] = q < g.gz ? w[i] : 0;
+        }
+    }
+    if (tiling_hash) {  // FNV-1a over every chunk's tile table (16-bit entries) and tile bounds (32-bit), low byte first
+        uint64_t h = 0xcbf29ce484222325ull;
+        auto mix = [&h](uint64_t v, int bytes) {
+            for (int i = 0; i < bytes; ++i) h = (h ^ (v >> (8 * i) & 0xff)) * 0x100000001b3ull;
+        };
+        for (const FyPlan &fp : f.tiling) {
+            for (unsigned short t : fp.table) mix(t, 2);
+            for (int e : fp.ebound) mix((uint32_t)e, 4);
+        }
+        *tiling_hash = tiled ? h : 0;
+    }
+    if (mt_in) {
+        const int64_t total = mt_in[0], idx = mt_in[1], span = mt_in[2], blk = mt_in[3], W = mt_in[4];
+        ACAV_REQUIRE(total >= 0 && idx >= 0 && idx <= 624 && span >= 0 && span < ((int64_t)1 << 40), ACAV_EINVAL, "bad generator shape");
+        ACAV_REQUIRE(blk == 0 ? W == 0 : blk >= 624 && blk % 624 == 0 && W >= 1 && W <= 32 && (W & (W - 1)) == 0, ACAV_EINVAL,
+                     "blk: a multiple of 624 with W a power of two up to 32, or neither");
+        const MtLanes m = mt_pick_lanes(total, (int)idx, span, blk, (int)W);
+        const int64_t v[8] = {m.head, m.blk, m.W, m.logW, m.nblocks, m.S, m.nsuper, m.wraps};
+        for (int i = 0; i < 8; ++i) mt_out[i] = v[i];
+    }
+    return ACAV_OK;
+}
+
 ACAV_EXPORT int acav_mi_run_greedy_multi(acav_mi **mis, int nchunks, const int64_t *const *candidates, const int64_t *L,
                                          const int64_t *const *start, const int *ns, const int64_t *subset, int B, int k,
                                          int keep_unselected, acav_rng **rngs, int64_t *const *S_out,
@@ -3226,9 +3111,6 @@ ACAV_EXPORT int acav_mi_run_greedy_multi(acav_mi **mis, int nchunks, const int64
     for (int c = 0; c < nchunks; ++c)
         if (mis[c]) mis[c]->pst_valid = false;  // the batch greedy changes the tables without the pair sums
     ACAV_HIP_TRY(hipSetDevice(lead->ctx.device));
-    // the tiled evaluation, chunks in lockstep, unless a list is too long for it (or ACAV_FY_LEGACY=1)
-    const char *legacy = getenv("ACAV_FY_LEGACY");
-    bool tiled = !(legacy && legacy[0] == '1');
     for (int c = 0; c < nchunks; ++c) {
         acav_mi *mi = mis[c];
         ACAV_TRY(check_chunk_args(c, mi, candidates[c], L[c], start ? start[c] : nullptr, ns[c], subset[c], rngs[c], S_out[c], GAIN_out[c]));
@@ -3237,25 +3119,23 @@ ACAV_EXPORT int acav_mi_run_greedy_multi(acav_mi **mis, int nchunks, const int64
                      SEL_MAXBP);
         for (int e = 0; e < c; ++e)
             ACAV_REQUIRE(mis[e] != mi && rngs[e] != rngs[c], ACAV_EINVAL, "chunks must not share a handle or a generator");
-        tiled = tiled && L[c] <= FY_TILED_MAX;
     }
-    if (tiled)
-        return run_greedy_tiled(mis, nchunks, candidates, L, start, ns, subset, B, k, keep_unselected, rngs, S_out, GAIN_out,
-                                n_selected, n_iters, TiledExtras());
+    // the tiled evaluation, chunks in lockstep, unless a list is too long for it (or ACAV_FY_LEGACY=1): the form says.  Every chunk
+    // is planned before the first one starts: a chunk whose candidates run out leaves no earlier chunk selected.
+    const auto t_form0 = clk::now();
+    const GreedySwitches sw = greedy_switches();
+    const GreedyForm f = greedy_form(mis, nchunks, L, subset, B, k, keep_unselected, -1, sw);
+    ACAV_TRY(greedy_refuse(f, sw, true));
+    if (f.path == GREEDY_TILED)
+        return run_greedy_tiled(mis, f, sw, candidates, L, start, ns, subset, rngs, S_out, GAIN_out, n_selected, n_iters, TiledExtras(),
+                                ms_since(t_form0));
     // Otherwise the chunks run one after another, each as a single-chunk call would run it (run_greedy_legacy): lockstep is there
-    // to share launch latency among short lists, and the legacy kernels are for long ones.  Every chunk is planned before the
-    // first one starts: a chunk whose candidates run out leaves no earlier chunk selected.
-    const int64_t dl = B - (keep_unselected ? B - k : 0);
-    for (int c = 0; c < nchunks; ++c) {
-        const GreedyPlan gp = greedy_plan(L[c], subset[c], B, k, dl, -1);
-        ACAV_REQUIRE(gp.short_l < 0, ACAV_ERANGE, "chunk %d: %lld candidates left < batch_size %d (batch.py:143-150)", c,
-                     (long long)gp.short_l, B);
-    }
+    // to share launch latency among short lists, and the legacy kernels are for long ones.
     for (int c = 0; c < nchunks; ++c) {
         ACAV_HIP_TRY(hipStreamSynchronize(mis[c]->ctx.stream));  // whatever the handle was doing on its own stream is over
         ACAV_TRY(run_greedy_legacy(mis[c], candidates[c], L[c], start ? start[c] : nullptr, ns[c], subset[c], B, k, keep_unselected,
-                                   rngs[c], S_out[c], GAIN_out[c], n_selected ? n_selected + c : nullptr,
-                                   n_iters ? n_iters + c : nullptr, TiledExtras()));
+                                   f.iters[(size_t)c], f.draws[(size_t)c], rngs[c], S_out[c], GAIN_out[c],
+                                   n_selected ? n_selected + c : nullptr, n_iters ? n_iters + c : nullptr, TiledExtras()));
     }
     return ACAV_OK;
 }
@@ -3930,29 +3810,26 @@ ACAV_EXPORT int acav_mi_run_greedy(acav_mi *mi, const int64_t *candidates, int64
     ex.trace_ids = trace_ids, ex.trace_scores = trace_scores, ex.trace_pos = trace_pos, ex.forced_pos = forced_pos;
     ex.max_iters = max_iters;
     // the permutation of every iteration: tiled evaluation (all atomics in LDS; run_greedy_tiled) unless the list is too long
-    // for its tile table, or ACAV_FY_LEGACY=1 asks for the global-atomic kernels (run_greedy_legacy)
-    const char *legacy = getenv("ACAV_FY_LEGACY");
-    if (L <= FY_TILED_MAX && !(legacy && legacy[0] == '1'))
-        return run_greedy_tiled(&mi, 1, &candidates, &L, &start, &ns, &subset, B, k, keep_unselected, &rng, &S_out, &GAIN_out,
-                                n_selected, n_iters, ex);
-    return run_greedy_legacy(mi, candidates, L, start, ns, subset, B, k, keep_unselected, rng, S_out, GAIN_out, n_selected, n_iters, ex);
+    // for its tile table, or ACAV_FY_LEGACY=1 asks for the global-atomic kernels (run_greedy_legacy): the form says
+    const auto t_form0 = clk::now();
+    const GreedySwitches sw = greedy_switches();
+    const GreedyForm f = greedy_form(&mi, 1, &L, &subset, B, k, keep_unselected, max_iters, sw);
+    ACAV_TRY(greedy_refuse(f, sw, false));
+    if (f.path == GREEDY_TILED)
+        return run_greedy_tiled(&mi, f, sw, &candidates, &L, &start, &ns, &subset, &rng, &S_out, &GAIN_out, n_selected, n_iters, ex,
+                                ms_since(t_form0));
+    return run_greedy_legacy(mi, candidates, L, start, ns, subset, B, k, keep_unselected, f.iters[0], f.draws[0], rng, S_out, GAIN_out,
+                             n_selected, n_iters, ex);
 }
 
 static int run_greedy_legacy(acav_mi *mi, const int64_t *candidates, int64_t L, const int64_t *start, int ns, int64_t subset,
-                             int B, int k, int keep_unselected, acav_rng *rng, int64_t *S_out, double *GAIN_out,
-                             int64_t *n_selected, int64_t *n_iters, const TiledExtras &ex)
+                             int B, int k, int keep_unselected, int64_t iters, int64_t draws, acav_rng *rng, int64_t *S_out,
+                             double *GAIN_out, int64_t *n_selected, int64_t *n_iters, const TiledExtras &ex)
 {
     hipStream_t st = mi->ctx.stream;
     const int64_t dl = B - (keep_unselected ? B - k : 0);  // candidates consumed per iteration
     if (ns) ACAV_TRY(acav_mi_add_samples(mi, start, ns));  // batch.py:215
-    const GreedyPlan gp = greedy_plan(L, subset, B, k, dl, ex.max_iters);
-    ACAV_REQUIRE(gp.short_l < 0, ACAV_ERANGE,
-                 "%lld candidates left < batch_size %d: the reference's topk(k=floor(B/k*B')) raises here "
-                 "(batch.py:143-150)", (long long)gp.short_l, B);
-    const int64_t iters = gp.iters;
-    ACAV_TRY(mi->A0.ensure(sizeof(int) * (size_t)(L + B)));  // before the conversion: ensure() does not copy
-    ACAV_TRY(ids_to_device32(mi, candidates, L, mi->stage, mi->A0));
-    ACAV_TRY(mi->A1.ensure(sizeof(int) * (size_t)(L + B)));
+    ACAV_TRY(greedy_chunk_buffers(mi, candidates, L, B, k, iters, (size_t)(B > SEL_MAXB ? B : SEL_MAXB), ex, st));
     ACAV_TRY(mi->h.ensure(sizeof(int) * (size_t)L));
     ACAV_TRY(mi->head.ensure(sizeof(int) * (size_t)L));
     ACAV_TRY(mi->next.ensure(sizeof(int) * (size_t)L));
@@ -3961,18 +3838,6 @@ static int run_greedy_legacy(acav_mi *mi, const int64_t *candidates, int64_t L, 
     ACAV_TRY(mi->g2.ensure(sizeof(int) * (size_t)L));
     ACAV_HIP_TRY(hipMemsetAsync(mi->head.p, 0xFF, sizeof(int) * (size_t)L, st));
     ACAV_HIP_TRY(hipMemsetAsync(mi->g.p, 0xFF, sizeof(int) * (size_t)L, st));
-    ACAV_TRY(mi->batch.ensure(sizeof(int) * (size_t)(B > SEL_MAXB ? B : SEL_MAXB)));
-    ACAV_TRY(mi->S.ensure(sizeof(long long) * (size_t)(iters * k + 1)));
-    ACAV_TRY(mi->G.ensure(sizeof(double) * (size_t)(iters * k + 1)));
-    if (ex.trace_pos) ACAV_TRY(mi->tr_pos.ensure(sizeof(int) * (size_t)(iters * k + 1)));
-    if (ex.trace_ids) ACAV_TRY(mi->tr_ids.ensure(sizeof(long long) * (size_t)(iters * B + 1)));
-    if (ex.trace_scores) ACAV_TRY(mi->tr_sc.ensure(sizeof(double) * (size_t)(iters * B + 1)));
-    if (ex.forced_pos) {
-        for (int64_t i = 0; i < iters * k; ++i)
-            ACAV_REQUIRE(ex.forced_pos[i] >= 0 && ex.forced_pos[i] < B, ACAV_EINVAL, "forced position out of range");
-        ACAV_TRY(mi->forced.ensure(sizeof(int) * (size_t)(iters * k + 1)));
-        ACAV_HIP_TRY(hipMemcpyAsync(mi->forced.p, ex.forced_pos, sizeof(int) * (size_t)(iters * k), hipMemcpyHostToDevice, st));
-    }
     // hand the host MT19937 stream to the device: W lanes generate it superblock by superblock on their own stream
     // (MtStream); nothing they do depends on what gets selected (L shrinks by a fixed amount per iteration)
     unsigned mtbuf[625];
@@ -3980,7 +3845,7 @@ static int run_greedy_legacy(acav_mi *mi, const int64_t *candidates, int64_t L, 
     ACAV_TRY(acav_rng_get_state(rng, mtbuf, &idx));
     MtStream ms;
     ACAV_TRY(mi_ensure_streams(mi));  // the generator runs on the handle's own generator stream, as in the tiled loop (not the null stream)
-    ACAV_TRY(ms.plan(mi, st, mtbuf, idx, gp.draws, L, L));
+    ACAV_TRY(ms.plan(mi, st, mtbuf, idx, draws, L, L));
 
     int *Acur = mi->A0.as<int>(), *Anew = mi->A1.as<int>();
     int64_t r0 = 0;  // first draw of this iteration, counted from the first draw of the run

@@ -8,7 +8,7 @@
 static int mt_bench()
 {
     const int W = 32, reps = 20;
-    const long long blk = MtStream::BLK_DEFAULT;
+    const long long blk = MT_BLK_DEFAULT;
     std::mt19937 rng(5);
     std::vector<unsigned> hs((size_t)625 * W);
     for (int w = 0; w < W; ++w) {
@@ -52,8 +52,7 @@ int main(int argc, char **argv)
     // still only descends (every g[q] < q), so the walks end.  FYB_SLOTS=16 is the unaliased layout at dl = 0 (the A/B baseline).
     const int slots = getenv("FYB_SLOTS") ? atoi(getenv("FYB_SLOTS")) : 0;
     const int G = FY_GROUP, B = 20, k = 4, dl = slots > 0 ? 0 : 4, reps = 40;
-    FyPlan fp;
-    fp.build(L);
+    const FyPlan fp = fy_pick_tiling(L, greedy_switches());  // the product's tiling, ACAV_FY_CAP / _TILES_MIN / _ECAP included
     printf("L %d  tiles %d cap %d gsh %d capg %d  tile smem %zu\n", L, fp.NT, fp.ecap, fp.gsh, fp.capg, fp.tile_smem());
     std::mt19937 rng(3);
     const size_t ndraw = (size_t)2 * G * L + 1024;
@@ -110,8 +109,8 @@ int main(int argc, char **argv)
     // the product's grids of the tile and resolve kernels (fy_launch_grid) under the product's switch: ACAV_FY_XCD_AFFINE=0 = 3-D
     const bool affine = !(getenv("ACAV_FY_XCD_AFFINE") && getenv("ACAV_FY_XCD_AFFINE")[0] == '0');
     FyGrid gr_tile, gr_res;
-    const dim3 grid_tile = fy_launch_grid(affine, (unsigned)fp.NT, 1u, (unsigned)G, FYT_THREADS, &gr_tile);
-    const dim3 grid_res = fy_launch_grid(affine, (unsigned)((L + 255) / 256), 1u, (unsigned)G, 256, &gr_res);
+    const dim3 grid_tile = to_dim3(fy_launch_grid(affine, (unsigned)fp.NT, 1u, (unsigned)G, FYT_THREADS, &gr_tile));
+    const dim3 grid_res = to_dim3(fy_launch_grid(affine, (unsigned)((L + 255) / 256), 1u, (unsigned)G, 256, &gr_res));
     printf("tile / resolve grids: %s (%u / %u workgroups in x)\n", gr_tile.nx ? "1-D, one XCD per iteration" : "3-D", grid_tile.x, grid_res.x);
     auto tile = [&]() { hipLaunchKernelGGL(tile_k, grid_tile, dim3(FYT_THREADS), fp.tile_smem(), 0, dcd, 0, dl, gr_tile); };
     auto resolve = [&]() { hipLaunchKernelGGL(k_fy_resolve_multi<false>, grid_res, dim3(256), 0, 0, dcd, 0, dl, B - k, gr_res); };
