@@ -28,6 +28,10 @@ device, like the run itself (frontend.py: FrontEnd): the report and the rows_pat
 A cache that holds `pca_components` (a `cluster --clustering.pca_dim=P` run) has its rows projected through the same helper,
 after the division: the view is judged in projected space and its report carries "pca_dim" and
 "pca_explained_variance_ratio" (the kept share of the total variance).  Epochs that disagree on a view's projection are refused.
+A cache that holds `normalize` (a `cluster --clustering.normalize=True` or `--clustering.spherical=True` run) has its rows divided
+by their L2 norms last, through the same helper: the view's report carries "normalized": true, and `silhouette_sampled` is then a
+silhouette of chord distances (||x - y||^2 = 2 - 2 cos for unit rows).  A spherical state (unit centres too) also gets
+"mean_cosine" = 1 - inertia / 2, the mean cosine between a row and its centre, exact for unit rows and unit centres.
 evaluate.rows_path: one <shard>.quality.npz per shard with `filename`, `epochs` and, per view, "<model_key>/<layer>" ->
 float64 [epochs, rows, 2] = (a2, b2) -- an outlier or low-margin filter downstream.  One process, one GPU.
 evaluate.silhouette_sample=M (default: off) adds the exact silhouette on a seeded sample (silhouette.py, acav_rows_silhouette):
@@ -237,6 +241,10 @@ def evaluate(args):
             tv = float(fit['total_variance'])
             rep['pca_dim'] = int(fit['components'].shape[0])
             rep['pca_explained_variance_ratio'] = float(fit['explained_variance'].sum() / tv) if tv > 0 else float('nan')
+        if fronts[v].normalize:  # every figure of this view is about directions
+            rep['normalized'] = True
+        if km.spherical:  # unit rows and unit centres: ||x - c||^2 = 2 - 2 cos(x, c)
+            rep['mean_cosine'] = 1.0 - rep['inertia'] / 2.0
         if sil_m is not None:  # the sample's labels in this state, then every pairwise distance of it
             K = km.centers.shape[0]
             labels, _ = km.calc_best(sample[v], need_mean=False)

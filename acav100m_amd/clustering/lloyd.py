@@ -16,7 +16,13 @@ Definition of one iteration on rows x [N, d] (fp32, after the whiten / PCA front
            (split_empty, after faiss's split_clusters): the currently largest cluster j (lowest index on ties) is split, c_i = c_j
            with the even columns of c_i times 1 + 1/1024 and of c_j times 1 - 1/1024, the odd columns the other way round, and i
            takes floor(count_j / 2) of j's count.
-The assignment and the sums are GPU sweeps (there is no CPU path); tests/_lloyd_np.py restates the iteration in numpy bit for bit.
+  spherical (clustering.spherical; faiss's Kmeans(spherical=True)): the rows are L2-normalised (clustering/normalize.py), and after
+           the steps above the [K, d] centre table is normalised row by row with the same kernel (acav_rows_normalize) -- on the
+           device, in the one place finish_iteration.  A cluster whose fp32 mean is exactly the zero vector (its rows cancel) counts
+           as empty: its count is set to 0 before the empty-cluster rule, which then splits the largest cluster into it.  With unit
+           rows and unit centres the Euclidean argmin of the assign sweep is the cosine argmax: the sweep is untouched.
+The assignment and the sums are GPU sweeps (there is no CPU path); tests/_lloyd_np.py restates the iteration in numpy bit for bit
+(tests/_rownorm_np.py: the spherical one).
 Several GPUs with the rows partitioned (clustering.multi_gpu=rows): the tables are integers, so their all-reduced sum is the
 one-GPU run's table whoever added what -- parallel/lloyd_rows.py and run_clustering._train_clusters_lloyd."""
 import ctypes as C
@@ -151,15 +157,18 @@ def split_empty(centers, counts):
     return splits
 
 
-def centers_from_sums(sums, counts, s):
+def centers_from_sums(sums, counts, s, zero_mean_is_empty=False):
     """(sums int64 [K, d], counts int64 [K], s) -> (centers fp32 [K, d], sizes int64 [K], splits): the mean of every cluster
-    rounded to fp32, then the empty-cluster rule"""
+    rounded to fp32, then the empty-cluster rule.  zero_mean_is_empty (a spherical iteration): a cluster whose fp32 mean is the
+    zero vector has no direction; its count is set to 0 first, so the rule treats it as empty."""
     sums, counts = np.asarray(sums, np.int64), np.array(counts, np.int64)
     if int(counts.sum()) == 0:
         raise ValueError("no row was accumulated: there is no centre to compute")
     with np.errstate(invalid='ignore', divide='ignore'):
         centers = np.float32(sums.astype(np.float64) * 2.0 ** -int(s) / counts[:, None].astype(np.float64))
     centers[counts == 0] = 0  # (0 / 0 above; split_empty overwrites every one of them)
+    if zero_mean_is_empty:
+        counts[~centers.any(axis=1)] = 0
     splits = split_empty(centers, counts)
     return centers, counts, splits
 
@@ -200,13 +209,22 @@ def lloyd_update(km, x, s, sums=None, counts=None):
     return labels, sums, counts
 
 
-def finish_iteration(km, sums, counts, s):
+def finish_iteration(km, sums, counts, s, spherical=False):
     """centres <- mean of their rows (+ the empty-cluster rule), counts <- the cluster sizes, count += the rows of the
     iteration -> number of splits.  Tables on the device (torch tensors) take acav_lloyd_centers: the centres go from device
     to device into km's handle and no table crosses the bus; when it reports an empty cluster, the iteration takes the host path
-    below (split_empty is sequential and rare).  Host tables (numpy) take the host path."""
+    below (split_empty is sequential and rare).  Host tables (numpy) take the host path.
+    spherical: the centre table is then normalised row by row on the device (normalize.normalize_: acav_rows_normalize), whichever
+    path made it.  A zero row it meets on the device path is a cluster whose mean is the zero vector: the table is dropped and the
+    iteration takes the host path, where such a cluster's count is set to 0 in front of the empty-cluster rule."""
+    if spherical:
+        from .normalize import normalize_
+        if km._h is None:
+            raise _lib.AcavError("a spherical iteration normalises its centres on the GPU: call KMeans.to('cuda') first")
     if hasattr(sums, "data_ptr") and sums.is_cuda and km._h is not None:
         centers, sizes, empty = centers_on_device(sums, counts, s)
+        if empty == 0 and spherical:
+            empty = normalize_(centers)[1]
         if empty == 0:
             n = int(counts.sum())
             _lib.check(_lib._lib.acav_kmeans_set_state(km._h, _lib.ptr(centers), _lib.ptr(sizes), km.count + n, km.fallback))
@@ -214,8 +232,16 @@ def finish_iteration(km, sums, counts, s):
     sums_h = sums.cpu().numpy() if hasattr(sums, "cpu") else sums
     counts_h = counts.cpu().numpy() if hasattr(counts, "cpu") else counts
     n = int(counts_h.sum())
-    centers, sizes, splits = centers_from_sums(sums_h, counts_h, s)
-    km.load_state_arrays(centers, sizes.astype(np.float32), km.count + n, km.fallback)
+    if not spherical:
+        centers, sizes, splits = centers_from_sums(sums_h, counts_h, s)
+        km.load_state_arrays(centers, sizes.astype(np.float32), km.count + n, km.fallback)
+        return splits
+    import torch
+    centers, sizes, splits = centers_from_sums(sums_h, counts_h, s, zero_mean_is_empty=True)
+    table = torch.from_numpy(centers).to("cuda:{}".format(km._device))
+    if normalize_(table)[1]:
+        raise ValueError("a centre is the zero vector after the empty-cluster rule: every cluster's rows cancel")
+    km.load_state_arrays(table.cpu().numpy(), sizes.astype(np.float32), km.count + n, km.fallback)
     return splits
 
 
@@ -225,19 +251,26 @@ class FitReport(list):
     potential = None
 
 
-def fit(x, k, iters, generator=None, device="cuda", init='random', trials=1, sample=None):
+def fit(x, k, iters, generator=None, device="cuda", init='random', trials=1, sample=None, normalize=False, spherical=False):
     """Lloyd k-means of x [n, d] (numpy or a torch tensor) in one resident piece -> (KMeans in its lloyd state, labels of the last
     iteration's assignment, report: per iteration (changed labels, splits)).  Initial centres: the rows generator.randperm(n)[:k]
     (init='random'), or (init='kmeans++', clustering/kmeanspp.py) k-means++ seeds with `trials` trials per pick on the sample
     made of the first min(n, sample or 256 k) entries of the same permutation, in ascending order -- the uniforms are the
     generator's draws after the permutation, and report.potential holds the seeding's potentials, int64 [k].
-    Stops early when an iteration changes no label."""
+    Stops early when an iteration changes no label.
+    normalize: the rows are L2-normalised first (a copy: x stays what it is); spherical: implies it, and every iteration
+    renormalises the centres (finish_iteration) -- the state then carries 'spherical'."""
     import torch
     from . import kmeanspp
     if init not in kmeanspp.INITS:
         raise ValueError("init must be 'random' or 'kmeans++', not {!r}".format(init))
     dev = x.device if hasattr(x, "is_cuda") and x.is_cuda else torch.device("cuda:{}".format(_device_index(device)))
     t = (x.detach() if hasattr(x, "data_ptr") else torch.from_numpy(np.ascontiguousarray(x, np.float32))).to(dev, torch.float32).contiguous()
+    if normalize or spherical:
+        from .normalize import normalize_
+        if hasattr(x, "data_ptr") and t.data_ptr() == x.data_ptr():
+            t = t.clone()
+        normalize_(t)
     n, d = t.shape
     if k > n:
         raise ValueError("{} centres from {} rows: K > N".format(k, n))
@@ -251,7 +284,7 @@ def fit(x, k, iters, generator=None, device="cuda", init='random', trials=1, sam
         picked, potential = kmeanspp.seed(t[torch.from_numpy(rows).to(dev)], k, trials, generator=gen)
         perm = rows[picked]
     km = KMeans(None, d, k, generator=generator)
-    km.to_lloyd(t[torch.from_numpy(perm).to(dev)].cpu().numpy())
+    km.to_lloyd(t[torch.from_numpy(perm).to(dev)].cpu().numpy(), spherical=spherical)
     km.to(dev)
     s = fixed_point_shift(rows_absmax(t), n)
     report, prev = FitReport(), None
@@ -259,7 +292,7 @@ def fit(x, k, iters, generator=None, device="cuda", init='random', trials=1, sam
     for _it in range(int(iters)):
         labels, sums, counts = lloyd_update(km, t, s)
         changed = n if prev is None else int((labels != prev).sum())
-        report.append((changed, finish_iteration(km, sums, counts, s)))
+        report.append((changed, finish_iteration(km, sums, counts, s, spherical=spherical)))
         prev = labels
         if changed == 0:
             break

@@ -112,7 +112,8 @@ class _RowGroups:
         return t
 
     def add_front_ends(self, stage):
-        """{view: FrontEnd} holding the next stage (the std, then the projection, or both at once) for every later upload.  Rows
+        """{view: FrontEnd} holding the next stage (the std, then the projection, then the row normalisation, or several at once)
+        for every later upload.  Rows
         that are already resident on the device -- uploaded by the pre-pass that computed the stage, with the earlier stage
         applied -- go through this stage here, exactly once and one view at a time: the peak is one extra view."""
         for v, f in stage.items():
@@ -122,6 +123,8 @@ class _RowGroups:
             for v in list(on_dev):
                 if v in stage:
                     on_dev[v] = stage[v].apply(on_dev[v])
+                    self.fronts[v].zero_rows += stage[v].zero_rows  # (what a row normalisation met is the view's tally)
+                    self.fronts[v].rows_normalized += stage[v].rows_normalized
 
     @property
     def streamed(self):

@@ -17,7 +17,7 @@ Same observable behaviour as the reference:
 clustering.algorithm=lloyd (ours; clustering/lloyd.py) trains with batch k-means instead: train_clusters branches once, to
 _train_clusters_lloyd; the caches, cached_epoch, the assign sweep and `evaluate` are the ones above.
 This module is the stage and its three training loops.  Beside it: cache.py (the cache_epoch files: locate, read, save, find),
-frontend.py (FrontEnd: a view's whiten / PCA stages, their cache keys, checks and application), row_groups.py (_RowGroups, the
+frontend.py (FrontEnd: a view's whiten / PCA / row-normalisation stages, their cache keys, checks and application), row_groups.py (_RowGroups, the
 device budget, the loader settings, the shard probe) and options.py (multi_gpu_mode and the refusals of check_options).
 """
 from collections import OrderedDict
@@ -32,7 +32,7 @@ from .cache import path as _cache_path, read as _read_cache  # noqa: F401  (the 
 from .frontend import PCA_KEYS, FrontEnd, pca_of as _pca_of  # noqa: F401
 from .kmeanspp import check_init
 from .lloyd import check_algorithm
-from .options import check_pca, check_whiten, multi_gpu_mode
+from .options import check_normalize, check_pca, check_whiten, multi_gpu_mode
 from . import row_groups
 from .row_groups import current_device as _device, loader_settings, open_row_groups, probe_shards  # noqa: F401
 from .sgd_clustering import KMeans
@@ -47,6 +47,7 @@ def check_options(args, world_size):
     """the refusals that need no device and no file, before anything is created or read"""
     check_whiten(args, world_size)
     check_pca(args, world_size)
+    check_normalize(args, world_size)
     check_algorithm(args, world_size, merges=('rows',))  # (_train_clusters_lloyd all-reduces the tables in that mode)
     check_init(args)
 
@@ -120,6 +121,22 @@ def check_cached_algorithm(args, cached=None):
         if have != want:
             raise ValueError("clustering.resume_training with clustering.algorithm={}, but view {} of the clustering cache {} was "
                              "trained by {}: a run continues with the algorithm it started with".format(want, '/'.join(key[1:]), path, have))
+        if args.clustering.spherical and not dt.get('spherical'):
+            raise ValueError("clustering.resume_training with clustering.spherical=True, but view {} of the clustering cache {} is "
+                             "not a spherical state: its centres are plain cluster means, and a run continues what it started "
+                             "as".format('/'.join(key[1:]), path))
+
+
+def cached_normalization(args, cached=None, normalize=False):
+    """(cache file, {(model_key, layer)} of the views whose rows the cache says are L2-normalised), like cached_whitening: the
+    cache is authoritative.  normalize (the run's switch, clustering.spherical included) against a cache without the key is the
+    ValueError of a cached run that names the file."""
+    path, saved = _usable(args, cached)
+    found = {key[1:] for key, dt in saved.items() if dt.get('normalize')}
+    if normalize and path is not None and not found:
+        raise ValueError("clustering.normalize=True (or clustering.spherical=True), but the clustering cache {} holds no 'normalize' "
+                         "key: its centres were trained on rows that were not normalised".format(path))
+    return path, found
 
 
 def cached_whitening(args, cached=None):
@@ -362,7 +379,8 @@ def _local_shard_counts(groups):
 def _train_clusters_lloyd(args, cl, groups, pre, iters, resumed, shard_stems=(), force_partitioned=False):
     """clustering.algorithm=lloyd: `iters` iterations of batch k-means per view (clustering/lloyd.py), each one pass over the row
     groups with two sweeps per view -- the assign sweep and acav_lloyd_accumulate into int64 tables on the device -- and the centre
-    update on the device too (acav_lloyd_centers; on the host in an iteration that has an empty cluster to split).  Before the first one, one read-once pass takes every view's largest magnitude (the scale of the fixed
+    update on the device too (acav_lloyd_centers; on the host in an iteration that has an empty cluster to split; a spherical
+    run -- clustering.spherical, or a resumed state that says so -- then renormalises the centre table, lloyd.finish_iteration).  Before the first one, one read-once pass takes every view's largest magnitude (the scale of the fixed
     point) and, for a fresh run, the initial centres: the rows generator.randperm(N)[:K], drawn view by view, read as the
     front-ends deliver them -- or, with clustering.init=kmeans++, k-means++ seeds drawn from a sample of the rows that the same
     pass gathers (clustering/kmeanspp.py).  The tables are integer sums, so resident and streamed rows give the same bytes.
@@ -492,7 +510,7 @@ def _train_clusters_lloyd(args, cl, groups, pre, iters, resumed, shard_stems=(),
         except ValueError as exc:
             raise ValueError("view {}: {}".format('/'.join(v[1:]), exc))
         if not resumed:
-            km.to_lloyd(init[v])
+            km.to_lloyd(init[v], spherical=bool(args.clustering.spherical))
         print("lloyd {}: {} rows, {} centres, largest magnitude {:.6g}, fixed point 2^{}".format(
             '/'.join(v[1:]), n_total, K, absmax[v], shift[v]))
     prev = {v: {} for v in cl}  # {view: {row group: the labels of the previous iteration}}
@@ -521,7 +539,7 @@ def _train_clusters_lloyd(args, cl, groups, pre, iters, resumed, shard_stems=(),
             for v, c in zip(live, lloyd_rows.allreduce_sum([changed[v] for v in live])):
                 changed[v] = c
         for v in live:
-            splits = lloyd.finish_iteration(cl[v], tables[v][0], tables[v][1], shift[v])
+            splits = lloyd.finish_iteration(cl[v], tables[v][0], tables[v][1], shift[v], spherical=cl[v].spherical)
             print("lloyd {}: iteration {}: {} labels changed, {} empty clusters split".format('/'.join(v[1:]), epoch, changed[v], splits))
             if changed[v] == 0:
                 done[v] = True
@@ -648,6 +666,8 @@ def run_clustering(args):
     cache_file, cached_std = cached_whitening(args, cached)
     _, cached_pca = cached_projection(args, cached)
     check_cached_algorithm(args, cached)
+    normalize, _spherical = check_normalize(args, w)
+    _, cached_norm = cached_normalization(args, cached, normalize)
     if args.clustering.whiten and cache_file is not None and not cached_std:
         raise ValueError("clustering.whiten=True, but the clustering cache {} holds no whiten_std: its centres were trained on "
                          "unwhitened rows".format(cache_file))
@@ -687,6 +707,9 @@ def run_clustering(args):
             if found and partitioned and not (what == 'whitened' and lloyd_cache):
                 raise ValueError("the clustering cache {} is {}: clustering.multi_gpu={} partitions the rows, use views".format(
                     cache_file, what, multi_gpu_mode(args)))
+        if cached_norm and partitioned and not lloyd_cache:
+            raise ValueError("the clustering cache {} is normalised: clustering.multi_gpu={} partitions the rows of an SGD run, and "
+                             "nothing tests that with the row normalisation; use views".format(cache_file, multi_gpu_mode(args)))
         fronts = OrderedDict((v, FrontEnd.from_attrs(cache.find(cached[1], v))) for v in view_dims)
         for v, f in fronts.items():
             f.check_width(v, view_dims[v], " in {}".format(cache_file))
@@ -694,16 +717,30 @@ def run_clustering(args):
             print("whitening with the std of the clustering cache {}".format(cache_file))
         if cached_pca:
             print("projecting with the components of the clustering cache {}".format(cache_file))
+        if cached_norm:
+            print("normalising the rows as the clustering cache {} says".format(cache_file))
         groups.add_front_ends(fronts)
-    else:  # a fresh run: the std, then the scatter matrices of the whitened rows, then the projection
+    else:  # a fresh run: the std, then the scatter matrices of the whitened rows, then the projection, then the row norms
         if args.clustering.whiten:
             stds = compute_whitening(groups, [p.stem for p in paths], view_dims) if partitioned else compute_whitening(groups)
             groups.add_front_ends({v: FrontEnd(std=s) for v, s in stds.items()})
         if args.clustering.pca_dim is not None:
             groups.add_front_ends({v: FrontEnd(pca=f) for v, f in compute_pca(groups, int(args.clustering.pca_dim)).items()})
+        if normalize:  # (a function of one row: no pre-pass, and rows that are already resident go through it once)
+            groups.add_front_ends({v: FrontEnd(normalize=True) for v in view_dims})
     cl = train_clusters(args, probe, groups, [p.stem for p in paths], cached)
+    _report_zero_rows(groups)
     mine = [p.stem for p in paths][rank::w]  # assign: shards strided over ranks (mps/distributed.py:439)
     return assign_clusters(args, groups, cl, mine)
+
+
+def _report_zero_rows(groups):
+    """one line per normalised view: the all-zero rows the normalisation met on the rows that went to the device so far (they
+    have no direction and are left as they are; streamed rows are met once per pass)"""
+    for v, f in groups.fronts.items():
+        if f.normalize:
+            print("normalize {}: {} all-zero rows among the {} rows normalised so far (left as they are)".format(
+                '/'.join(v[1:]), f.zero_rows, f.rows_normalized))
 
 
 def store_shards_set(args, saved_paths):

@@ -73,6 +73,7 @@ class KMeans:
             self.reinit = reinit
             self.sequential = False
             self.algorithm = None  # 'lloyd' once to_lloyd() has run (clustering/lloyd.py); an SGD state carries no such key
+            self.spherical = False  # True: a Lloyd state whose centres are renormalised to unit length after every update
 
     # ------------------------------------------------------------------ handle management
     def __del__(self):
@@ -89,12 +90,14 @@ class KMeans:
                                  "cluster means and its hyper-parameters switch the warm-up and the discount off.  Continue it with "
                                  "clustering.algorithm=lloyd (clustering.lloyd.lloyd_update); the two are not mixed".format(what))
 
-    def to_lloyd(self, centers=None):
+    def to_lloyd(self, centers=None, spherical=False):
         """Make this a batch (Lloyd) k-means state (clustering/lloyd.py): no warm-up (initial_rounds = 0) and a discount that
         divides by exactly 1 (reinit = (.7, 1.0)), so calc_best labels every row with its plainly nearest centre; the state says
         so under 'algorithm', and the SGD entry points refuse it.  centers [k, d]: the initial centres (counts and count start
-        at 0); None keeps the current state."""
+        at 0); None keeps the current state.  spherical: the state of a spherical run (clustering.spherical: unit rows, and
+        finish_iteration renormalises the centres); it says so under 'spherical', a key only such states have."""
         self.algorithm = 'lloyd'
+        self.spherical = bool(spherical)
         self.initial_rounds, self.reinit = 0, (.7, 1.0)
         if self._h is not None:
             _lib.check(_lib._lib.acav_kmeans_set_hyper(self._h, 0, .7, 1.0))
@@ -221,6 +224,8 @@ class KMeans:
         }
         if self.algorithm is not None:  # only a Lloyd state has the key: an SGD state's attrs stay what they were
             dt['algorithm'] = self.algorithm
+        if self.spherical:  # only a spherical Lloyd state has the key
+            dt['spherical'] = True
         return dt
 
     def load_from_saves(self, dt):
@@ -231,6 +236,7 @@ class KMeans:
         self.reinit = tuple(dt.get('reinit', (.7, 5.0)))
         self.sequential = dt.get('sequential', False)
         self.algorithm = dt.get('algorithm')
+        self.spherical = bool(dt.get('spherical'))
         self._centers0 = np.ascontiguousarray(dt['centers'], np.float32)
         self._counts0 = np.ascontiguousarray(dt['counts'], np.float32)
         self._count0 = int(dt.get('count', 0))

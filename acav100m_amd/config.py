@@ -169,6 +169,23 @@ CLUSTERING_DEFAULTS = {
         # rows of the k-means++ sample: None (default) = min(N, 256 * ncentroids) (faiss's max_points_per_centroid), or an
         # integer of at least ncentroids; only the sample has to be resident, the rows themselves may stream
         'init_sample': None,
+        # ours: divide every row of every view by its L2 norm, after the whitening and the projection if they are on (faiss's
+        # normalize_L2, the step in front of the spherical k-means that the reference's correspondence_retrieval/code/
+        # clustering.py runs by default): the clusterer then separates directions, not magnitudes -- a clip's row norm follows
+        # loudness and motion energy.  One in-place sweep on the device as the rows arrive there (acav_rows_normalize), a pure
+        # function of the row; an all-zero row is left as it is and reported, a row with an inf or NaN is an error.  Works with
+        # both algorithms (for sgd it is a row function in front of the unchanged chain: the centres are running means inside the
+        # unit ball).  The cache file keeps 'normalize': True, and a cached run (clustering.cached_epoch) and `evaluate` follow the
+        # cache, whatever this switch says; True against a cache without the key is refused.  Several GPUs: clustering.multi_gpu=
+        # views, or rows with algorithm=lloyd.  False (default): every file stays what it is without the switch.
+        'normalize': False,
+        # ours (algorithm=lloyd only; implies normalize): spherical k-means -- after every centre update the centres are
+        # renormalised to unit length with the same kernel (faiss's Kmeans(spherical=True)).  With unit rows and unit centres the
+        # Euclidean argmin of the assign sweep is the cosine argmax.  A cluster whose mean is exactly the zero vector counts as
+        # empty (the split rule applies).  The cached state carries 'spherical': True beside 'algorithm': 'lloyd';
+        # resume_training continues what the cache says and refuses a switch that contradicts it.  `evaluate` then reports
+        # mean_cosine = 1 - inertia / 2.  False (default): every file stays what it is without the switch.
+        'spherical': False,
     },
     'debug': False,
 }
