@@ -1,7 +1,8 @@
 """GPU: acav_lloyd_centers, the centre update of Lloyd k-means on the device, against the numpy restatement
 (tests/_lloyd_np.centers_of before its empty-cluster rule) bit for bit -- three correctly rounded operations that numpy performs
 identically, so nothing here has a tolerance -- and lloyd.finish_iteration with device tables against the same call with the
-tables copied to numpy (the host path), without and with empty clusters."""
+tables copied to numpy (the host path), without and with empty clusters.  Also past the kernel's capped grid (sized from the
+device's compute unit count), at rows shorter than a quad, and with tables that start off a 16-byte boundary."""
 import ctypes as C
 
 import numpy as np
@@ -12,6 +13,9 @@ from tests import _lloyd_np as L
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(1, 1), (5, 3), (64, 64), (257, 65), (33, 1027)]  # tails in k and d, a pitch off 16 bytes, more than one workgroup
+# rows shorter than a quad: a quad of the flat table spans 4, 2 and 2 rows and steps to the next row's count up to three times,
+# empties among them; k d leaves 3, 2 and 2 tail elements and fills more than one workgroup
+SHAPES += [(1031, 1), (1031, 2), (1030, 3)]
 SHIFTS = [-103, 0, 40, 209]                                  # the ends of fixed_point_shift for fp32 input, and two inside
 COUNTS = [0, 1, 3, 2 ** 31, 2 ** 37]
 SPECIAL = [0, 2 ** 53 + 1, -(2 ** 53 + 1), 2 ** 53 + 3, -(2 ** 53 + 3), 2 ** 62 - 1, -(2 ** 62 - 1), 1, -1, 3, -3]
@@ -67,6 +71,59 @@ def test_centres_sizes_and_empties_are_the_restatements(torch_gpu, monkeypatch, 
         big = np.abs(sums) > 2 ** 53
         kept += int((big & (counts[:, None] > 0)).sum())
     assert kept > 0 or k * d < 8  # the ties above 2^53 are really among the quotients that are compared
+
+
+def test_a_table_past_the_capped_grid(torch_gpu, monkeypatch):
+    """k_lloyd_centers caps its grid at 8 workgroups of 256 threads per compute unit, a quad of elements per thread: a table of
+    more than 4 x 256 x 8 x cus elements is walked in a second round"""
+    torch = torch_gpu
+    from acav100m_amd.clustering.lloyd import centers_on_device
+    cus = int(torch.cuda.get_device_properties(0).multi_processor_count)
+    d = 1024
+    k = 4 * 256 * 8 * cus // d + len(COUNTS)  # 2053 at 256 units: the last five rows are the second round's
+    assert (k - len(COUNTS)) * d >= 4 * 256 * 8 * cus and k * d // 4 // 256 >= 8 * cus
+    for turn, s in ((1, 0), (2, 40)):
+        sums, counts, want = _tables(k, d, s, turn, monkeypatch)
+        assert (counts[-len(COUNTS):] == 0).sum() == 1  # an empty row among the second round's
+        centers, sizes, empty = centers_on_device(torch.from_numpy(sums).cuda(), torch.from_numpy(counts).cuda(), s)
+        got = centers.cpu().numpy()
+        print((k, d), "s", s, "empty", empty, "mismatches", int((got.view(np.uint32) != want.view(np.uint32)).sum()))
+        assert got.tobytes() == want.tobytes(), (k, d, s)
+        assert np.array_equal(sizes.cpu().numpy(), counts.astype(np.float32)), (k, d, s)
+        assert empty == int((counts == 0).sum()), (k, d, s)
+
+
+@pytest.mark.parametrize("k,d", [(257, 65), (33, 1027), (1031, 1)])
+def test_tables_that_start_off_16_bytes(torch_gpu, monkeypatch, k, d):
+    """sums, or centers, off a 16-byte boundary: every element goes one by one (vec == 0) -- the bytes of the aligned call"""
+    torch = torch_gpu
+    from acav100m_amd import _lib
+    from acav100m_amd.clustering.lloyd import centers_on_device
+    assert d % 2 == 1
+    s = 40
+    sums, counts, _want = _tables(k + 1, d, s, 3, monkeypatch)
+    want = _before_the_split(sums[1:], counts[1:], s, monkeypatch)
+    whole_s, whole_c = torch.from_numpy(sums).cuda(), torch.from_numpy(counts).cuda()
+    aligned = centers_on_device(whole_s[1:].clone(), whole_c[1:].clone(), s)
+    assert aligned[0].cpu().numpy().tobytes() == want.tobytes()
+    # sums off 16 bytes (8 d bytes into the table, d odd); the slice is contiguous
+    off_s = whole_s[1:]
+    assert off_s.data_ptr() % 16 == 8 and off_s.is_contiguous()
+    got = centers_on_device(off_s, whole_c[1:], s)
+    assert got[0].cpu().numpy().tobytes() == aligned[0].cpu().numpy().tobytes()
+    assert torch.equal(got[1], aligned[1]) and got[2] == aligned[2] == int((counts[1:] == 0).sum())
+    # centers off 16 bytes (4 d bytes into a buffer): the entry point itself, centers_on_device allocates its own buffer
+    sums_a, counts_a = whole_s[1:].clone(), whole_c[1:].clone()
+    buf = torch.full((k + 1, d), 7.0, dtype=torch.float32, device="cuda")
+    centers, sizes = buf[1:], torch.empty(k, dtype=torch.float32, device="cuda")
+    assert sums_a.data_ptr() % 16 == 0 and centers.data_ptr() % 16 != 0 and centers.is_contiguous()
+    torch.cuda.synchronize()
+    empty = C.c_int64(-5)
+    _lib.check(_lib.load_library().acav_lloyd_centers(0, _lib.ptr(sums_a), _lib.ptr(counts_a), k, d, s, _lib.ptr(centers), _lib.ptr(sizes),
+                                                      C.byref(empty), None))
+    assert centers.cpu().numpy().tobytes() == aligned[0].cpu().numpy().tobytes()
+    assert torch.equal(sizes, aligned[1]) and empty.value == aligned[2]
+    assert bool((buf[0] == 7.0).all())  # the row in front of the table is left alone
 
 
 def test_ties_above_2_53_go_to_even(torch_gpu):

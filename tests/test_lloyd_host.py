@@ -193,6 +193,34 @@ def test_plan_cuts_every_list_into_chunks_of_at_most_512(hist, d):
     assert (chunks[:, 0] == int(np.argmax(hist))).sum() == -(-int(hist.max()) // 512)
 
 
+@pytest.mark.parametrize("cus", [256, 80])
+def test_plan_past_its_caps(cus):
+    """the arms and the clamps of the launch plan: no LDS histogram past 8192 clusters, the sum grid at 8 workgroups per compute
+    unit once there are more than 4 x 8 x cus items, the binning grid at 4 per unit with ceil(n / grid) rows each past
+    4096 x 4 x cus rows"""
+    from acav100m_amd.clustering.lloyd import accumulate_plan
+    for k, lds in ((8192, 1), (8193, 0), (20000, 0)):
+        hist = np.zeros(k, np.int64)
+        hist[[0, k // 2, k - 1]] = 700, 1, 1
+        plan, chunks = accumulate_plan(hist, 3, cus=cus)
+        assert plan["lds_bins"] == lds and plan["chunks"] == len(chunks) == 4 and plan["bin_grid"] == 1 and plan["bin_rows"] == 702
+        assert chunks.tolist() == [[0, 0, 512], [0, 512, 188], [k // 2, 700, 1], [k - 1, 701, 1]]
+    # one-row lists at d = 130: three strips per chunk
+    for n in (4 * 8 * cus // 3, 4 * 8 * cus // 3 + 1, 4 * 8 * cus // 3 + 270):
+        plan, _chunks = accumulate_plan(np.ones(n, np.int64), 130, cus=cus)
+        assert plan["items"] == 3 * n and plan["grid"] == min(-(-3 * n // 4), 8 * cus)
+        if plan["items"] > 4 * 8 * cus:
+            assert plan["grid"] == 8 * cus
+    assert plan["items"] > 4 * 8 * cus
+    for n in (4096 * 4 * cus - 1, 4096 * 4 * cus, 4096 * 4 * cus + 1, 3 * 4096 * 4 * cus + 5):
+        hist = np.array([n - n // 2, 0, n // 2], np.int64)
+        plan, _chunks = accumulate_plan(hist, 1, cus=cus)
+        assert plan["bin_grid"] == min(-(-n // 4096), 4 * cus) and plan["bin_rows"] == -(-n // plan["bin_grid"])
+        assert (plan["bin_rows"] > 4096) == (n > 4096 * 4 * cus)
+        assert plan["bin_grid"] * plan["bin_rows"] >= n > (plan["bin_grid"] - 1) * plan["bin_rows"]  # no workgroup without rows
+    assert plan["bin_grid"] == 4 * cus and plan["bin_rows"] == 3 * 4096 + 1
+
+
 def test_accumulate_refuses_bad_arguments_without_a_device(lib):
     x = np.zeros((10, 4), np.float32)
     lab = np.zeros(10, np.int64)
