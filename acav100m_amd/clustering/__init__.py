@@ -6,3 +6,5 @@ from .lloyd import accumulate, centers_from_sums, fit, fixed_point_shift, lloyd_
 from . import kmeanspp  # noqa: F401
 from . import silhouette  # noqa: F401
 from .silhouette import sample_indices, silhouette_samples, summarise  # noqa: F401
+from . import dedup  # noqa: F401
+from .dedup import nearest_earlier  # noqa: F401

@@ -1,7 +1,9 @@
 """`python cli.py cluster --feature_path=<brace glob .pkl> --out_path=<dir> --meta_path=<dir> [--a.b=v]`
 -- the entry point of clustering/code/cli.py:12-27 + args.py:11-24 on the MI355X hot path.
 `python cli.py evaluate ... --clustering.cached_epoch=<e | [e0,e1,...]>` (ours, clustering/evaluate.py): judge the cached
-clusterings of such a run on the same feature shards."""
+clusterings of such a run on the same feature shards.
+`python cli.py dedup ... --clustering.cached_epoch=<e> --dedup.threshold=<t> --dedup.out_path=<csv>` (ours, clustering/dedup.py):
+near-duplicates inside the clusters of one view of such a run."""
 import sys
 
 from .. import shards as io
@@ -48,6 +50,11 @@ class Cli:
         from .evaluate import evaluate
         return evaluate(get_args(**kwargs))
 
+    def dedup(self, **kwargs):
+        """near-duplicates inside the clusters of one cached epoch and view (clustering/dedup.py); writes nothing into out_path"""
+        from .dedup import dedup
+        return dedup(get_args(**kwargs))
+
 
 def main(argv=None):
     """One process per GPU like the reference (script.py:52-65): started plainly with computation.num_gpus > 1
@@ -58,9 +65,9 @@ def main(argv=None):
     from .. import configure_runtime
     configure_runtime()  # hardware queues for side-by-side clusterings: before the first device call of the process
     from ..parallel import launch
-    if command == 'evaluate':  # a one-process, one-GPU verb: computation.num_gpus starts no further process
+    if command in ('evaluate', 'dedup'):  # one-process, one-GPU verbs: computation.num_gpus starts no further process
         if int(kwargs.get('computation.num_gpus') or 1) > 1:
-            print("evaluate runs in one process on one GPU: computation.num_gpus={} is ignored".format(kwargs['computation.num_gpus']))
+            print("{} runs in one process on one GPU: computation.num_gpus={} is ignored".format(command, kwargs['computation.num_gpus']))
         kwargs['computation.num_gpus'] = 1
     elif launch.env_world() is None:
         want = kwargs.get('computation.num_gpus')

@@ -1,0 +1,211 @@
+"""Near-duplicates inside clusters (`cli.py dedup`, KMeans.near_duplicates, acav_rows_neardup).  No counterpart in the reference:
+it removes duplicates only upstream, inside one video, with an ffmpeg signature; across videos nothing does.
+
+Re-uploads, the same segment cut twice, a channel's static intro: fifty copies of one clip are fifty votes for one cell of the MI
+selection's contingency tables, and picking one copy does nothing to make the next less attractive.  The method is SemDeDup's:
+the clustering is the blocking structure, rows are compared only inside their cluster.  Near-duplicates land in the same cluster
+and bitwise-equal rows always do (a label is a pure function of the row and the state); a pair that a cluster border splits is
+missed -- the documented price of not doing N^2 work.
+
+Definition on rows x [n, d] (fp32, after the view's front-end) with labels l [n] in [0, K), float64 throughout
+(include/acav_hip.h states the summation order and the error bound):
+  cos(i, j)  = x_i.x_j / sqrt(||x_i||^2 ||x_j||^2)
+  E_i        = { j < i : l_j = l_i, ||x_j|| > 0 }: the earlier rows of the same cluster, in input order
+  best[i]    = max over E_i of cos(i, j);  partner[i] = the lowest such j that attains it
+  best[i] = -inf, partner[i] = -1 when E_i is empty or x_i is all zero; a zero row is never a partner
+  flag[i]    = best[i] >= threshold
+The rule is not transitive: a row is judged against every earlier row of its cluster, flagged or not (a chain a ~ b ~ c with a
+and c apart flags b and c and keeps a).  The first occurrence wins.  Bitwise-equal rows come out within the bound of 1, not
+necessarily at 1.0: a threshold of exactly 1 may miss them.  Every pair is a GPU sweep (there is no CPU path);
+tests/_neardup_np.py restates the definition in numpy.
+
+    python -m acav100m_amd.clustering.cli dedup --feature_path=<brace glob .pkl> --meta_path=<dir> \\
+        --out_path=<dir of a cluster run> --clustering.cached_epoch=<e> --dedup.threshold=<t in (0, 1]> \\
+        --dedup.out_path=<csv> [--dedup.view=<model_key>/<layer>] [--dedup.report_path=<json>]
+
+Reads cache_epoch_{e}_{name} as `evaluate` does (warm-up refusal, the front-end of the cache: a whitened, projected or normalised
+view is compared in the space it was clustered in), makes one pass over the row groups, gathers the chosen view's rows after the
+front-end into one device buffer (only that view has to be held in one piece, the groups may stream), labels the buffer with
+calc_best and runs acav_rows_neardup on it.  dedup.out_path (overwritten) holds the flagged rows in global row order, one line
+each: shard_name,filename,partner_shard_name,partner_filename,similarity (repr of the float) -- a file `subset_selection/cli.py
+run --exclude_path=` accepts.  dedup.report_path receives summarise's dictionary as json plus view, epoch, feature_path and
+clusters_path.  Writes nothing into the cluster run's directory.  One process, one GPU."""
+import csv
+import json
+import numbers
+from collections import OrderedDict
+from pathlib import Path
+
+import numpy as np
+
+from .. import _lib
+from .sgd_clustering import _as_f32_2d, _device_index
+from .silhouette import _labels
+
+SIMILARITY_GRID = (0.5, 0.6, 0.7, 0.8, 0.9, 0.95, 0.98, 0.99, 0.999, 0.9999)
+
+
+def nearest_earlier(x, labels, k=None, device="cuda"):
+    """(best float64 [n], partner int64 [n]) of x [n, d] with labels [n] in [0, k) (k=None: max label + 1): acav_rows_neardup.
+    x and labels: numpy or torch, host or device."""
+    keep, xp, n, on_gpu = _as_f32_2d(x)
+    d = int(keep.shape[1])
+    lab = _labels(labels, n)
+    if k is None:
+        k = int(lab.max()) + 1 if n else 1
+    best, partner = np.empty(n, np.float64), np.empty(n, np.int64)
+    lib = _lib.load_library()
+    dev = keep.device.index if on_gpu else _device_index(device)
+    _lib.check(lib.acav_rows_neardup(dev, xp, n, d, _lib.ptr(lab), int(k), _lib.ptr(best), _lib.ptr(partner), None))
+    return best, partner
+
+
+def flag(best, threshold):
+    """bool [n]: best >= threshold (-inf, a row without an earlier row to compare with, is never flagged)"""
+    return np.asarray(best, np.float64) >= float(threshold)
+
+
+def summarise(best, partner, labels, k, threshold):
+    """the report of one run (pure numpy): n, K, threshold, flagged and flagged_share, flagged_by_cluster [K], zero_rows -- the
+    rows that have an earlier row in their cluster and yet no partner: all-zero rows, or rows all of whose earlier cluster mates
+    are all-zero -- and similarity_counts: the rows with best >= g for every g of SIMILARITY_GRID, so that a threshold can be
+    picked from one run"""
+    best, partner = np.asarray(best, np.float64), np.asarray(partner, np.int64)
+    lab, k = np.asarray(labels, np.int64), int(k)
+    n = int(best.shape[0])
+    if partner.shape != (n,) or lab.shape != (n,):
+        raise ValueError("best {}, partner {} and labels {} do not belong together".format(best.shape, partner.shape, lab.shape))
+    flagged = flag(best, threshold)
+    first = np.ones(n, bool)  # the first row of its cluster in input order
+    order = np.argsort(lab, kind='stable')
+    first[order[1:]] = lab[order[1:]] != lab[order[:-1]]
+    return {
+        'n': n, 'K': k, 'threshold': float(threshold),
+        'flagged': int(flagged.sum()), 'flagged_share': float(flagged.sum() / n) if n else float('nan'),
+        'flagged_by_cluster': [int(c) for c in np.bincount(lab[flagged], minlength=k)],
+        'zero_rows': int(((partner < 0) & ~first).sum()),
+        'similarity_counts': OrderedDict((repr(g), int((best >= g).sum())) for g in SIMILARITY_GRID),
+    }
+
+
+def check_options(opts, views=None, epoch=None):
+    """the `dedup` options -> (threshold, view, out_path, report_path).  Pure: no device, no file.  views: the names
+    "<model_key>/<layer>" the cache holds, once it is known (None: dedup.view is only checked for its form); epoch:
+    clustering.cached_epoch, when given exactly one epoch is required"""
+    opts = opts or {}
+    thr = opts.get('threshold')
+    if thr is None:
+        raise ValueError("dedup needs --dedup.threshold=<t in (0, 1]>: the cosine from which a row counts as a duplicate of an "
+                         "earlier one; there is no default, the right value depends on the embedding")
+    if isinstance(thr, bool) or not isinstance(thr, numbers.Real) or not 0.0 < float(thr) <= 1.0:
+        raise ValueError("dedup.threshold must be a number in (0, 1], not {!r}".format(thr))
+    out_path, report_path, view = opts.get('out_path'), opts.get('report_path'), opts.get('view')
+    if out_path is None:
+        raise ValueError("dedup needs --dedup.out_path=<csv>: where the flagged rows go")
+    if view is not None and (not isinstance(view, str) or view.count('/') != 1):
+        raise ValueError("dedup.view must be \"<model_key>/<layer>\", not {!r}".format(view))
+    if views is not None:
+        views = list(views)
+        if view is None:
+            if len(views) != 1:
+                raise ValueError("dedup.view is required, the cache holds {} views: {}".format(len(views), ', '.join(views)))
+            view = views[0]
+        elif view not in views:
+            raise ValueError("dedup.view={!r} is not a view of the cache (it has {})".format(view, ', '.join(views)))
+    if epoch is not None:
+        if isinstance(epoch, (list, tuple)) and len(epoch) == 1:
+            epoch = epoch[0]
+        if isinstance(epoch, bool) or not isinstance(epoch, int):
+            raise ValueError("dedup takes exactly one epoch, --clustering.cached_epoch=<e>, not {!r}".format(epoch))
+    return float(thr), view, out_path, report_path
+
+
+def dedup(args):
+    """the `dedup` verb: prints a summary line and the similarity_counts row, writes dedup.out_path (and dedup.report_path),
+    returns the report"""
+    import torch
+    from .. import shards as io
+    from . import cache
+    from .evaluate import load_states
+    from .frontend import FrontEnd
+    from .row_groups import current_device, open_row_groups, probe_shards
+    from .sgd_clustering import KMeans
+    opts = args.get('dedup') or {}
+    if args.clustering.cached_epoch is None:
+        raise ValueError("dedup needs --clustering.cached_epoch=<e>: the epoch of the cluster run whose clusters block the pairs")
+    check_options(opts, epoch=args.clustering.cached_epoch)  # refused before any cache or shard is read
+    epoch = args.clustering.cached_epoch
+    epoch = epoch[0] if isinstance(epoch, (list, tuple)) else epoch
+    saved = load_states(args, [epoch])[epoch]
+    names = OrderedDict(('/'.join(key[1:]), key) for key in saved)
+    threshold, view, out_path, report_path = check_options(opts, views=sorted(names))
+
+    paths = [Path(p) for p in sorted(io.brace_expand(args.data.path))]
+    sizes = io.shard_sizes_from_meta(paths, args.data.meta.path, use_cache=True)
+    paths = [p for p in paths if p.stem in sizes]
+    _probe, view_dims = probe_shards(args, paths)
+    if view_dims is None:
+        raise ValueError("none of the {} shards of {} could be read".format(len(paths), args.data.path))
+    v = next((key for key in view_dims if '/'.join(key[1:]) == view), None)
+    if v is None:
+        raise ValueError("the shards hold no view {} (they have {})".format(view, ', '.join('/'.join(key[1:]) for key in view_dims)))
+    dev = current_device(args)
+    dt = cache.find(saved, v)
+    front = FrontEnd.from_attrs(dt)
+    front.check_width(v, view_dims[v])
+    d = front.width_out(view_dims[v])
+    if dt['centers'].shape[1] != d:
+        raise ValueError("the clustering cache of epoch {} lacks view {} (width {})".format(epoch, view, d))
+    km = KMeans.load(dt)
+    km.args = None  # one process, one GPU, whatever run wrote the cache
+    km = km.to(dev)
+    K = km.centers.shape[0]
+
+    n_total = sum(int(sizes[p.stem]) for p in paths)
+    need = 4 * n_total * d
+    groups = open_row_groups(args, paths, sizes, view_dims)
+    free, _total = torch.cuda.mem_get_info()
+    beside = groups.budget // 2 if groups.streamed else 0  # a streamed group's rows lie beside the buffer they are copied into
+    if need + beside > free:  # the one view in one piece, refused before the pass starts
+        raise ValueError("dedup holds view {} in one piece: {} rows x {} columns need {} bytes on the device ({} more for a row "
+                         "group), {} are free; dedup a part of the shards, or a projected view".format(
+                             view, n_total, d, need, beside, free))
+    groups.add_front_ends({v: front})
+    x, base, shard_name, filename = None, 0, [], []
+    for _gi, table, rows in groups.iterate(views={v}):
+        part = rows[v]
+        if x is None:
+            x = part if not groups.streamed else torch.empty((n_total, d), dtype=torch.float32, device=part.device)
+        if groups.streamed:
+            if base + part.shape[0] > n_total:
+                raise RuntimeError("the shards deliver more rows than their metadata states ({})".format(n_total))
+            x[base:base + part.shape[0]] = part
+        base += part.shape[0]
+        shard_name.extend(table.shard_name)
+        filename.extend(table.filename)
+    if x is None or base != x.shape[0] or base != len(filename):
+        raise RuntimeError("the shards delivered {} rows, their metadata states {}: fix the metadata or drop the unreadable shards "
+                           "from the list".format(base, n_total))
+    labels, _ = km.calc_best(x, need_mean=False)  # a row's label is a pure function of the row and the state
+    best, partner = nearest_earlier(x, labels, k=K)
+    labels = labels.cpu().numpy() if hasattr(labels, "cpu") else np.asarray(labels)
+
+    report = summarise(best, partner, labels, K, threshold)
+    report.update(view=view, epoch=int(epoch), feature_path=str(args.data.path), clusters_path=str(args.data.output.path))
+    out_path = Path(out_path)
+    out_path.parent.mkdir(parents=True, exist_ok=True)
+    with open(out_path, 'w', newline='') as f:
+        writer = csv.writer(f)
+        for i in np.flatnonzero(flag(best, threshold)):
+            j = int(partner[i])
+            writer.writerow([shard_name[i], filename[i], shard_name[j], filename[j], repr(float(best[i]))])
+    print("dedup: view {} epoch {}: {} of {} rows ({:.3f}%) have an earlier row of their cluster at cosine >= {!r}; {} zero rows; "
+          "wrote {}".format(view, epoch, report['flagged'], report['n'], 100.0 * report['flagged_share'], threshold,
+                            report['zero_rows'], out_path))
+    print("rows with best >= " + "  ".join("{}: {}".format(g, c) for g, c in report['similarity_counts'].items()))
+    if report_path is not None:
+        report_path = Path(report_path)
+        report_path.parent.mkdir(parents=True, exist_ok=True)
+        with open(report_path, 'w') as f:
+            json.dump(report, f, indent=1)
+    return report

@@ -316,6 +316,16 @@ class KMeans:
             labels, _ = self.calc_best(batch, need_mean=False)
         return silhouette_samples(batch, labels, k=self._shape[0], device="cuda:{}".format(self._device))
 
+    def near_duplicates(self, batch, labels=None):
+        """For every row the largest cosine to an earlier row of its own cluster and that row (clustering/dedup.py,
+        acav_rows_neardup: every such pair in float64) -> (best float64 [b], partner int64 [b]; -inf and -1 for a row without
+        one).  labels=None: calc_best(batch, need_mean=False)'s, as for quality.  The centres enter through the labels alone."""
+        from .dedup import nearest_earlier
+        self._require_handle()
+        if labels is None:
+            labels, _ = self.calc_best(batch, need_mean=False)
+        return nearest_earlier(batch, labels, k=self._shape[0], device="cuda:{}".format(self._device))
+
     def train_stats(self):
         """(bulk training calls that ran as one persistent launch, launches that gave up and were re-run per step)"""
         a, b = C.c_int64(0), C.c_int64(0)

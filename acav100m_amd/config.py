@@ -187,6 +187,12 @@ CLUSTERING_DEFAULTS = {
         # mean_cosine = 1 - inertia / 2.  False (default): every file stays what it is without the switch.
         'spherical': False,
     },
+    # ours: the keys of the `dedup` verb (clustering/dedup.py) are read with args.get('dedup') and have no entry here:
+    #   dedup.threshold    required, a number in (0, 1]: the cosine to an earlier row of its cluster from which a row is flagged
+    #                      (no default: the right value depends on the embedding; the run prints the counts over a grid)
+    #   dedup.view         "<model_key>/<layer>": the view whose rows are compared; required when the cache holds several
+    #   dedup.out_path     required: the csv of the flagged rows, shard_name,filename,partner_shard_name,partner_filename,similarity
+    #   dedup.report_path  optional: the summary as json
     'debug': False,
 }
 
@@ -229,6 +235,10 @@ SUBSET_DEFAULTS = {
     #   0 = plain greedy.  batch_mi and contrastive refuse a nonzero value
     'celf_ratio': 0,
     'shuffle_candidates': True,
+    # ours: exclude_path=<csv> (subset_selection/exclude.py) is read with args.get('exclude_path') and has no entry here: the
+    #   clips listed in the file's first two columns (shard_name,filename: a `clustering/cli.py dedup` file, or the output.csv of
+    #   an earlier run) are dropped right after the assignment shards are loaded, subset.ratio applies to the rest; refused for
+    #   contrastive and the pca measures, which read feature shards
     'chunk_size': None,
     'save_cache_as_csvs': True,
     'log_every': 1000,

@@ -1,0 +1,407 @@
+// acav_neardup.hip -- near-duplicates inside clusters (acav_rows_neardup; clustering/dedup.py, the `dedup` verb): for every row
+// the largest cosine to an EARLIER row of its own cluster and that row, every such pair in float64.  SemDeDup's rule with the
+// clusterings as the blocking structure; the reference removes duplicates only upstream, inside one video.
+//
+// Arithmetic.  Everything is float64 on the stored fp32 values, as in acav_silhouette.hip: nrm_i = ||x_i||^2 one wave per row
+// (lane l chains fma(v, v, .) over its columns l, l + 64, ... from +0, then v[l] + v[l ^ o] for o = 32 ... 1), dot(i, j) one chain
+// of v_mfma_f64_16x16x4_f64 over the columns 0, 4, 8, ... from a zero accumulator (tails in d are zero-filled when a stage is
+// loaded: they add exactly 0), cos(i, j) = dot(i, j) / sqrt(nrm_i * nrm_j): one product, one sqrt, one division.
+//
+// Label-sorted positions.  The entry sorts the positions by label, stably, so a cluster is one contiguous RUN in which ascending
+// sorted position is ascending input position.  The earlier rows of row p's cluster are then the sorted positions
+// [start of p's run, p): one pair of bounds per row, no run ids.  A column whose norm is 0 is stored as -inf and never wins.
+//
+// Tiling.  One workgroup (4 waves) owns a tile of ND_QM = 64 RT consecutive sorted positions (RT = 1 or 2 by the plan) and walks
+// the column blocks of ND_CN = 64 sorted positions from the block that holds the start of its FIRST row's run up to the block
+// that holds its own LAST row: the work is triangular.  Stages, operands and accumulators are acav_silhouette.hip's.  After the
+// last stage of a block the tile's cosines go to LDS (over the stages) and one thread per query row walks its columns
+// max(block start, run start) ... min(block end, p) - 1 in ascending position with a strict `>`: the lowest position wins a tie,
+// within a block and -- the blocks being walked in ascending order -- across them.
+//
+// Tile list.  Tiles late in a large cluster walk more blocks than early ones, so the host orders the tiles by descending number
+// of blocks (ties: ascending tile index) and workgroup b takes entry b of that list: the long tiles start first.  neardup_tiles
+// builds the list from the label histogram alone; acav_rows_neardup_plan exposes it, the entry point launches from it.
+//
+// Invariance.  (best_i, partner_i) is a pure function of the rows of cluster labels[i] up to row i: the dot of a pair is the same
+// chain wherever the pair sits in a tile, the maximum is taken in ascending position whatever the tile size, the workgroup, the
+// other clusters or host / device / unaligned input (the guarded load path feeds the same values into the same chain).  No
+// floating-point atomics; the same call gives the same bytes every time.
+#include <algorithm>
+#include <cmath>
+#include <numeric>
+#include <vector>
+
+#include "acav_common.h"
+
+using namespace acav;
+
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+
+namespace {
+
+constexpr int64_t ND_MAX_N = ((int64_t)1 << 31) - 1;  // positions are 32-bit
+constexpr int ND_MAX_D = 16384;
+constexpr int ND_QM = 64;        // query rows of a tile per RT: 16 per wave
+constexpr int ND_CN = 64;        // columns of a block: four 16 x 16 accumulators per wave and RT
+constexpr int ND_DK = 32;        // columns of d of a stage
+constexpr int ND_ST = ND_DK + 4; // fp32 stage, row stride: the 16 rows x 4 columns of a fragment fall into 64 different banks
+constexpr int ND_CS = ND_CN + 1; // float64 cosine tile, row stride: the walk's lanes (one row each) fall into different bank pairs
+
+constexpr size_t neardup_lds(int rt)
+{
+    // the cosine tile lies over the two stages (which are dead by then)
+    return std::max(sizeof(double) * (size_t)ND_QM * rt * ND_CS, sizeof(float) * (size_t)(ND_QM * rt + ND_CN) * ND_ST);
+}
+static_assert(2 * neardup_lds(2) <= 160 * 1024, "two workgroups of the larger tile share a compute unit's LDS");
+
+struct NdTile {
+    int q0, rows, cb0, blocks;  // first sorted position, rows, first column block, column blocks
+};
+
+struct NdPlan {
+    int rt;
+    int64_t tiles, blocks;  // blocks: column blocks walked by all tiles together
+    size_t lds, scratch;
+};
+
+// 128-row tiles (less operand traffic per multiply-add) once they alone give every compute unit a workgroup, 64-row tiles
+// otherwise: acav_rows_silhouette_plan's rule
+int neardup_rt(int64_t n, int cus) { return (n + 2 * ND_QM - 1) / (2 * ND_QM) >= cus ? 2 : 1; }
+
+// the tiles of a label histogram: tile t holds the sorted positions [t QM, min(n, (t + 1) QM)) and walks the column blocks from
+// the one that holds the start of the run of its first row up to the one that holds its last row.  list (NULL: skipped): the
+// tiles by descending blocks, ties by ascending t.  Returns the plan.
+NdPlan neardup_tiles(const int64_t *hist, int k, int d, int cus, std::vector<NdTile> *list)
+{
+    (void)d;
+    int64_t n = 0;
+    for (int b = 0; b < k; ++b) n += hist[b];
+    NdPlan p;
+    p.rt = neardup_rt(n, cus);
+    const int64_t qm = (int64_t)ND_QM * p.rt;
+    p.tiles = (n + qm - 1) / qm;
+    p.blocks = 0;
+    if (list) list->clear(), list->reserve((size_t)p.tiles);
+    int b = 0;
+    int64_t start = 0;  // of the run that holds the tile's first row
+    for (int64_t t = 0; t < p.tiles; ++t) {
+        const int64_t q0 = t * qm, q1 = std::min(n, q0 + qm);
+        while (start + hist[b] <= q0) start += hist[b], ++b;  // empty labels have no run
+        const int64_t cb0 = start / ND_CN, cb1 = (q1 - 1) / ND_CN;
+        p.blocks += cb1 - cb0 + 1;
+        if (list) list->push_back(NdTile{(int)q0, (int)(q1 - q0), (int)cb0, (int)(cb1 - cb0 + 1)});
+    }
+    if (list) std::stable_sort(list->begin(), list->end(), [](const NdTile &a, const NdTile &c) { return a.blocks > c.blocks; });
+    p.lds = neardup_lds(p.rt);
+    // the sorted positions and run starts, the norms, the tile list, (best, partner)
+    p.scratch = sizeof(int) * 2 * (size_t)n + sizeof(double) * (size_t)n + sizeof(NdTile) * (size_t)p.tiles +
+                (sizeof(double) + sizeof(int64_t)) * (size_t)n;
+    return p;
+}
+
+// labels outside [0, k): counted before anything is indexed with a label
+__global__ __launch_bounds__(256) void k_nd_labels(const int64_t *__restrict__ labels, int64_t n, int k, unsigned *__restrict__ bad)
+{
+    unsigned mine = 0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+        mine += (labels[i] < 0 || labels[i] >= k) ? 1u : 0u;
+    if (mine) atomicAdd(bad, mine);
+}
+
+// values that are not finite (an all-ones exponent), counted likewise
+__global__ __launch_bounds__(256) void k_nd_finite(const float *__restrict__ x, size_t total, unsigned long long *__restrict__ bad)
+{
+    unsigned long long mine = 0;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256)
+        mine += (__float_as_uint(x[i]) & 0x7f800000u) == 0x7f800000u ? 1ull : 0ull;
+    if (mine) atomicAdd(bad, mine);
+}
+
+// one wave per sorted position c: nrm[c] = ||x[perm[c]]||^2 (lane l: columns l, l + 64, ...; then a fixed tree)
+__global__ __launch_bounds__(64) void k_nd_norms(const float *__restrict__ x, int d, const int *__restrict__ perm, double *__restrict__ nrm)
+{
+    const size_t base = (size_t)perm[blockIdx.x] * d;
+    double p = 0.0;
+    for (int j = threadIdx.x; j < d; j += 64) {
+        const double v = (double)x[base + j];
+        p = fma(v, v, p);
+    }
+    for (int o = 32; o >= 1; o >>= 1) p = p + __shfl_xor(p, o);
+    if (threadIdx.x == 0) nrm[blockIdx.x] = p;
+}
+
+// columns j .. j + 3 of a row as they are stored; no branch: the load goes to a clamped address inside the row, nd_mask zeroes
+// what was clamped
+template <bool VEC>
+__device__ __forceinline__ float4 nd_fetch(const float *__restrict__ r, int d, int j)
+{
+    if (VEC) return *reinterpret_cast<const float4 *>(r + min(j, d - 4));  // d % 4 == 0: j < d means j + 3 < d
+    return make_float4(r[min(j, d - 1)], r[min(j + 1, d - 1)], r[min(j + 2, d - 1)], r[min(j + 3, d - 1)]);
+}
+
+__device__ __forceinline__ float4 nd_mask(float4 a, bool row_ok, int d, int j)
+{
+    float4 v;
+    v.x = (row_ok && j < d) ? a.x : 0.f;
+    v.y = (row_ok && j + 1 < d) ? a.y : 0.f;
+    v.z = (row_ok && j + 2 < d) ? a.z : 0.f;
+    v.w = (row_ok && j + 3 < d) ? a.w : 0.f;
+    return v;
+}
+
+// perm[c]: the input position of sorted position c; rstart[c]: the sorted position its run starts at; nrm[c]: ||x||^2.
+// tiles[b]: the tile workgroup b takes.  best / partner: by INPUT position
+template <int RT, bool VEC>
+__global__ __launch_bounds__(256, 2) void k_neardup(const float *__restrict__ x, int d, int n, const int *__restrict__ perm,
+                                                    const int *__restrict__ rstart, const double *__restrict__ nrm,
+                                                    const NdTile *__restrict__ tiles, double *__restrict__ best,
+                                                    int64_t *__restrict__ partner)
+{
+    constexpr int QM = ND_QM * RT;
+    extern __shared__ double nd_smem[];
+    double *cosv = nd_smem;                          // [QM][ND_CS], after the last chunk of a block
+    float *qs = reinterpret_cast<float *>(nd_smem);  // [QM][ND_ST]
+    float *cs = qs + QM * ND_ST;                     // [ND_CN][ND_ST]
+
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int fr = lane & 15, fq = lane >> 4;  // fragment row (A) / column (B) and k index of this lane
+    const int lq = t & 7, lr = t >> 3;         // this thread stages columns 4 lq .. 4 lq + 3 of the rows lr + 32 u
+    const NdTile tile = tiles[blockIdx.x];
+    const int q0 = tile.q0, q1 = tile.q0 + tile.rows;  // q1 <= n
+    const double inf = __builtin_inf();
+
+    // the query rows this thread stages, and the ones whose results it holds
+    const float *qrow[2 * RT];
+    bool qok[2 * RT];
+#pragma unroll
+    for (int u = 0; u < 2 * RT; ++u) {
+        const int q = q0 + lr + 32 * u;
+        qok[u] = q < q1;
+        qrow[u] = x + (size_t)perm[qok[u] ? q : q0] * d;
+    }
+    double qn[RT][4];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {  // C/D of the f64 MFMA: column = lane & 15, row = (lane >> 4) + 4 * register
+            const int q = q0 + wave * 16 * RT + rt * 16 + fq + 4 * r;
+            qn[rt][r] = nrm[q < q1 ? q : q0];
+        }
+    // the walk: thread t < QM owns query row t of the tile; a zero row has no partner and is none
+    const int my_pos = q0 + t;
+    const bool walker = t < QM && my_pos < q1;
+    const int my_lo = walker && nrm[my_pos] > 0.0 ? rstart[my_pos] : n;  // its columns: the sorted positions [my_lo, my_pos)
+    double top = -inf;
+    int arg = -1;
+
+    for (int cb = tile.cb0; cb < tile.cb0 + tile.blocks; ++cb) {
+        const int c0 = cb * ND_CN;  // c0 <= q1 - 1 < n
+        const float *crow[2];
+        bool cok[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int c = c0 + lr + 32 * u;
+            cok[u] = c < n;
+            crow[u] = x + (size_t)perm[cok[u] ? c : c0] * d;
+        }
+        f64x4 acc[RT][4];
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+            for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = f64x4{0.0, 0.0, 0.0, 0.0};
+        float4 pq[2 * RT], pc[2];  // the next chunk, in flight while the current one is multiplied
+#pragma unroll
+        for (int u = 0; u < 2 * RT; ++u) pq[u] = nd_fetch<VEC>(qrow[u], d, 4 * lq);
+#pragma unroll
+        for (int u = 0; u < 2; ++u) pc[u] = nd_fetch<VEC>(crow[u], d, 4 * lq);
+        for (int j0 = 0; j0 < d; j0 += ND_DK) {
+            __syncthreads();  // the previous stage has been read (and the previous block's cosine tile walked)
+#pragma unroll
+            for (int u = 0; u < 2 * RT; ++u)
+                *reinterpret_cast<float4 *>(&qs[(lr + 32 * u) * ND_ST + 4 * lq]) = nd_mask(pq[u], qok[u], d, j0 + 4 * lq);
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+                *reinterpret_cast<float4 *>(&cs[(lr + 32 * u) * ND_ST + 4 * lq]) = nd_mask(pc[u], cok[u], d, j0 + 4 * lq);
+            __syncthreads();
+            if (j0 + ND_DK < d) {
+#pragma unroll
+                for (int u = 0; u < 2 * RT; ++u) pq[u] = nd_fetch<VEC>(qrow[u], d, j0 + ND_DK + 4 * lq);
+#pragma unroll
+                for (int u = 0; u < 2; ++u) pc[u] = nd_fetch<VEC>(crow[u], d, j0 + ND_DK + 4 * lq);
+            }
+#pragma unroll
+            for (int kk = 0; kk < ND_DK / 4; ++kk) {
+                double a[RT], b[4];
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt) a[rt] = (double)qs[(wave * 16 * RT + rt * 16 + fr) * ND_ST + kk * 4 + fq];
+#pragma unroll
+                for (int ct = 0; ct < 4; ++ct) b[ct] = (double)cs[(ct * 16 + fr) * ND_ST + kk * 4 + fq];
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                    for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[rt], b[ct], acc[rt][ct], 0, 0, 0);
+            }
+        }
+        __syncthreads();  // every wave has read the last stage: the cosine tile goes over it
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct) {
+            const int c = c0 + ct * 16 + fr;
+            const double cn = nrm[c < n ? c : n - 1];
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    cosv[(wave * 16 * RT + rt * 16 + fq + 4 * r) * ND_CS + ct * 16 + fr] =
+                        cn > 0.0 ? acc[rt][ct][r] / sqrt(qn[rt][r] * cn) : -inf;  // a zero row is never a partner
+        }
+        __syncthreads();
+        if (walker) {
+            const int lo = my_lo > c0 ? my_lo : c0, hi = my_pos < c0 + ND_CN ? my_pos : c0 + ND_CN;
+            const double *mine = cosv + t * ND_CS;
+            for (int c = lo; c < hi; ++c) {
+                const double v = mine[c - c0];
+                if (v > top) top = v, arg = c;  // strict: the lowest position keeps a tie
+            }
+        }
+    }
+    if (walker) {
+        const size_t o = (size_t)perm[my_pos];
+        best[o] = top;
+        partner[o] = arg >= 0 ? (int64_t)perm[arg] : (int64_t)-1;
+    }
+}
+
+int use_device(int device, int *cus)
+{
+    int n = 0;
+    hipError_t e = hipGetDeviceCount(&n);
+    if (e != hipSuccess || n == 0) {
+        (void)hipGetLastError();
+        set_error("no HIP device available: this library does not fall back to the CPU");
+        return ACAV_EHIP;
+    }
+    ACAV_REQUIRE(device >= 0 && device < n, ACAV_EINVAL, "device %d out of range (have %d)", device, n);
+    ACAV_HIP_TRY(hipSetDevice(device));
+    ACAV_HIP_TRY(hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, device));
+    return ACAV_OK;
+}
+
+template <int RT>
+int launch(const NdPlan &plan, bool vec, hipStream_t st, const float *x, int d, int n, const int *perm, const int *rstart,
+           const double *nrm, const NdTile *tiles, double *best, int64_t *partner)
+{
+    // the tile's size, whatever another thread's call asks for: it never lowers it under a pending launch
+    const void *fn = vec ? reinterpret_cast<const void *>(k_neardup<RT, true>) : reinterpret_cast<const void *>(k_neardup<RT, false>);
+    ACAV_HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)neardup_lds(RT)));
+    if (vec)
+        hipLaunchKernelGGL((k_neardup<RT, true>), dim3((unsigned)plan.tiles), dim3(256), plan.lds, st, x, d, n, perm, rstart, nrm,
+                           tiles, best, partner);
+    else
+        hipLaunchKernelGGL((k_neardup<RT, false>), dim3((unsigned)plan.tiles), dim3(256), plan.lds, st, x, d, n, perm, rstart, nrm,
+                           tiles, best, partner);
+    ACAV_HIP_TRY(hipGetLastError());
+    return ACAV_OK;
+}
+
+}  // namespace
+
+ACAV_EXPORT int acav_rows_neardup_plan(const int64_t *hist, int k, int d, int cus, int64_t *out, int64_t *tiles, int64_t cap)
+{
+    ACAV_REQUIRE(hist && out, ACAV_EINVAL, "NULL argument");
+    ACAV_REQUIRE(k >= 1 && d >= 1 && d <= ND_MAX_D && cus > 0, ACAV_EINVAL, "bad sizes");
+    int64_t n = 0;
+    for (int b = 0; b < k; ++b) {
+        ACAV_REQUIRE(hist[b] >= 0 && hist[b] <= ND_MAX_N, ACAV_EINVAL, "hist[%d] = %lld must be in [0, 2^31)", b, (long long)hist[b]);
+        n += hist[b];
+        ACAV_REQUIRE(n <= ND_MAX_N, ACAV_EINVAL, "the histogram holds 2^31 rows or more: positions are 32-bit");
+    }
+    ACAV_REQUIRE(n >= 1, ACAV_EINVAL, "the histogram holds no row");
+    std::vector<NdTile> list;
+    const NdPlan p = neardup_tiles(hist, k, d, cus, tiles ? &list : nullptr);
+    ACAV_REQUIRE(!tiles || cap >= p.tiles, ACAV_EINVAL, "room for %lld tiles, the rows are cut into %lld", (long long)cap, (long long)p.tiles);
+    out[0] = (int64_t)ND_QM * p.rt, out[1] = p.tiles, out[2] = p.blocks, out[3] = p.tiles, out[4] = (int64_t)p.lds;
+    out[5] = (int64_t)p.scratch;
+    if (tiles)
+        for (int64_t t = 0; t < p.tiles; ++t) {
+            const NdTile &e = list[(size_t)t];
+            tiles[4 * t] = e.q0, tiles[4 * t + 1] = e.rows, tiles[4 * t + 2] = e.cb0, tiles[4 * t + 3] = e.blocks;
+        }
+    return ACAV_OK;
+}
+
+ACAV_EXPORT int acav_rows_neardup(int device, const float *x, int64_t n, int d, const int64_t *labels, int k, double *best,
+                                  int64_t *partner, void *stream)
+{
+    ACAV_REQUIRE(x && labels && best && partner, ACAV_EINVAL, "NULL argument");
+    ACAV_REQUIRE(n >= 1 && n <= ND_MAX_N, ACAV_EINVAL, "n=%lld must be in [1, 2^31): positions are 32-bit", (long long)n);
+    ACAV_REQUIRE(d >= 1 && d <= ND_MAX_D, ACAV_EINVAL, "d=%d must be in [1, %d]", d, ND_MAX_D);
+    ACAV_REQUIRE(k >= 1, ACAV_EINVAL, "k=%d must be at least 1", k);
+    int cus = 0;
+    ACAV_TRY(use_device(device, &cus));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+
+    DevBuf stage_x, stage_lab, bad, ints, nrm, dtiles, obest, opartner;
+    StreamDrain drain = {st};
+    const void *dx = nullptr, *dl = nullptr;
+    const size_t total = (size_t)n * d;
+    ACAV_TRY(to_device(x, sizeof(float) * total, stage_x, st, &dx));
+    ACAV_TRY(to_device(labels, sizeof(int64_t) * (size_t)n, stage_lab, st, &dl));
+    const float *xd = static_cast<const float *>(dx);
+    ACAV_TRY(bad.ensure(sizeof(unsigned long long) * 2));  // [0] labels out of range (its low word), [1] values not finite
+    ACAV_HIP_TRY(hipMemsetAsync(bad.p, 0, sizeof(unsigned long long) * 2, st));
+    hipLaunchKernelGGL(k_nd_labels, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, st,
+                       static_cast<const int64_t *>(dl), n, k, bad.as<unsigned>());
+    ACAV_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_nd_finite, dim3((unsigned)std::min<size_t>((total + 255) / 256, (size_t)cus * 8)), dim3(256), 0, st, xd, total,
+                       bad.as<unsigned long long>() + 1);
+    ACAV_HIP_TRY(hipGetLastError());
+    unsigned long long nbad[2] = {0, 0};
+    std::vector<int64_t> lab((size_t)n);
+    ACAV_HIP_TRY(hipMemcpyAsync(nbad, bad.p, sizeof(nbad), hipMemcpyDeviceToHost, st));
+    ACAV_HIP_TRY(hipMemcpyAsync(lab.data(), dl, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+    ACAV_HIP_TRY(hipStreamSynchronize(st));
+    ACAV_REQUIRE(nbad[0] == 0, ACAV_EINVAL, "%llu of %lld labels are outside [0, %d)", nbad[0], (long long)n, k);
+    ACAV_REQUIRE(nbad[1] == 0, ACAV_EINVAL, "%llu of the %lld x %d values are not finite (inf or NaN)", nbad[1], (long long)n, d);
+
+    // the positions by label, stably; per sorted position the start of its run; the label histogram for the tile list
+    std::vector<int> host((size_t)(2 * n));
+    int *perm = host.data(), *rstart = perm + n;
+    if ((int64_t)k <= 4 * n + 1024) {  // a counting sort, n + k steps (a million rows: a few ms against the merge sort's 100)
+        std::vector<int64_t> at((size_t)k + 1, 0);
+        for (int64_t i = 0; i < n; ++i) ++at[(size_t)lab[(size_t)i] + 1];
+        for (int b = 0; b < k; ++b) at[(size_t)b + 1] += at[(size_t)b];
+        for (int64_t i = 0; i < n; ++i) perm[at[(size_t)lab[(size_t)i]]++] = (int)i;
+    } else {  // the same permutation without a table of k entries: k is not limited
+        std::iota(perm, perm + n, 0);
+        std::stable_sort(perm, perm + n, [&](int a, int b) { return lab[(size_t)a] < lab[(size_t)b]; });
+    }
+    std::vector<int64_t> runs;  // the histogram without its empty labels: the same tiles
+    for (int64_t c = 0, first = 0; c < n; ++c) {
+        if (c == 0 || lab[(size_t)perm[c]] != lab[(size_t)perm[c - 1]]) first = c, runs.push_back(0);
+        rstart[c] = (int)first;
+        ++runs.back();
+    }
+    std::vector<NdTile> list;
+    const NdPlan plan = neardup_tiles(runs.data(), (int)runs.size(), d, cus, &list);
+
+    const bool best_dev = is_device_ptr(best), partner_dev = is_device_ptr(partner);
+    ACAV_TRY(upload(ints, host.data(), sizeof(int) * host.size(), st));
+    ACAV_TRY(upload(dtiles, list.data(), sizeof(NdTile) * list.size(), st));
+    ACAV_TRY(nrm.ensure(sizeof(double) * (size_t)n));
+    if (!best_dev) ACAV_TRY(obest.ensure(sizeof(double) * (size_t)n));
+    if (!partner_dev) ACAV_TRY(opartner.ensure(sizeof(int64_t) * (size_t)n));
+    double *dbest = best_dev ? best : obest.as<double>();
+    int64_t *dpartner = partner_dev ? partner : opartner.as<int64_t>();
+    const int *dperm = ints.as<int>(), *drstart = dperm + n;
+    const bool vec = d % 4 == 0 && (reinterpret_cast<uintptr_t>(xd) & 15) == 0;
+    hipLaunchKernelGGL(k_nd_norms, dim3((unsigned)n), dim3(64), 0, st, xd, d, dperm, nrm.as<double>());
+    ACAV_HIP_TRY(hipGetLastError());
+    if (plan.rt == 2)
+        ACAV_TRY(launch<2>(plan, vec, st, xd, d, (int)n, dperm, drstart, nrm.as<double>(), dtiles.as<NdTile>(), dbest, dpartner));
+    else
+        ACAV_TRY(launch<1>(plan, vec, st, xd, d, (int)n, dperm, drstart, nrm.as<double>(), dtiles.as<NdTile>(), dbest, dpartner));
+    if (!best_dev) ACAV_HIP_TRY(hipMemcpyAsync(best, obest.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
+    if (!partner_dev) ACAV_HIP_TRY(hipMemcpyAsync(partner, opartner.p, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+    ACAV_HIP_TRY(hipStreamSynchronize(st));
+    return ACAV_OK;
+}

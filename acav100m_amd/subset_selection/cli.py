@@ -9,6 +9,7 @@ import time
 from pathlib import Path
 
 from ..config import SUBSET_DEFAULTS, merge, parse_cli
+from .exclude import check_exclude
 from .run import compare_measures, lockstep_supported, merge_all_csvs, reduce_all_pkls, run_chunks, run_single
 from .run_contrastive import merge_contrastive, run_chunks_contrastive, run_single_contrastive
 from .run_greedy import check_celf_ratio, check_weight_type
@@ -55,6 +56,7 @@ def check_run(args):
     pca = is_pca_measure(args.measure_name)
     check_weight_type(args.measure_name, args.clustering.weight_type)
     check_celf_ratio(args.measure_name, args.get('celf_ratio', 0))
+    check_exclude(args.measure_name, args.get('exclude_path'))
     # a lockstep width means something to a chunked run only; the pca measures refuse it without a chunk_size too
     if int(args.computation.concurrent_chunks or 1) > 1 and (args.chunk_size is not None or pca):
         lockstep_supported(args.measure_name, args.get('celf_ratio', 0))

@@ -12,6 +12,7 @@ import numpy as np
 
 from .. import shards as io
 from .chunks import plan_chunks, save_chunk
+from .exclude import apply_exclude, read_exclude
 from .measures import get_measure
 from .run_greedy import _prepare, _run_greedy, run_greedy
 
@@ -54,6 +55,9 @@ def _load(args, path):
     """chunk.load_and_preprocess (chunk.py:156-175): everything of a chunk that does not need the GPU."""
     partitions, metas = load_data(path, args.data.meta.path, args.verbose)
     data = [(k, io.load_assignment_shards(partitions[k])) for k in sorted(partitions)]
+    if args.get('exclude_path') is not None:  # ours (exclude.py): the listed clips never reach the selection
+        keys = read_exclude(args.get('exclude_path'))
+        data = [(k, apply_exclude(keys, loaded)) for k, loaded in data]
     return data, metas
 
 
