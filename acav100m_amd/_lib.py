@@ -112,6 +112,8 @@ SIGNATURES = {
     "acav_gs_block_grid": [i64, i32, i32, C.POINTER(i64)],
     "acav_gs_block_map": [i64, i32, i32, C.POINTER(i32), C.POINTER(i64)],
     "acav_mi_greedy_form": [i32, vp, vp, i32, i32, i32, i64, i32, i32, i32, vp, i64, i64, vp, vp, vp, vp],
+    "acav_mi_run_draw": [vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64],
+    "acav_mi_draw_form": [i32, vp, vp, i32, i32, i32, i64, i32, i32, i32, vp],
     "acav_mi_run_exact": [vp, vp, i64, i32, i64, vp, vp, C.POINTER(i64), vp, vp, vp],
     "acav_mi_run_exact_multi": [vp, i32, vp, vp, vp, vp, vp, vp, vp],
     "acav_mi_run_celf": [vp, vp, i64, i32, i64, f64, vp, vp, vp, C.POINTER(i64), i64, vp, vp, vp],

@@ -223,6 +223,11 @@ SUBSET_DEFAULTS = {
     #   1 <= selection_size <= batch_size <= 1024 and batch_size x clustering pairs <= 8192 (both are clamped to the number of
     #   clips first).  The defaults are the reference CLI's; its paper grids run at batch_size 100 / selection_size 25 (every
     #   correspondence_retrieval search target) -- 6 x fewer iterations, hence permutations of the candidate list, per subset
+    # ours: batch.sampler='permutation' | 'draw' is read with args.batch.get('sampler') and has no entry here (missing reads as
+    #   'permutation': the whole candidate list is shuffled every iteration on the reference's generator stream).  'draw'
+    #   performs only the first batch_size steps of that shuffle -- every batch keeps its distribution, an iteration costs
+    #   O(batch_size) instead of O(candidates), the generator stream (hence the selection) is its own; batch_mi only
+    #   (run_greedy.check_sampler), and it works with computation.concurrent_chunks
     'batch': {'batch_size': 20, 'selection_size': 4, 'keep_unselected': True},
     'contrastive': {'num_epochs': 3, 'num_warmup_steps': 1, 'base_lr': 2e-4, 'train_batch_size': 128, 'test_batch_size': 128,
                     'cached_epoch': None, 'train_from_cached': False},

@@ -2168,6 +2168,188 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     }
 }
 
+// ------------------------------------------------------------------- the draw sampler (batch.sampler=draw)
+// The batch of an iteration is the first B entries of a fresh uniform permutation of the live list, and the first B steps of
+// randperm's loop (for i < n - 1: z = u32 % (n - i); swap(r[i], r[i + z])) already fix them: a step i >= B never touches a position
+// below B.  k_mi_draw runs only those B steps, on the window r[lo .. L0) of the chunk's candidate array, then today's selection
+// (mi_select_stage / mi_select_body) on r[lo .. lo + B), then moves the window start: O(B P) per iteration, nothing O(L).
+// One workgroup per chunk; the iterations [it0, it0 + nit) of a launch are a loop in the kernel, and what one iteration stores
+// (tables, running sums, candidates) the next one reads after a __syncthreads() (which waits for the vector stores, unlike
+// lds_barrier).  Chunks share nothing.  Between launches the window start and the generator live in device memory (DrawState, mt).
+struct DrawState {
+    int lo, idx;  // the window start; the next word of the generator block mt[624] (624: the block is used up)
+};
+struct DrawChunk {
+    int *r;        // [L0] candidate ids
+    unsigned *mt;  // [624] MT19937 block (raw words)
+    DrawState *st;
+    const int *asg, *pairs;
+    int *Nc, *ac, *bc;
+    double *SN, *Sa, *Sb;
+    const double *phi;
+    MiScalars *sc;
+    long long *S;
+    double *G;
+    int *tr_pos;
+    long long *tr_ids;
+    double *tr_sc;
+    const float *w;
+    int L0, iters, D, C, P;
+};
+
+// The next block of 624 words in place, by the workgroup: acav_rng::refill's loop in its four dependent ranges -- [0, 227) reads
+// the old block only, [227, 454) and [454, 623) also the new words 227 back, word 623 the new words 396 and 0.  Every range reads,
+// meets at a barrier, writes (a word's right-hand neighbour is still the old one when it is read).
+__device__ __forceinline__ void draw_mt_refill(unsigned *mt)
+{
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int ph = 0; ph < 4; ++ph) {
+        const int lo = ph == 0 ? 0 : ph == 1 ? 227 : ph == 2 ? 454 : 623, hi = ph == 0 ? 227 : ph == 1 ? 454 : ph == 2 ? 623 : 624;
+        const int i = lo + tid;
+        unsigned v = 0;
+        if (i < hi) {
+            const unsigned y = (mt[i] & 0x80000000u) | (mt[i == 623 ? 0 : i + 1] & 0x7fffffffu);
+            v = mt[i < 227 ? i + 397 : i - 227] ^ mt_twist(y);
+        }
+        lds_barrier();
+        if (i < hi) mt[i] = v;
+        lds_barrier();
+    }
+}
+
+constexpr int DRAW_WPT = SEL_WIDEB / DRAW_THREADS;  // batch positions per thread: t = tid + 256 q
+// draw_off: where the swap arrays start in dynamic LDS (draw_lds_off of the launch's selection LDS: behind every chunk's layout)
+template <bool W, bool WIDE>
+__global__ __launch_bounds__(DRAW_THREADS) void k_mi_draw(const DrawChunk *__restrict__ cd, int it0, int nit, int B, int k, int mode,
+                                                          int keep_unselected, unsigned draw_off)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    __shared__ SelSharedOf<W> ss;
+    __shared__ unsigned sMT[624];
+    __shared__ int sInWin;
+    const DrawChunk c = cd[blockIdx.x];
+    const int tid = threadIdx.x;
+    const int it1 = it0 + nit < c.iters ? it0 + nit : c.iters;
+    if (it0 >= it1) return;  // this chunk is over
+    // win: the window's first B entries (the batch, once the swaps are resolved); dep: what a step leaves at its outside target;
+    // tgt: window-relative target of step t; orig: the value found at an outside target; prev: the last earlier step with the same
+    // outside target, or -1 (after the selection: 1 = this batch position was committed)
+    int *const sWin = reinterpret_cast<int *>(smem_raw + draw_off), *const sDep = sWin + B, *const sTgt = sDep + B, *const sOrig = sTgt + B,
+               *const sPrev = sOrig + B;
+    for (int i = tid; i < 624; i += DRAW_THREADS) sMT[i] = c.mt[i];
+    int idx = c.st->idx, lo = c.st->lo;
+    const int dl = keep_unselected ? k : B;
+    __syncthreads();
+    for (int it = it0; it < it1; ++it) {
+        const int L = c.L0 - lo;  // >= B: the plan refused the call otherwise
+        // ---- the B draws and their targets: step t swaps window positions t and t + w % (L - t)
+        for (int done = 0; done < B;) {  // at most B / 624 + 2 rounds
+            if (idx >= 624) {
+                draw_mt_refill(sMT);
+                idx = 0;
+            }
+            const int n = 624 - idx < B - done ? 624 - idx : B - done;
+            for (int j = tid; j < n; j += DRAW_THREADS) {
+                const int t = done + j;
+                sTgt[t] = t + (int)(mt_temper(sMT[idx + j]) % (unsigned)(L - t));
+            }
+            idx += n, done += n;
+        }
+        if (tid == 0) sInWin = 0;
+        lds_barrier();
+        // ---- the window and the outside targets' values, all loads in flight together
+        int tg[DRAW_WPT], wv[DRAW_WPT], ov[DRAW_WPT];
+#pragma unroll
+        for (int q = 0; q < DRAW_WPT; ++q) {
+            const int t = tid + DRAW_THREADS * q;
+            tg[q] = WIDE || q == 0 ? (t < B ? sTgt[t] : -1) : -1;
+        }
+#pragma unroll
+        for (int q = 0; q < DRAW_WPT; ++q) {
+            const int t = tid + DRAW_THREADS * q;
+            wv[q] = tg[q] >= 0 ? c.r[(size_t)lo + t] : 0;
+            ov[q] = tg[q] >= B ? c.r[(size_t)lo + tg[q]] : 0;
+        }
+        unsigned last = 0;  // bit q: no later step has the outside target of step t_q -- this step's value stays there
+#pragma unroll
+        for (int q = 0; q < DRAW_WPT; ++q) {
+            const int t = tid + DRAW_THREADS * q;
+            if (tg[q] < 0) continue;
+            int prev = -1;
+            bool l = tg[q] >= B;
+            if (l) {
+                for (int u = 0; u < B; ++u) {
+                    const int tu = sTgt[u];
+                    if (tu == tg[q] && u < t) prev = u;
+                    if (tu == tg[q] && u > t) l = false;
+                }
+            } else {
+                sInWin = 1;
+            }
+            last |= l ? 1u << q : 0u;
+            sWin[t] = wv[q], sDep[t] = wv[q], sOrig[t] = ov[q], sPrev[t] = prev;
+        }
+        lds_barrier();
+        // ---- the swap sequence.  No target inside the window (nearly always when L >> B): the steps only meet at shared outside
+        // targets -- step t takes what the step before it left there (that step's own window value), else what was there.
+        // Otherwise one thread walks the B steps in order.
+        if (sInWin == 0) {
+#pragma unroll
+            for (int q = 0; q < DRAW_WPT; ++q) {
+                const int t = tid + DRAW_THREADS * q;
+                if (tg[q] < 0) continue;
+                const int p = sPrev[t];
+                sWin[t] = p >= 0 ? sDep[p] : sOrig[t];
+            }
+        } else if (tid == 0) {
+            for (int t = 0; t < B; ++t) {
+                const int j = sTgt[t], mine = sWin[t];
+                if (j < B) {
+                    sWin[t] = sWin[j];
+                    sWin[j] = mine;
+                } else {
+                    const int p = sPrev[t];
+                    sWin[t] = p >= 0 ? sDep[p] : sOrig[t];
+                    sDep[t] = mine;
+                }
+            }
+        }
+        lds_barrier();
+#pragma unroll
+        for (int q = 0; q < DRAW_WPT; ++q) {
+            const int t = tid + DRAW_THREADS * q;
+            if (last >> q & 1u) c.r[(size_t)lo + tg[q]] = sDep[t];  // the displaced values
+        }
+        // ---- score, rank, commit: the batch is sWin[0 .. B)
+        mi_select_stage<W>(ss, c.P, c.pairs, c.SN, c.Sa, c.Sb, c.sc, W ? c.w : nullptr);
+        mi_select_body<W, WIDE>(ss, c.asg, c.D, c.C, c.P, c.pairs, sWin, 0, nullptr, B, k, mode, c.Nc, c.ac, c.bc, c.SN, c.Sa, c.Sb, c.phi,
+                                c.sc, nullptr, c.S + (size_t)it * k, c.G + (size_t)it * k, nullptr,
+                                c.tr_pos ? c.tr_pos + (size_t)it * k : nullptr, c.tr_ids ? c.tr_ids + (size_t)it * B : nullptr,
+                                c.tr_sc ? c.tr_sc + (size_t)it * B : nullptr, 0, nullptr, 1, W ? c.w : nullptr);
+        // ---- shrink: the unselected ids, in batch order, to r[lo + k .. lo + B)
+        if (keep_unselected && k < B) {
+            const int *sPos = WIDE ? sel_wide(smem_raw, sel_layout(B, c.P, c.D, k, mode), B).pos : ss.pos;
+            for (int b = tid; b < B; b += DRAW_THREADS) sPrev[b] = 0;
+            lds_barrier();
+            for (int r = tid; r < k; r += DRAW_THREADS) sPrev[sPos[r]] = 1;
+            lds_barrier();
+#pragma unroll
+            for (int q = 0; q < DRAW_WPT; ++q) {
+                const int t = tid + DRAW_THREADS * q;
+                if (tg[q] < 0 || sPrev[t]) continue;
+                int rank = 0;
+                for (int u = 0; u < t; ++u) rank += sPrev[u] ? 0 : 1;
+                c.r[(size_t)lo + k + rank] = sWin[t];
+            }
+        }
+        lo += dl;
+        __syncthreads();  // the tables, the running sums and the candidates this iteration stored: the next one reads them
+    }
+    for (int i = tid; i < 624; i += DRAW_THREADS) c.mt[i] = sMT[i];
+    if (tid == 0) c.st->idx = idx, c.st->lo = lo;
+}
+
 __global__ void k_i64_to_i32(const long long *__restrict__ in, int *__restrict__ out, long long n)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2191,6 +2373,7 @@ struct acav_mi {
     DevBuf chunk_desc;                         // descriptor array of a multi-chunk run (lead handle)
     DevBuf chunk_blocks;                       // workgroup -> descriptor table of acav_mi_run_exact_multi (lead handle)
     DevBuf lane_states, ring, polys;           // MT19937 lanes of the single-chunk greedy (MtStream)
+    DevBuf draw_mt;                            // the draw sampler's generator block [624] and its DrawState (acav_mi_run_draw)
     DevBuf lnk, lf;   // ln k and ln k! tables of the `ami` / `nmi` scores and of subset scoring (mi_ensure_log_tables)
     int64_t log_kmax = -1;  // the tables hold k = 0 .. log_kmax
     int measure = 0;  // exact greedy: 0 = calc_MI, 1 = calc_AMI, 2 = calc_NMI, 3 = constant, 4 = FM, 5 = Rand, 6 = ARI
@@ -3136,6 +3319,139 @@ ACAV_EXPORT int acav_mi_run_greedy_multi(acav_mi **mis, int nchunks, const int64
         ACAV_TRY(run_greedy_legacy(mis[c], candidates[c], L[c], start ? start[c] : nullptr, ns[c], subset[c], B, k, keep_unselected,
                                    f.iters[(size_t)c], f.draws[(size_t)c], rngs[c], S_out[c], GAIN_out[c],
                                    n_selected ? n_selected + c : nullptr, n_iters ? n_iters + c : nullptr, TiledExtras()));
+    }
+    return ACAV_OK;
+}
+
+// ------------------------------------------------------------------------------ the draw sampler (batch.sampler=draw)
+// The plan of a call: the shape from the arguments, ACAV_DRAW_GROUP from the environment (read on every call: the tests change it).
+static DrawForm draw_form(const GreedyShape &s)
+{
+    const char *v = getenv("ACAV_DRAW_GROUP");
+    return draw_pick_form(s, v ? atoi(v) : 0);
+}
+
+static int draw_refuse(const DrawForm &f)
+{
+    ACAV_REQUIRE(f.refusal != GREEDY_SHORT_LIST, ACAV_ERANGE,
+                 "chunk %d: %lld candidates left < batch_size %d before the subset is full (batch.py:143-150 raises here)",
+                 f.refused_chunk, (long long)f.short_l, f.B);
+    ACAV_REQUIRE(f.refusal != GREEDY_LDS, ACAV_EINVAL,
+                 "batch_size %d x %d clusterings (x %d pairs) needs %zu bytes of LDS: more than a workgroup has (%zu); lower batch_size",
+                 f.B, f.dmax, f.pmax, f.smem + DRAW_STATIC_LDS, SEL_LDS_PER_WG);
+    return ACAV_OK;
+}
+
+// What acav_mi_run_draw launches for a shape, without a device.  The layout of form: include/acav_hip.h.
+ACAV_EXPORT int acav_mi_draw_form(int nchunks, const int64_t *L, const int64_t *subset, int B, int k, int keep_unselected,
+                                  int64_t max_iters, int pmax, int dmax, int weighted, int64_t *form)
+{
+    ACAV_REQUIRE(L && subset && form && nchunks > 0, ACAV_EINVAL, "NULL argument");
+    ACAV_REQUIRE(B > 0 && B <= SEL_WIDEB && k > 0 && k <= B && pmax > 0 && dmax > 0 && (int64_t)B * pmax <= SEL_MAXBP, ACAV_EINVAL,
+                 "batch_size %d / selection_size %d / pairs %d / clusterings %d out of range", B, k, pmax, dmax);
+    for (int c = 0; c < nchunks; ++c)
+        ACAV_REQUIRE(L[c] > 0 && L[c] <= 0x7fffffffll && subset[c] >= 0, ACAV_EINVAL, "chunk %d: bad sizes", c);
+    const DrawForm f = draw_form({nchunks, L, subset, B, k, keep_unselected != 0, max_iters, pmax, dmax, weighted != 0});
+    const bool ok = f.refusal == GREEDY_OK;
+    const int64_t head[16] = {ok ? ACAV_OK : f.refusal == GREEDY_SHORT_LIST ? ACAV_ERANGE : ACAV_EINVAL, f.refusal, f.refused_chunk,
+                              f.short_l, f.dl, f.wide, ok ? f.sel_mode : 0, ok ? (int64_t)f.smem : 0, f.group, DRAW_GROUP,
+                              ok ? f.launches : 0, ok ? f.iters_max : 0, ok ? (int64_t)f.sel_smem : 0, DRAW_THREADS, 0, 0};
+    for (int i = 0; i < 16; ++i) form[i] = head[i];
+    for (int c = 0; c < nchunks; ++c)
+        form[16 + c] = ok ? f.iters[(size_t)c] : 0, form[16 + nchunks + c] = ok ? f.draws[(size_t)c] : 0;
+    return ACAV_OK;
+}
+
+ACAV_EXPORT int acav_mi_run_draw(acav_mi **mis, int nchunks, const int64_t *const *candidates, const int64_t *L,
+                                 const int64_t *const *start, const int *ns, const int64_t *subset, int B, int k, int keep_unselected,
+                                 acav_rng **rngs, int64_t *const *S_out, double *const *GAIN_out, int64_t *n_selected,
+                                 int64_t *n_iters, int64_t *const *trace_ids, double *const *trace_scores, int32_t *const *trace_pos,
+                                 int64_t max_iters)
+{
+    ACAV_REQUIRE(mis && nchunks > 0 && candidates && L && ns && subset && rngs && S_out && GAIN_out, ACAV_EINVAL, "NULL argument");
+    ACAV_REQUIRE(B > 0 && B <= SEL_WIDEB && k > 0 && k <= B, ACAV_EINVAL,
+                 "batch_size %d / selection_size %d out of range (1 <= selection_size <= batch_size <= %d)", B, k, SEL_WIDEB);
+    acav_mi *lead = mis[0];
+    ACAV_REQUIRE(lead, ACAV_EINVAL, "handle is NULL");
+    GreedyShape s{nchunks, L, subset, B, k, keep_unselected != 0, max_iters, 1, 1, false};
+    for (int c = 0; c < nchunks; ++c) {
+        acav_mi *mi = mis[c];
+        ACAV_TRY(check_chunk_args(c, mi, candidates[c], L[c], start ? start[c] : nullptr, ns[c], subset[c], rngs[c], S_out[c], GAIN_out[c]));
+        ACAV_REQUIRE(L[c] <= 0x7fffffffll, ACAV_EINVAL, "chunk %d: lists of 2^31 candidates or more are not supported", c);
+        ACAV_REQUIRE(mi->ctx.device == lead->ctx.device, ACAV_EINVAL, "chunk %d lives on another device", c);
+        ACAV_REQUIRE((int64_t)B * mi->P <= SEL_MAXBP, ACAV_EINVAL, "chunk %d: batch_size %d x %d pairs exceeds B*P <= %d", c, B, mi->P,
+                     SEL_MAXBP);
+        for (int e = 0; e < c; ++e)
+            ACAV_REQUIRE(mis[e] != mi && rngs[e] != rngs[c], ACAV_EINVAL, "chunks must not share a handle or a generator");
+        s.pmax = mi->P > s.pmax ? mi->P : s.pmax;
+        s.dmax = mi->D > s.dmax ? mi->D : s.dmax;
+        s.weighted = s.weighted || mi->weighted;
+    }
+    // every chunk is planned before anything changes: a refused call leaves the tables, the outputs and the generators alone
+    const DrawForm f = draw_form(s);
+    ACAV_TRY(draw_refuse(f));
+    ACAV_HIP_TRY(hipSetDevice(lead->ctx.device));
+    hipStream_t st = lead->ctx.stream;
+    std::vector<DrawChunk> desc((size_t)nchunks);
+    std::vector<TiledExtras> ex((size_t)nchunks);
+    std::vector<unsigned> mtbuf((size_t)nchunks * 626);  // per chunk: the block, then DrawState {lo, idx}
+    for (int c = 0; c < nchunks; ++c) {
+        acav_mi *mi = mis[c];
+        const int64_t itc = f.iters[(size_t)c];
+        mi->pst_valid = false;  // the batch greedy changes the tables without the pair sums
+        ACAV_HIP_TRY(hipStreamSynchronize(mi->ctx.stream));  // whatever the handle was doing on its own stream is over
+        if (!is_device_ptr(candidates[c])) ACAV_TRY(mi->stage.ensure(sizeof(int64_t) * (size_t)L[c]));  // before add_samples uses it
+        if (ns[c]) ACAV_TRY(acav_mi_add_samples(mi, start[c], ns[c]));  // batch.py:215
+        ACAV_HIP_TRY(hipStreamSynchronize(mi->ctx.stream));
+        TiledExtras &e = ex[(size_t)c];
+        e.trace_ids = trace_ids ? trace_ids[c] : nullptr;
+        e.trace_scores = trace_scores ? trace_scores[c] : nullptr;
+        e.trace_pos = trace_pos ? trace_pos[c] : nullptr;
+        ACAV_TRY(mi->A0.ensure(sizeof(int) * (size_t)L[c]));  // before the conversion: ensure() does not copy
+        ACAV_TRY(ids_to_device32(mi, candidates[c], L[c], mi->stage, mi->A0, st));
+        ACAV_TRY(mi->S.ensure(sizeof(long long) * (size_t)(itc * k + 1)));
+        ACAV_TRY(mi->G.ensure(sizeof(double) * (size_t)(itc * k + 1)));
+        if (e.trace_pos) ACAV_TRY(mi->tr_pos.ensure(sizeof(int) * (size_t)(itc * k + 1)));
+        if (e.trace_ids) ACAV_TRY(mi->tr_ids.ensure(sizeof(long long) * (size_t)(itc * B + 1)));
+        if (e.trace_scores) ACAV_TRY(mi->tr_sc.ensure(sizeof(double) * (size_t)(itc * B + 1)));
+        unsigned *hb = mtbuf.data() + (size_t)c * 626;
+        int idx = 0;
+        ACAV_TRY(acav_rng_get_state(rngs[c], hb, &idx));
+        hb[624] = 0u, hb[625] = (unsigned)idx;
+        ACAV_TRY(mi->draw_mt.ensure(sizeof(unsigned) * 626));
+        ACAV_HIP_TRY(hipMemcpyAsync(mi->draw_mt.p, hb, sizeof(unsigned) * 626, hipMemcpyHostToDevice, st));
+        DrawChunk &d = desc[(size_t)c];
+        d.r = mi->A0.as<int>(), d.mt = mi->draw_mt.as<unsigned>(), d.st = reinterpret_cast<DrawState *>(mi->draw_mt.as<unsigned>() + 624);
+        d.asg = mi->asg.as<int>(), d.pairs = mi->pairs.as<int>();
+        d.Nc = mi->Nc.as<int>(), d.ac = mi->ac.as<int>(), d.bc = mi->bc.as<int>();
+        d.SN = mi->SN.as<double>(), d.Sa = mi->Sa.as<double>(), d.Sb = mi->Sb.as<double>();
+        d.phi = mi->phi.as<double>(), d.sc = mi->scalars.as<MiScalars>();
+        d.S = mi->S.as<long long>(), d.G = mi->G.as<double>();
+        d.tr_pos = e.trace_pos ? mi->tr_pos.as<int>() : nullptr;
+        d.tr_ids = e.trace_ids ? mi->tr_ids.as<long long>() : nullptr;
+        d.tr_sc = e.trace_scores ? mi->tr_sc.as<double>() : nullptr;
+        d.w = mi_weights(mi);
+        d.L0 = (int)L[c], d.iters = (int)itc, d.D = mi->D, d.C = mi->C, d.P = mi->P;
+    }
+    ACAV_TRY(lead->chunk_desc.ensure(sizeof(DrawChunk) * (size_t)nchunks));
+    ACAV_HIP_TRY(hipMemcpyAsync(lead->chunk_desc.p, desc.data(), sizeof(DrawChunk) * (size_t)nchunks, hipMemcpyHostToDevice, st));
+    auto kn = f.wide ? (f.weighted ? k_mi_draw<true, true> : k_mi_draw<false, true>)
+                     : (f.weighted ? k_mi_draw<true, false> : k_mi_draw<false, false>);
+    if (f.smem > 48 * 1024)
+        ACAV_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.smem));
+    for (int64_t g0 = 0; g0 < f.iters_max; g0 += f.group)  // at most f.group iterations per launch; chunks that are over return at once
+        hipLaunchKernelGGL(kn, dim3((unsigned)nchunks), dim3(DRAW_THREADS), f.smem, st, lead->chunk_desc.as<DrawChunk>(), (int)g0, f.group, B,
+                           k, f.sel_mode, keep_unselected ? 1 : 0, draw_lds_off(f.sel_smem));
+    ACAV_HIP_TRY(hipGetLastError());
+    for (int c = 0; c < nchunks; ++c) {
+        ACAV_TRY(read_back(mis[c], st, f.iters[(size_t)c], subset[c], B, k, S_out[c], GAIN_out[c], ex[(size_t)c],
+                           n_selected ? n_selected + c : nullptr, n_iters ? n_iters + c : nullptr));
+        ACAV_HIP_TRY(hipMemcpyAsync(mtbuf.data() + (size_t)c * 626, mis[c]->draw_mt.p, sizeof(unsigned) * 626, hipMemcpyDeviceToHost, st));
+    }
+    ACAV_HIP_TRY(hipStreamSynchronize(st));
+    for (int c = 0; c < nchunks; ++c) {  // every generator continues on the host where its chunk stopped drawing
+        const unsigned *hb = mtbuf.data() + (size_t)c * 626;
+        ACAV_TRY(acav_rng_set_state(rngs[c], hb, (int)hb[625]));
     }
     return ACAV_OK;
 }

@@ -443,3 +443,57 @@ inline GreedyGroup greedy_group_grids(const GreedyForm &f, int64_t g0, long long
     }
     return g;
 }
+
+// ================================================================================================ the draw sampler
+// batch.sampler=draw (acav_mi_run_draw, k_mi_draw in acav_mi.hip): per iteration only the first B steps of randperm's swap loop.
+// One workgroup per chunk runs the iterations as a loop inside the kernel; a launch runs at most DRAW_GROUP of them (at a few us
+// each: tens of ms per launch, however long the list), ACAV_DRAW_GROUP=<n> lowers that for the tests.
+constexpr int DRAW_GROUP = 4096;
+constexpr int DRAW_THREADS = 256;
+// dynamic LDS behind the selection's: win, dep, tgt, orig, prev [B] i32 each (the swap sequence of one iteration)
+constexpr unsigned DRAW_ARRAYS = 5;
+constexpr size_t DRAW_STATIC_LDS = sizeof(SelSharedW) + 624 * sizeof(unsigned) + 64;  // + the generator block and a flag, rounded up
+ACAV_FORM_HD inline unsigned draw_lds_off(size_t sel_smem) { return ((unsigned)sel_smem + 15u) & ~15u; }
+ACAV_FORM_HD inline size_t draw_smem_bytes(size_t sel_smem, int B) { return (size_t)draw_lds_off(sel_smem) + 4u * DRAW_ARRAYS * (size_t)B; }
+
+struct DrawForm {
+    int refusal = GREEDY_OK, refused_chunk = -1;  // GREEDY_SHORT_LIST (ACAV_ERANGE) or GREEDY_LDS (ACAV_EINVAL)
+    int64_t short_l = -1;
+    int nchunks = 0, B = 0, k = 0, pmax = 1, dmax = 1;
+    bool keep_unselected = false, wide = false, weighted = false;
+    int64_t dl = 0;  // the window start moves by this much per iteration: k (keep_unselected) or B
+    int sel_mode = 0;
+    size_t sel_smem = 0, smem = 0;  // the selection's dynamic LDS, and the launch's (with the swap arrays)
+    int group = DRAW_GROUP;         // iterations per launch
+    int64_t iters_max = 0, launches = 0;
+    std::vector<int64_t> iters, draws;  // per chunk; draws = iters * B
+};
+// group_env: ACAV_DRAW_GROUP as a number (<= 0: not set); values above DRAW_GROUP do not raise it
+inline DrawForm draw_pick_form(const GreedyShape &s, int group_env)
+{
+    DrawForm f;
+    f.nchunks = s.nchunks, f.B = s.B, f.k = s.k, f.pmax = s.pmax, f.dmax = s.dmax;
+    f.keep_unselected = s.keep_unselected, f.weighted = s.weighted;
+    f.dl = s.keep_unselected ? s.k : s.B;
+    f.wide = s.B > SEL_MAXB;
+    f.group = group_env > 0 && group_env < DRAW_GROUP ? group_env : DRAW_GROUP;
+    f.iters.assign((size_t)s.nchunks, 0), f.draws.assign((size_t)s.nchunks, 0);
+    for (int c = 0; c < s.nchunks; ++c) {
+        const GreedyPlan gp = greedy_plan(s.L[c], s.subset[c], s.B, s.k, f.dl, s.max_iters);  // the permutation loop's condition
+        if (gp.short_l >= 0) {
+            f.refusal = GREEDY_SHORT_LIST, f.refused_chunk = c, f.short_l = gp.short_l;
+            return f;
+        }
+        f.iters[(size_t)c] = gp.iters, f.draws[(size_t)c] = gp.iters * s.B;
+        f.iters_max = gp.iters > f.iters_max ? gp.iters : f.iters_max;
+    }
+    f.sel_mode = sel_mode(s.B, s.pmax, s.k);
+    f.sel_smem = sel_smem_bytes(s.B, s.pmax, s.dmax, s.k, f.sel_mode);
+    f.smem = draw_smem_bytes(f.sel_smem, s.B);
+    if (f.smem + DRAW_STATIC_LDS > SEL_LDS_PER_WG) {
+        f.refusal = GREEDY_LDS;
+        return f;
+    }
+    f.launches = (f.iters_max + f.group - 1) / f.group;
+    return f;
+}

@@ -12,7 +12,7 @@ from ..config import SUBSET_DEFAULTS, merge, parse_cli
 from .exclude import check_exclude
 from .run import compare_measures, lockstep_supported, merge_all_csvs, reduce_all_pkls, run_chunks, run_single
 from .run_contrastive import merge_contrastive, run_chunks_contrastive, run_single_contrastive
-from .run_greedy import check_celf_ratio, check_weight_type
+from .run_greedy import batch_sampler, check_celf_ratio, check_sampler, check_weight_type
 from .run_pca import is_pca_measure, run_chunks_pca, run_single_pca
 
 
@@ -57,6 +57,7 @@ def check_run(args):
     check_weight_type(args.measure_name, args.clustering.weight_type)
     check_celf_ratio(args.measure_name, args.get('celf_ratio', 0))
     check_exclude(args.measure_name, args.get('exclude_path'))
+    check_sampler(args.measure_name, batch_sampler(args))
     # a lockstep width means something to a chunked run only; the pca measures refuse it without a chunk_size too
     if int(args.computation.concurrent_chunks or 1) > 1 and (args.chunk_size is not None or pca):
         lockstep_supported(args.measure_name, args.get('celf_ratio', 0))

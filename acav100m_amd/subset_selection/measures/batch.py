@@ -69,13 +69,39 @@ def compose_scores(stats):
     return dict(zip(SCORE_NAMES, out.tolist()))
 
 
+# how batch_mi draws an iteration's batch (batch.sampler)
+SAMPLERS = ('permutation', 'draw')
+
+
+def draw_form(L, subset, B, k, keep_unselected, max_iters=-1, pmax=1, dmax=2, weighted=False):
+    """what a sampler='draw' selection of this shape launches, without a GPU (acav_mi_draw_form): L, subset: one entry per
+    chunk.  -> dict; a refused shape has 'code' != 0 (-5: a list falls below a batch; -1: the LDS does not fit)."""
+    L = np.ascontiguousarray(np.atleast_1d(L), dtype=np.int64)
+    sub = np.ascontiguousarray(np.atleast_1d(subset), dtype=np.int64)
+    n = len(L)
+    form = np.zeros(16 + 2 * n, np.int64)
+    _lib.check(_lib.load_library().acav_mi_draw_form(n, _lib.ptr(L), _lib.ptr(sub), int(B), int(k), int(bool(keep_unselected)),
+                                                      int(max_iters), int(pmax), int(dmax), int(bool(weighted)), _lib.ptr(form)))
+    names = ('code', 'refusal', 'chunk', 'left', 'step', 'wide', 'mode', 'lds', 'group', 'group_max', 'launches', 'iters_max',
+             'sel_lds', 'threads')
+    out = {name: int(form[i]) for i, name in enumerate(names)}
+    out['iters'], out['draws'] = form[16:16 + n].tolist(), form[16 + n:16 + 2 * n].tolist()
+    return out
+
+
 class EfficientBatchMI:
     """ this implementation requires the users to use the same ncentroids for all clusterings """
     _takes_weights = True  # the MI score multiplies by the pair weights; the measures that override it ignore them
 
     def __init__(self, assignments, measure_type='mutual_info', average_method='arithmetic',
                  ncentroids=20, batch_size=1, selection_size=1, device='cpu', keep_unselected=False,
-                 generator=None, **kwargs):
+                 generator=None, sampler='permutation', **kwargs):
+        """sampler (ours): 'permutation' (default) shuffles the whole candidate list every iteration on the reference's generator
+        stream; 'draw' performs only the first batch_size steps of that shuffle (acav_mi_run_draw) -- the same distribution of
+        every batch for O(batch_size) instead of O(candidates) work per iteration, on a generator stream of its own."""
+        if sampler not in SAMPLERS:
+            raise ValueError("sampler={!r}: choose from {}".format(sampler, list(SAMPLERS)))
+        self.sampler = sampler
         self.average_method = average_method.lower()
         self.ncentroids = int(ncentroids)
         self.assignments = np.ascontiguousarray(assignments, dtype=np.int64)  # V x D
@@ -229,12 +255,18 @@ class EfficientBatchMI:
         tr_sc = np.empty((niters, B), np.float64) if record_trace else None
         tr_pos = np.empty((niters, k), np.int32) if record_trace else None
         fp = None if forced_pos is None else np.ascontiguousarray(forced_pos, dtype=np.int32)
+        if self.sampler == 'draw' and fp is not None:
+            raise ValueError("forced_pos replays a trace of the permutation sampler: sampler='draw' has no teacher forcing")
         nsel, nit = C.c_int64(0), C.c_int64(0)
         greedy_start_time = time.time()
-        _lib.check(_lib._lib.acav_mi_run_greedy(
-            self._h, _lib.ptr(cand), len(cand), _lib.ptr(start), len(start), int(subset_size), B, k,
-            int(bool(self.keep_unselected)), self._generator.handle, _lib.ptr(S), _lib.ptr(G), C.byref(nsel),
-            C.byref(nit), _lib.ptr(tr_ids), _lib.ptr(tr_sc), _lib.ptr(tr_pos), _lib.ptr(fp), int(max_iters)))
+        if self.sampler == 'draw':
+            nsel, nit = self._run_draw([self], [subset_size], [start], [S], [G], [(tr_ids, tr_sc, tr_pos)], max_iters)[0]
+            nsel, nit = C.c_int64(nsel), C.c_int64(nit)
+        else:
+            _lib.check(_lib._lib.acav_mi_run_greedy(
+                self._h, _lib.ptr(cand), len(cand), _lib.ptr(start), len(start), int(subset_size), B, k,
+                int(bool(self.keep_unselected)), self._generator.handle, _lib.ptr(S), _lib.ptr(G), C.byref(nsel),
+                C.byref(nit), _lib.ptr(tr_ids), _lib.ptr(tr_sc), _lib.ptr(tr_pos), _lib.ptr(fp), int(max_iters)))
         elapsed = time.time() - greedy_start_time
         nit, nsel = nit.value, nsel.value
         if record_trace:
@@ -252,6 +284,30 @@ class EfficientBatchMI:
         print("Time Consumed: {} seconds".format(elapsed))
         return (S_list, GAIN, timelapse, LOOKUPS)
 
+
+    # ------------------------------------------------------------ sampler='draw': one chunk or several
+    @staticmethod
+    def _run_draw(measures, subset_sizes, starts, S, G, traces, max_iters):
+        """acav_mi_run_draw for the measures (a chunk each; they share B, k and keep_unselected), results into the S / G arrays
+        and the (ids, scores, pos) trace arrays (or Nones) of every chunk.  -> [(n_selected, n_iters)] per chunk."""
+        n = len(measures)
+        m0 = measures[0]
+
+        def parr(ptrs):
+            return (C.c_void_p * n)(*[p.value if isinstance(p, C.c_void_p) else p for p in ptrs])
+
+        cands = [m.candidate_ids for m in measures]
+        L = np.array([len(c) for c in cands], np.int64)
+        ns = np.array([len(s) for s in starts], np.int32)
+        sub = np.array([int(s) for s in subset_sizes], np.int64)
+        nsel, nit = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        _lib.check(_lib._lib.acav_mi_run_draw(
+            parr([m._h for m in measures]), n, parr([_lib.ptr(c) for c in cands]), _lib.ptr(L),
+            parr([_lib.ptr(s) if len(s) else None for s in starts]), _lib.ptr(ns), _lib.ptr(sub), int(m0.B), int(m0.k),
+            int(bool(m0.keep_unselected)), parr([m._generator.handle for m in measures]), parr([_lib.ptr(a) for a in S]),
+            parr([_lib.ptr(a) for a in G]), _lib.ptr(nsel), _lib.ptr(nit), parr([_lib.ptr(t[0]) for t in traces]),
+            parr([_lib.ptr(t[1]) for t in traces]), parr([_lib.ptr(t[2]) for t in traces]), int(max_iters)))
+        return [(int(a), int(b)) for a, b in zip(nsel, nit)]
 
     # ------------------------------------------------------------ several chunks in lockstep
     @staticmethod
@@ -289,10 +345,16 @@ class EfficientBatchMI:
         sub = np.array([int(s) for s in subset_sizes], np.int64)
         nsel = np.zeros(n, np.int64)
         nit = np.zeros(n, np.int64)
+        samplers = {getattr(m, 'sampler', 'permutation') for m in measures}
+        assert len(samplers) == 1, "chunks run together must share batch.sampler"
         t0 = time.time()
-        _lib.check(_lib._lib.acav_mi_run_greedy_multi(h_arr, n, c_arr, _lib.ptr(L), s_arr, _lib.ptr(ns), _lib.ptr(sub), B, k,
-                                                      int(bool(m0.keep_unselected)), r_arr, S_arr, G_arr, _lib.ptr(nsel),
-                                                      _lib.ptr(nit)))
+        if samplers == {'draw'}:  # one launch of n workgroups, a chunk each
+            for i, (a, b) in enumerate(EfficientBatchMI._run_draw(measures, subset_sizes, starts, S, G, [(None,) * 3] * n, -1)):
+                nsel[i], nit[i] = a, b
+        else:
+            _lib.check(_lib._lib.acav_mi_run_greedy_multi(h_arr, n, c_arr, _lib.ptr(L), s_arr, _lib.ptr(ns), _lib.ptr(sub), B, k,
+                                                          int(bool(m0.keep_unselected)), r_arr, S_arr, G_arr, _lib.ptr(nsel),
+                                                          _lib.ptr(nit)))
         elapsed = time.time() - t0
         if verbose:
             print("Time Consumed: {} seconds for {} chunks in lockstep".format(elapsed, n))

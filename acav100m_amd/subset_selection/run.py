@@ -14,7 +14,7 @@ from .. import shards as io
 from .chunks import plan_chunks, save_chunk
 from .exclude import apply_exclude, read_exclude
 from .measures import get_measure
-from .run_greedy import _prepare, _run_greedy, run_greedy
+from .run_greedy import _prepare, _run_greedy, batch_sampler, check_sampler, run_greedy
 
 
 def load_data(shard_paths, metas_path, verbose=False):
@@ -106,7 +106,9 @@ def run_chunks(args):
     plan, chunk_args = plan_chunks(args)
     mine = plan.mine
     width = int(chunk_args.computation.concurrent_chunks or 1)
-    if width > 1:
+    # batch.sampler=draw is on a generator stream of its own anyway: its chunks ALWAYS draw from their own generators
+    # (random_seed + 1 + chunk number), so the files do not depend on the width -- width chunks are one launch of width workgroups
+    if width > 1 or check_sampler(chunk_args.measure_name, batch_sampler(chunk_args)) == 'draw':
         return _run_chunks_lockstep(args, chunk_args, plan, width)
     written = []
     # computation.load_async (chunk.py:119-120,197-226): the next chunk's shards are read and parsed by a host

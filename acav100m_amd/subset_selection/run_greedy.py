@@ -16,6 +16,7 @@ in lockstep (run.py).
 import numpy as np
 
 from .measures import get_measure
+from .measures.batch import SAMPLERS  # batch.sampler: how batch_mi draws an iteration's batch
 from .pairing import get_cluster_pairing
 
 # the measures whose score the pair weights scale (correspondence_retrieval: EfficientMI / EfficientMemMI / EfficientBatchMI);
@@ -43,6 +44,24 @@ def check_celf_ratio(measure_name, celf_ratio):
     return ratio
 
 
+def check_sampler(measure_name, sampler):
+    """-> the sampler's name ('permutation' for None); ValueError for an unknown one, and for 'draw' with any measure but
+    batch_mi (the exact measures draw nothing, the others have no batch)"""
+    name = 'permutation' if sampler is None else sampler
+    if name not in SAMPLERS:
+        raise ValueError("batch.sampler={!r}: choose from {}".format(sampler, list(SAMPLERS)))
+    if name == 'draw' and str(measure_name).lower() != 'batch_mi':
+        raise ValueError("batch.sampler='draw' needs measure_name=batch_mi, not {!r}: only its greedy loop draws batches"
+                         .format(measure_name))
+    return name
+
+
+def batch_sampler(args):
+    """batch.sampler of a configuration; the key has no entry in the defaults and reads as None ('permutation') when missing"""
+    batch = args.batch
+    return batch.get('sampler') if hasattr(batch, 'get') else getattr(batch, 'sampler', None)
+
+
 class _Plan:
     """sizes of one selection, derived once from the assignment matrix and the `batch` options"""
 
@@ -64,6 +83,7 @@ class _Plan:
 def _prepare(args, assignments, clustering_types, subset_size, subset_ratio, measure_name='mi',
              cluster_pairing='combination', shuffle_candidates=True, verbose=False, generator=None, weight_type=None, celf_ratio=0):
     """-> (measure ready to run, start_indices, subset_size)"""
+    sampler = check_sampler(measure_name, batch_sampler(args))  # before any device work, like the two below
     check_weight_type(measure_name, weight_type)
     check_celf_ratio(measure_name, celf_ratio)  # checked here, before any device work; it is run_greedy's keyword, not init's
     plan = _Plan(args, assignments, subset_size, subset_ratio)
@@ -73,6 +93,8 @@ def _prepare(args, assignments, clustering_types, subset_size, subset_ratio, mea
                    device=args.computation.device, keep_unselected=args.batch.keep_unselected)
     if generator is not None:
         options['generator'] = generator
+    if sampler != 'permutation':
+        options['sampler'] = sampler
     measure = get_measure(measure_name)(assignments, **options)
     order = plan.candidate_order(shuffle_candidates)
     head, rest = order[:1], order[1:]  # a singleton start: it seeds the tables, it is never selected (batch.py:205-206)
