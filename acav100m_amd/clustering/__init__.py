@@ -7,4 +7,4 @@ from . import kmeanspp  # noqa: F401
 from . import silhouette  # noqa: F401
 from .silhouette import sample_indices, silhouette_samples, summarise  # noqa: F401
 from . import dedup  # noqa: F401
-from .dedup import nearest_earlier  # noqa: F401
+from .dedup import nearest_earlier, nearest_in  # noqa: F401

@@ -3,7 +3,8 @@
 `python cli.py evaluate ... --clustering.cached_epoch=<e | [e0,e1,...]>` (ours, clustering/evaluate.py): judge the cached
 clusterings of such a run on the same feature shards.
 `python cli.py dedup ... --clustering.cached_epoch=<e> --dedup.threshold=<t> --dedup.out_path=<csv>` (ours, clustering/dedup.py):
-near-duplicates inside the clusters of one view of such a run."""
+near-duplicates inside the clusters of one view of such a run; with `--dedup.against_path=<brace glob .pkl>
+--dedup.against_meta_path=<dir> [--dedup.blocking=none|cluster]` the copies of a held-out set's clips in the (streamed) pool."""
 import sys
 
 from .. import shards as io

@@ -29,7 +29,27 @@ front-end into one device buffer (only that view has to be held in one piece, th
 calc_best and runs acav_rows_neardup on it.  dedup.out_path (overwritten) holds the flagged rows in global row order, one line
 each: shard_name,filename,partner_shard_name,partner_filename,similarity (repr of the float) -- a file `subset_selection/cli.py
 run --exclude_path=` accepts.  dedup.report_path receives summarise's dictionary as json plus view, epoch, feature_path and
-clusters_path.  Writes nothing into the cluster run's directory.  One process, one GPU."""
+clusters_path.  Writes nothing into the cluster run's directory.  One process, one GPU.
+
+Against a held-out set (nearest_in, KMeans.near_duplicates_in, acav_rows_crossdup): does the pool contain the evaluation sets,
+do the new shards copy what is already curated?  For every row of a STREAMED pool the largest cosine to any row of a RESIDENT
+held-out set y [m, d] and that row:
+  E_i        = { j : ly_j = lx_i, ||y_j|| > 0 }  (no blocking: every non-zero row of y)
+  best[i]    = max over E_i of cos(x_i, y_j);  partner[i] = the lowest such j, a position in y
+  best[i] = -inf, partner[i] = -1 when E_i is empty or x_i is all zero
+A pool row's answer depends on no other pool row, so the pool is taken one row group at a time and no [N, d] buffer of it
+exists: only the held-out set has to fit the device in one piece.  A clip that is in both sets is flagged -- it IS a copy of a
+held-out clip; remove it from the held-out shards if that is not wanted.  tests/_crossdup_np.py restates the definition.
+
+    python -m acav100m_amd.clustering.cli dedup <the keys above> --dedup.against_path=<brace glob .pkl> \\
+        --dedup.against_meta_path=<dir> [--dedup.blocking=none|cluster]
+
+blocking=none (default) compares every pool row with every held-out row: no pair is missed, the cost is n m (printed before the
+sweep).  blocking=cluster compares a pool row only with the held-out rows calc_best gives the same label: the in-cluster rule,
+for a held-out set too large for n m (an earlier release); a bitwise copy always gets its source's label.  Both sets go
+through the front-end of the cache, so a threshold read off an in-cluster run's similarity grid means the same here.  The csv
+has the same layout, the partner columns naming the HELD-OUT clip; the json is summarise_against's dictionary plus view, epoch,
+feature_path, clusters_path, against_path, blocking, pool_zero_rows and against_zero_rows."""
 import csv
 import json
 import numbers
@@ -57,6 +77,30 @@ def nearest_earlier(x, labels, k=None, device="cuda"):
     lib = _lib.load_library()
     dev = keep.device.index if on_gpu else _device_index(device)
     _lib.check(lib.acav_rows_neardup(dev, xp, n, d, _lib.ptr(lab), int(k), _lib.ptr(best), _lib.ptr(partner), None))
+    return best, partner
+
+
+def nearest_in(x, y, labels_x=None, labels_y=None, k=None, device="cuda"):
+    """(best float64 [n], partner int64 [n]) of the rows of x [n, d] against the held-out rows y [m, d]: acav_rows_crossdup.
+    labels_x [n] and labels_y [m] in [0, k) (k=None: the largest label of either + 1) block the pairs; both None: every pair.
+    x, y and the labels: numpy or torch, host or device; a device y is used where it lies, not copied."""
+    keep_x, xp, n, x_gpu = _as_f32_2d(x)
+    d = int(keep_x.shape[1])
+    keep_y, yp, m, y_gpu = _as_f32_2d(y, width=d)
+    if (labels_x is None) != (labels_y is None):
+        raise ValueError("labels_x and labels_y go together: both, or neither (no blocking)")
+    lab_x = lab_y = None
+    if labels_x is not None:
+        lab_x, lab_y = _labels(labels_x, n), _labels(labels_y, m)
+        if k is None:
+            k = 1 + max(int(lab_x.max()) if n else 0, int(lab_y.max()) if m else 0)
+    elif k is None:
+        k = 1
+    best, partner = np.empty(n, np.float64), np.empty(n, np.int64)
+    lib = _lib.load_library()
+    dev = keep_y.device.index if y_gpu else keep_x.device.index if x_gpu else _device_index(device)
+    _lib.check(lib.acav_rows_crossdup(dev, xp, n, yp, m, d, _lib.ptr(lab_x), _lib.ptr(lab_y), int(k), _lib.ptr(best),
+                                      _lib.ptr(partner), None))
     return best, partner
 
 
@@ -88,11 +132,64 @@ def summarise(best, partner, labels, k, threshold):
     }
 
 
+def summarise_against(best, partner, labels_x, hist_y, k, threshold, m):
+    """the report of one run against a held-out set of m rows (pure numpy).  labels_x [n] and hist_y [k] (the held-out rows per
+    cluster): blocking=cluster; both None and k = 1: no blocking.  n, m, K, threshold, flagged and flagged_share,
+    flagged_by_cluster [K] (blocked only), similarity_counts as in summarise, pairs = sum over the clusters of (pool rows) x
+    (held-out rows), n m when unblocked, and without_candidates: the pool rows whose cluster holds no non-zero held-out row --
+    counted as the rows of the clusters in which no pool row has a partner (a cluster all of whose pool rows are all-zero
+    counts too: pool_zero_rows of the verb's report tells)"""
+    best, partner, k, m = np.asarray(best, np.float64), np.asarray(partner, np.int64), int(k), int(m)
+    n = int(best.shape[0])
+    blocked = labels_x is not None
+    if blocked != (hist_y is not None) or (not blocked and k != 1):
+        raise ValueError("labels_x and hist_y go together; without them k is 1")
+    lab = np.asarray(labels_x, np.int64) if blocked else np.zeros(n, np.int64)
+    hist = np.asarray(hist_y, np.int64) if blocked else np.array([m], np.int64)
+    if partner.shape != (n,) or lab.shape != (n,) or hist.shape != (k,) or int(hist.sum()) != m:
+        raise ValueError("best {}, partner {}, labels_x {} and hist_y {} (m = {}) do not belong together".format(
+            best.shape, partner.shape, lab.shape, hist.shape, m))
+    flagged = flag(best, threshold)
+    hist_x = np.bincount(lab, minlength=k)
+    served = np.bincount(lab[partner >= 0], minlength=k) > 0  # the clusters in which a pool row found a partner
+    report = OrderedDict([
+        ('n', n), ('m', m), ('K', k), ('threshold', float(threshold)),
+        ('flagged', int(flagged.sum())), ('flagged_share', float(flagged.sum() / n) if n else float('nan'))])
+    if blocked:
+        report['flagged_by_cluster'] = [int(c) for c in np.bincount(lab[flagged], minlength=k)]
+    report['similarity_counts'] = OrderedDict((repr(g), int((best >= g).sum())) for g in SIMILARITY_GRID)
+    report['pairs'] = int(sum(int(a) * int(b) for a, b in zip(hist_x, hist)))
+    report['without_candidates'] = int(hist_x[~served].sum())
+    return report
+
+
+def check_against_options(opts):
+    """the keys of the against mode -> (against_path, against_meta_path, blocking); against_path None: the in-cluster dedup.
+    Pure: no device, no file"""
+    opts = opts or {}
+    path, meta, blocking = opts.get('against_path'), opts.get('against_meta_path'), opts.get('blocking')
+    if path is None:
+        for key, value in (('against_meta_path', meta), ('blocking', blocking)):
+            if value is not None:
+                raise ValueError("dedup.{} is only valid with --dedup.against_path=<brace glob of the held-out feature "
+                                 "shards>".format(key))
+        return None, None, None
+    if not isinstance(path, str) or not path:
+        raise ValueError("dedup.against_path must be a brace glob of feature .pkl shards, not {!r}".format(path))
+    if meta is None:
+        raise ValueError("dedup.against_path needs --dedup.against_meta_path=<dir>: the metadata of the held-out shards")
+    blocking = 'none' if blocking is None else blocking
+    if blocking not in ('none', 'cluster'):
+        raise ValueError("dedup.blocking must be 'none' or 'cluster', not {!r}".format(blocking))
+    return path, str(meta), blocking
+
+
 def check_options(opts, views=None, epoch=None):
     """the `dedup` options -> (threshold, view, out_path, report_path).  Pure: no device, no file.  views: the names
     "<model_key>/<layer>" the cache holds, once it is known (None: dedup.view is only checked for its form); epoch:
     clustering.cached_epoch, when given exactly one epoch is required"""
     opts = opts or {}
+    check_against_options(opts)
     thr = opts.get('threshold')
     if thr is None:
         raise ValueError("dedup needs --dedup.threshold=<t in (0, 1]>: the cosine from which a row counts as a duplicate of an "
@@ -160,6 +257,9 @@ def dedup(args):
     km.args = None  # one process, one GPU, whatever run wrote the cache
     km = km.to(dev)
     K = km.centers.shape[0]
+    against = check_against_options(opts)
+    if against[0] is not None:
+        return _dedup_against(args, against, paths, sizes, view_dims, v, dt, km, threshold, view, epoch, out_path, report_path)
 
     n_total = sum(int(sizes[p.stem]) for p in paths)
     need = 4 * n_total * d
@@ -192,20 +292,127 @@ def dedup(args):
 
     report = summarise(best, partner, labels, K, threshold)
     report.update(view=view, epoch=int(epoch), feature_path=str(args.data.path), clusters_path=str(args.data.output.path))
+    out_path = _write_csv(out_path, best, partner, threshold, (shard_name, filename), (shard_name, filename))
+    print("dedup: view {} epoch {}: {} of {} rows ({:.3f}%) have an earlier row of their cluster at cosine >= {!r}; {} zero rows; "
+          "wrote {}".format(view, epoch, report['flagged'], report['n'], 100.0 * report['flagged_share'], threshold,
+                            report['zero_rows'], out_path))
+    print("rows with best >= " + "  ".join("{}: {}".format(g, c) for g, c in report['similarity_counts'].items()))
+    _write_report(report_path, report)
+    return report
+
+
+def _host(labels):
+    return labels.cpu().numpy() if hasattr(labels, "cpu") else np.asarray(labels)
+
+
+def _write_csv(out_path, best, partner, threshold, names, partner_names):
+    """the flagged rows in row order: shard_name,filename of the row, then of its partner, then repr(best); overwritten"""
     out_path = Path(out_path)
     out_path.parent.mkdir(parents=True, exist_ok=True)
     with open(out_path, 'w', newline='') as f:
         writer = csv.writer(f)
         for i in np.flatnonzero(flag(best, threshold)):
             j = int(partner[i])
-            writer.writerow([shard_name[i], filename[i], shard_name[j], filename[j], repr(float(best[i]))])
-    print("dedup: view {} epoch {}: {} of {} rows ({:.3f}%) have an earlier row of their cluster at cosine >= {!r}; {} zero rows; "
-          "wrote {}".format(view, epoch, report['flagged'], report['n'], 100.0 * report['flagged_share'], threshold,
-                            report['zero_rows'], out_path))
-    print("rows with best >= " + "  ".join("{}: {}".format(g, c) for g, c in report['similarity_counts'].items()))
+            writer.writerow([names[0][i], names[1][i], partner_names[0][j], partner_names[1][j], repr(float(best[i]))])
+    return out_path
+
+
+def _write_report(report_path, report):
     if report_path is not None:
         report_path = Path(report_path)
         report_path.parent.mkdir(parents=True, exist_ok=True)
         with open(report_path, 'w') as f:
             json.dump(report, f, indent=1)
+
+
+def _dedup_against(args, against, paths, sizes, view_dims, v, dt, km, threshold, view, epoch, out_path, report_path):
+    """the against mode of the verb: the held-out view resident in one device buffer, one pass over the pool's row groups"""
+    import torch
+    from .. import shards as io
+    from .frontend import FrontEnd
+    from .row_groups import open_row_groups, probe_shards
+    against_path, against_meta, blocking = against
+    K = km.centers.shape[0] if blocking == 'cluster' else 1
+    hpaths = [Path(p) for p in sorted(io.brace_expand(against_path))]
+    hsizes = io.shard_sizes_from_meta(hpaths, Path(against_meta), use_cache=True)
+    hpaths = [p for p in hpaths if p.stem in hsizes]
+    m_total = sum(int(hsizes[p.stem]) for p in hpaths)
+    if m_total < 1:
+        raise ValueError("the held-out set is empty: no shard of {} has rows in the metadata of {}".format(against_path, against_meta))
+    _probe, hdims = probe_shards(args, hpaths)
+    if hdims is None:
+        raise ValueError("none of the {} held-out shards of {} could be read".format(len(hpaths), against_path))
+    if v not in hdims:
+        raise ValueError("the held-out shards hold no view {} (they have {})".format(view, ', '.join('/'.join(key[1:]) for key in hdims)))
+    if hdims[v] != view_dims[v]:
+        raise ValueError("view {} has {} columns in the held-out shards and {} in the pool's".format(view, hdims[v], view_dims[v]))
+    fronts = [FrontEnd.from_attrs(dt), FrontEnd.from_attrs(dt)]  # one per set: a front-end tallies the rows it meets
+    for front in fronts:
+        front.check_width(v, view_dims[v])
+    d = fronts[0].width_out(view_dims[v])
+
+    n_total = sum(int(sizes[p.stem]) for p in paths)
+    pool, held = open_row_groups(args, paths, sizes, view_dims), open_row_groups(args, hpaths, hsizes, hdims)
+    need = 4 * m_total * d
+    beside = (pool.budget // 2 if pool.streamed else 4 * n_total * view_dims[v]) + (held.budget // 2 if held.streamed else 0)
+    free, _total = torch.cuda.mem_get_info()
+    if need + beside > free:  # only the held-out view in one piece, refused before the pass starts
+        raise ValueError("dedup holds view {} of the held-out set in one piece: {} rows x {} columns need {} bytes on the device "
+                         "({} more for the row groups), {} are free; compare against a part of the held-out shards, or a "
+                         "projected view".format(view, m_total, d, need, beside, free))
+    pool.add_front_ends({v: fronts[0]})
+    held.add_front_ends({v: fronts[1]})
+
+    y, base, hshard, hfile = None, 0, [], []
+    for _gi, table, rows in held.iterate(views={v}):
+        part = rows[v]
+        if y is None:
+            y = part if not held.streamed else torch.empty((m_total, d), dtype=torch.float32, device=part.device)
+        if held.streamed:
+            if base + part.shape[0] > m_total:
+                raise RuntimeError("the held-out shards deliver more rows than their metadata states ({})".format(m_total))
+            y[base:base + part.shape[0]] = part
+        base += part.shape[0]
+        hshard.extend(table.shard_name)
+        hfile.extend(table.filename)
+    if y is None or base != y.shape[0] or base != len(hfile):
+        raise RuntimeError("the held-out shards delivered {} rows, their metadata states {}: fix the metadata or drop the unreadable "
+                           "shards from the list".format(base, m_total))
+    against_zero = int((torch.count_nonzero(y, dim=1) == 0).sum())
+    labels_y = hist_y = None
+    if blocking == 'cluster':
+        labels_y, _ = km.calc_best(y, need_mean=False)  # once: a row's label is a pure function of the row and the state
+        hist_y = np.bincount(_host(labels_y), minlength=K)
+    pairs = n_total * m_total if hist_y is None else None
+    print("dedup: view {} epoch {}: {} pool rows against {} held-out rows, blocking={}{}".format(
+        view, epoch, n_total, m_total, blocking, ": {} pairs".format(pairs) if pairs is not None else ""))
+
+    best, partner, labels_x, pool_zero, shard_name, filename = [], [], [], 0, [], []
+    for _gi, table, rows in pool.iterate(views={v}):
+        part = rows[v]
+        lab = None
+        if blocking == 'cluster':
+            lab, _ = km.calc_best(part, need_mean=False)
+            labels_x.append(_host(lab))
+        b, p = nearest_in(part, y, lab, labels_y, k=K)
+        best.append(b)
+        partner.append(p)
+        pool_zero += int((torch.count_nonzero(part, dim=1) == 0).sum())
+        shard_name.extend(table.shard_name)
+        filename.extend(table.filename)
+    best, partner = np.concatenate(best), np.concatenate(partner)
+    if len(best) != n_total or len(filename) != n_total:
+        raise RuntimeError("the shards delivered {} rows, their metadata states {}: fix the metadata or drop the unreadable shards "
+                           "from the list".format(len(best), n_total))
+    labels_x = np.concatenate(labels_x) if blocking == 'cluster' else None
+
+    report = summarise_against(best, partner, labels_x, hist_y, K, threshold, m_total)
+    report.update(view=view, epoch=int(epoch), feature_path=str(args.data.path), clusters_path=str(args.data.output.path),
+                  against_path=str(against_path), blocking=blocking, pool_zero_rows=pool_zero, against_zero_rows=against_zero)
+    out_path = _write_csv(out_path, best, partner, threshold, (shard_name, filename), (hshard, hfile))
+    print("dedup: view {} epoch {}: {} of {} rows ({:.3f}%) have a held-out row at cosine >= {!r} ({} pairs compared, {} rows "
+          "without candidates); wrote {}".format(view, epoch, report['flagged'], report['n'], 100.0 * report['flagged_share'],
+                                                  threshold, report['pairs'], report['without_candidates'], out_path))
+    print("rows with best >= " + "  ".join("{}: {}".format(g, c) for g, c in report['similarity_counts'].items()))
+    _write_report(report_path, report)
     return report

@@ -326,6 +326,21 @@ class KMeans:
             labels, _ = self.calc_best(batch, need_mean=False)
         return nearest_earlier(batch, labels, k=self._shape[0], device="cuda:{}".format(self._device))
 
+    def near_duplicates_in(self, batch, other, blocking='cluster'):
+        """For every row of batch the largest cosine to a row of the held-out rows `other` and that row (clustering/dedup.py,
+        acav_rows_crossdup) -> (best float64 [b], partner int64 [b], a position in other; -inf and -1 for a row without one).
+        blocking='cluster': only the rows of other that calc_best(., need_mean=False) gives the same label; 'none': all."""
+        from .dedup import nearest_in
+        self._require_handle()
+        if blocking not in ('cluster', 'none'):
+            raise ValueError("blocking must be 'cluster' or 'none', not {!r}".format(blocking))
+        lab_x = lab_y = None
+        if blocking == 'cluster':
+            lab_x, _ = self.calc_best(batch, need_mean=False)
+            lab_y, _ = self.calc_best(other, need_mean=False)
+        return nearest_in(batch, other, lab_x, lab_y, k=self._shape[0] if blocking == 'cluster' else 1,
+                          device="cuda:{}".format(self._device))
+
     def train_stats(self):
         """(bulk training calls that ran as one persistent launch, launches that gave up and were re-run per step)"""
         a, b = C.c_int64(0), C.c_int64(0)

@@ -193,6 +193,12 @@ CLUSTERING_DEFAULTS = {
     #   dedup.view         "<model_key>/<layer>": the view whose rows are compared; required when the cache holds several
     #   dedup.out_path     required: the csv of the flagged rows, shard_name,filename,partner_shard_name,partner_filename,similarity
     #   dedup.report_path  optional: the summary as json
+    #   dedup.against_path       a brace glob of feature .pkl shards: the held-out set.  Switches the mode: every pool row is
+    #                            compared with the rows of THAT set (decontamination; new shards against curated ones), the pool
+    #                            streams, only the held-out view has to fit the device.  Without it: the in-cluster dedup
+    #   dedup.against_meta_path  required with against_path: the metadata directory of the held-out shards
+    #   dedup.blocking           only with against_path: none (default; every pair, n m of them) or cluster (a pool row meets
+    #                            only the held-out rows that calc_best gives its label)
     'debug': False,
 }
 

@@ -26,6 +26,14 @@
 // chain wherever the pair sits in a tile, the maximum is taken in ascending position whatever the tile size, the workgroup, the
 // other clusters or host / device / unaligned input (the guarded load path feeds the same values into the same chain).  No
 // floating-point atomics; the same call gives the same bytes every time.
+//
+// Against a held-out set (acav_rows_crossdup; dedup.nearest_in, `dedup --dedup.against_path`): the same arithmetic over TWO
+// arrays.  For every row of a pool piece x the largest cosine to a row of the held-out set y with its label and that row.  Both
+// arrays are label-sorted; per sorted pool position the run [ylo, yhi) of its label in y's sorted order replaces the triangle's
+// bounds, and a tile walks the column blocks of y that cover [ylo of its first row, yhi of its last row): a rectangle per
+// label, one contiguous range per tile, possibly empty.  k_crossdup is k_neardup's stage loop with the columns taken from y;
+// crossdup_tiles builds its tile list from the two histograms.  A pool row's result depends on no other pool row, so the pool
+// may come in pieces of any length: only y has to be resident.
 #include <algorithm>
 #include <cmath>
 #include <numeric>
@@ -286,6 +294,20 @@ int use_device(int device, int *cus)
     return ACAV_OK;
 }
 
+// perm [n]: the positions 0 ... n - 1 by label, stably
+void sort_by_label(const std::vector<int64_t> &lab, int64_t n, int k, int *perm)
+{
+    if ((int64_t)k <= 4 * n + 1024) {  // a counting sort, n + k steps (a million rows: a few ms against the merge sort's 100)
+        std::vector<int64_t> at((size_t)k + 1, 0);
+        for (int64_t i = 0; i < n; ++i) ++at[(size_t)lab[(size_t)i] + 1];
+        for (int b = 0; b < k; ++b) at[(size_t)b + 1] += at[(size_t)b];
+        for (int64_t i = 0; i < n; ++i) perm[at[(size_t)lab[(size_t)i]]++] = (int)i;
+    } else {  // the same permutation without a table of k entries: k is not limited
+        std::iota(perm, perm + n, 0);
+        std::stable_sort(perm, perm + n, [&](int a, int b) { return lab[(size_t)a] < lab[(size_t)b]; });
+    }
+}
+
 template <int RT>
 int launch(const NdPlan &plan, bool vec, hipStream_t st, const float *x, int d, int n, const int *perm, const int *rstart,
            const double *nrm, const NdTile *tiles, double *best, int64_t *partner)
@@ -300,6 +322,201 @@ int launch(const NdPlan &plan, bool vec, hipStream_t st, const float *x, int d, 
         hipLaunchKernelGGL((k_neardup<RT, false>), dim3((unsigned)plan.tiles), dim3(256), plan.lds, st, x, d, n, perm, rstart, nrm,
                            tiles, best, partner);
     ACAV_HIP_TRY(hipGetLastError());
+    return ACAV_OK;
+}
+
+// ---- acav_rows_crossdup: the pool piece x [n] against the held-out set y [m]
+
+// the tiles of two label histograms: tile t holds the sorted pool positions [t QM, min(n, (t + 1) QM)) and walks the column
+// blocks of y's sorted order that cover [ystart[label of its first row], yend[label of its last row]) -- both arrays being
+// label-sorted that is one contiguous range, which holds the run of every row of the tile; it is empty (0 blocks, first block
+// floor(ystart / 64)) when none of the tile's labels has a held-out row.  list (NULL: skipped): the tiles by descending blocks,
+// ties by ascending t.  Returns the plan.
+NdPlan crossdup_tiles(const int64_t *hist_x, const int64_t *hist_y, int k, int d, int cus, std::vector<NdTile> *list)
+{
+    (void)d;
+    int64_t n = 0, m = 0;
+    for (int b = 0; b < k; ++b) n += hist_x[b], m += hist_y[b];
+    NdPlan p;
+    p.rt = neardup_rt(n, cus);
+    const int64_t qm = (int64_t)ND_QM * p.rt;
+    p.tiles = (n + qm - 1) / qm;
+    p.blocks = 0;
+    if (list) list->clear(), list->reserve((size_t)p.tiles);
+    int b = 0;
+    int64_t xs = 0, ys = 0;  // the starts of label b's runs in x and in y; b: the label of the tile's first row
+    for (int64_t t = 0; t < p.tiles; ++t) {
+        const int64_t q0 = t * qm, q1 = std::min(n, q0 + qm);
+        while (xs + hist_x[b] <= q0) xs += hist_x[b], ys += hist_y[b], ++b;
+        int e = b;  // the label of the tile's last row, xe and ye the ends of its runs
+        int64_t xe = xs + hist_x[b], ye = ys + hist_y[b];
+        while (xe < q1) ++e, xe += hist_x[e], ye += hist_y[e];
+        const int64_t cb0 = ys / ND_CN, blocks = ye > ys ? (ye + ND_CN - 1) / ND_CN - cb0 : 0;
+        p.blocks += blocks;
+        if (list) list->push_back(NdTile{(int)q0, (int)(q1 - q0), (int)cb0, (int)blocks});
+    }
+    if (list) std::stable_sort(list->begin(), list->end(), [](const NdTile &a, const NdTile &c) { return a.blocks > c.blocks; });
+    p.lds = neardup_lds(p.rt);
+    // the sorted positions of both arrays and the two bounds per pool row, the norms, the tile list, (best, partner)
+    p.scratch = sizeof(int) * (3 * (size_t)n + (size_t)m) + sizeof(double) * (size_t)(n + m) + sizeof(NdTile) * (size_t)p.tiles +
+                (sizeof(double) + sizeof(int64_t)) * (size_t)n;
+    return p;
+}
+
+// permx[q] / permy[c]: the input position of sorted position q of x / c of y; ylo[q], yhi[q]: the run of q's label in y's sorted
+// order; nrmx / nrmy: ||.||^2 by sorted position.  tiles[b]: the tile workgroup b takes.  best / partner: by INPUT position of
+// x, partner an input position of y.  k_neardup's stages, operands and accumulators; positions past 2^31 - 64 are compared
+// unsigned
+template <int RT, bool VEC>
+__global__ __launch_bounds__(256, 2) void k_crossdup(const float *__restrict__ x, const float *__restrict__ y, int d, int m,
+                                                     const int *__restrict__ permx, const int *__restrict__ permy,
+                                                     const int *__restrict__ ylo, const int *__restrict__ yhi,
+                                                     const double *__restrict__ nrmx, const double *__restrict__ nrmy,
+                                                     const NdTile *__restrict__ tiles, double *__restrict__ best,
+                                                     int64_t *__restrict__ partner)
+{
+    constexpr int QM = ND_QM * RT;
+    extern __shared__ double nd_smem[];
+    double *cosv = nd_smem;                          // [QM][ND_CS], after the last chunk of a block
+    float *qs = reinterpret_cast<float *>(nd_smem);  // [QM][ND_ST]
+    float *cs = qs + QM * ND_ST;                     // [ND_CN][ND_ST]
+
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int fr = lane & 15, fq = lane >> 4;  // fragment row (A) / column (B) and k index of this lane
+    const int lq = t & 7, lr = t >> 3;         // this thread stages columns 4 lq .. 4 lq + 3 of the rows lr + 32 u
+    const NdTile tile = tiles[blockIdx.x];
+    const unsigned q0 = (unsigned)tile.q0, q1 = q0 + (unsigned)tile.rows, um = (unsigned)m;  // q1 <= n
+    const double inf = __builtin_inf();
+
+    // the pool rows this thread stages, and the ones whose results it holds
+    const float *qrow[2 * RT];
+    bool qok[2 * RT];
+#pragma unroll
+    for (int u = 0; u < 2 * RT; ++u) {
+        const unsigned q = q0 + lr + 32 * u;
+        qok[u] = q < q1;
+        qrow[u] = x + (size_t)permx[qok[u] ? q : q0] * d;
+    }
+    double qn[RT][4];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {  // C/D of the f64 MFMA: column = lane & 15, row = (lane >> 4) + 4 * register
+            const unsigned q = q0 + wave * 16 * RT + rt * 16 + fq + 4 * r;
+            qn[rt][r] = nrmx[q < q1 ? q : q0];
+        }
+    // the walk: thread t < QM owns pool row t of the tile; a zero row has no partner
+    const unsigned my_pos = q0 + t;
+    const bool walker = t < QM && my_pos < q1;
+    const bool alive = walker && nrmx[my_pos] > 0.0;
+    const unsigned my_lo = alive ? (unsigned)ylo[my_pos] : 0u, my_hi = alive ? (unsigned)yhi[my_pos] : 0u;  // its columns
+    double top = -inf;
+    int arg = -1;
+
+    for (int cb = tile.cb0; cb < tile.cb0 + tile.blocks; ++cb) {
+        const unsigned c0 = (unsigned)cb * ND_CN;  // c0 < yhi of the tile's last row <= m
+        const float *crow[2];
+        bool cok[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const unsigned c = c0 + lr + 32 * u;
+            cok[u] = c < um;
+            crow[u] = y + (size_t)permy[cok[u] ? c : c0] * d;
+        }
+        f64x4 acc[RT][4];
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+            for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = f64x4{0.0, 0.0, 0.0, 0.0};
+        float4 pq[2 * RT], pc[2];  // the next chunk, in flight while the current one is multiplied
+#pragma unroll
+        for (int u = 0; u < 2 * RT; ++u) pq[u] = nd_fetch<VEC>(qrow[u], d, 4 * lq);
+#pragma unroll
+        for (int u = 0; u < 2; ++u) pc[u] = nd_fetch<VEC>(crow[u], d, 4 * lq);
+        for (int j0 = 0; j0 < d; j0 += ND_DK) {
+            __syncthreads();  // the previous stage has been read (and the previous block's cosine tile walked)
+#pragma unroll
+            for (int u = 0; u < 2 * RT; ++u)
+                *reinterpret_cast<float4 *>(&qs[(lr + 32 * u) * ND_ST + 4 * lq]) = nd_mask(pq[u], qok[u], d, j0 + 4 * lq);
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+                *reinterpret_cast<float4 *>(&cs[(lr + 32 * u) * ND_ST + 4 * lq]) = nd_mask(pc[u], cok[u], d, j0 + 4 * lq);
+            __syncthreads();
+            if (j0 + ND_DK < d) {
+#pragma unroll
+                for (int u = 0; u < 2 * RT; ++u) pq[u] = nd_fetch<VEC>(qrow[u], d, j0 + ND_DK + 4 * lq);
+#pragma unroll
+                for (int u = 0; u < 2; ++u) pc[u] = nd_fetch<VEC>(crow[u], d, j0 + ND_DK + 4 * lq);
+            }
+#pragma unroll
+            for (int kk = 0; kk < ND_DK / 4; ++kk) {
+                double a[RT], b[4];
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt) a[rt] = (double)qs[(wave * 16 * RT + rt * 16 + fr) * ND_ST + kk * 4 + fq];
+#pragma unroll
+                for (int ct = 0; ct < 4; ++ct) b[ct] = (double)cs[(ct * 16 + fr) * ND_ST + kk * 4 + fq];
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                    for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[rt], b[ct], acc[rt][ct], 0, 0, 0);
+            }
+        }
+        __syncthreads();  // every wave has read the last stage: the cosine tile goes over it
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct) {
+            const unsigned c = c0 + ct * 16 + fr;
+            const double cn = nrmy[c < um ? c : um - 1];
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    cosv[(wave * 16 * RT + rt * 16 + fq + 4 * r) * ND_CS + ct * 16 + fr] =
+                        cn > 0.0 ? acc[rt][ct][r] / sqrt(qn[rt][r] * cn) : -inf;  // a zero row is never a partner
+        }
+        __syncthreads();
+        if (walker) {
+            const unsigned lo = my_lo > c0 ? my_lo : c0, hi = my_hi < c0 + ND_CN ? my_hi : c0 + ND_CN;
+            const double *mine = cosv + t * ND_CS;
+            for (unsigned c = lo; c < hi; ++c) {
+                const double v = mine[c - c0];
+                if (v > top) top = v, arg = (int)c;  // strict: the lowest position keeps a tie
+            }
+        }
+    }
+    if (walker) {
+        const size_t o = (size_t)permx[my_pos];
+        best[o] = top;
+        partner[o] = arg >= 0 ? (int64_t)permy[arg] : (int64_t)-1;
+    }
+}
+
+template <int RT>
+int launch_cross(const NdPlan &plan, bool vec, hipStream_t st, const float *x, const float *y, int d, int m, const int *permx,
+                 const int *permy, const int *ylo, const int *yhi, const double *nrmx, const double *nrmy, const NdTile *tiles,
+                 double *best, int64_t *partner)
+{
+    const void *fn = vec ? reinterpret_cast<const void *>(k_crossdup<RT, true>) : reinterpret_cast<const void *>(k_crossdup<RT, false>);
+    ACAV_HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)neardup_lds(RT)));
+    if (vec)
+        hipLaunchKernelGGL((k_crossdup<RT, true>), dim3((unsigned)plan.tiles), dim3(256), plan.lds, st, x, y, d, m, permx, permy, ylo,
+                           yhi, nrmx, nrmy, tiles, best, partner);
+    else
+        hipLaunchKernelGGL((k_crossdup<RT, false>), dim3((unsigned)plan.tiles), dim3(256), plan.lds, st, x, y, d, m, permx, permy, ylo,
+                           yhi, nrmx, nrmy, tiles, best, partner);
+    ACAV_HIP_TRY(hipGetLastError());
+    return ACAV_OK;
+}
+
+int check_hist(const int64_t *hist, int k, const char *what, int64_t *sum)
+{
+    int64_t n = 0;
+    for (int b = 0; b < k; ++b) {
+        ACAV_REQUIRE(hist[b] >= 0 && hist[b] <= ND_MAX_N, ACAV_EINVAL, "%s[%d] = %lld must be in [0, 2^31)", what, b, (long long)hist[b]);
+        n += hist[b];
+        ACAV_REQUIRE(n <= ND_MAX_N, ACAV_EINVAL, "%s holds 2^31 rows or more: positions are 32-bit", what);
+    }
+    ACAV_REQUIRE(n >= 1, ACAV_EINVAL, "%s holds no row", what);
+    *sum = n;
     return ACAV_OK;
 }
 
@@ -366,15 +583,7 @@ ACAV_EXPORT int acav_rows_neardup(int device, const float *x, int64_t n, int d, 
     // the positions by label, stably; per sorted position the start of its run; the label histogram for the tile list
     std::vector<int> host((size_t)(2 * n));
     int *perm = host.data(), *rstart = perm + n;
-    if ((int64_t)k <= 4 * n + 1024) {  // a counting sort, n + k steps (a million rows: a few ms against the merge sort's 100)
-        std::vector<int64_t> at((size_t)k + 1, 0);
-        for (int64_t i = 0; i < n; ++i) ++at[(size_t)lab[(size_t)i] + 1];
-        for (int b = 0; b < k; ++b) at[(size_t)b + 1] += at[(size_t)b];
-        for (int64_t i = 0; i < n; ++i) perm[at[(size_t)lab[(size_t)i]]++] = (int)i;
-    } else {  // the same permutation without a table of k entries: k is not limited
-        std::iota(perm, perm + n, 0);
-        std::stable_sort(perm, perm + n, [&](int a, int b) { return lab[(size_t)a] < lab[(size_t)b]; });
-    }
+    sort_by_label(lab, n, k, perm);
     std::vector<int64_t> runs;  // the histogram without its empty labels: the same tiles
     for (int64_t c = 0, first = 0; c < n; ++c) {
         if (c == 0 || lab[(size_t)perm[c]] != lab[(size_t)perm[c - 1]]) first = c, runs.push_back(0);
@@ -400,6 +609,136 @@ ACAV_EXPORT int acav_rows_neardup(int device, const float *x, int64_t n, int d, 
         ACAV_TRY(launch<2>(plan, vec, st, xd, d, (int)n, dperm, drstart, nrm.as<double>(), dtiles.as<NdTile>(), dbest, dpartner));
     else
         ACAV_TRY(launch<1>(plan, vec, st, xd, d, (int)n, dperm, drstart, nrm.as<double>(), dtiles.as<NdTile>(), dbest, dpartner));
+    if (!best_dev) ACAV_HIP_TRY(hipMemcpyAsync(best, obest.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
+    if (!partner_dev) ACAV_HIP_TRY(hipMemcpyAsync(partner, opartner.p, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+    ACAV_HIP_TRY(hipStreamSynchronize(st));
+    return ACAV_OK;
+}
+
+ACAV_EXPORT int acav_rows_crossdup_plan(const int64_t *hist_x, const int64_t *hist_y, int k, int d, int cus, int64_t *out,
+                                        int64_t *tiles, int64_t cap)
+{
+    ACAV_REQUIRE(hist_x && hist_y && out, ACAV_EINVAL, "NULL argument");
+    ACAV_REQUIRE(k >= 1 && d >= 1 && d <= ND_MAX_D && cus > 0, ACAV_EINVAL, "bad sizes");
+    int64_t n = 0, m = 0;
+    ACAV_TRY(check_hist(hist_x, k, "hist_x", &n));
+    ACAV_TRY(check_hist(hist_y, k, "hist_y", &m));
+    std::vector<NdTile> list;
+    const NdPlan p = crossdup_tiles(hist_x, hist_y, k, d, cus, tiles ? &list : nullptr);
+    ACAV_REQUIRE(!tiles || cap >= p.tiles, ACAV_EINVAL, "room for %lld tiles, the rows are cut into %lld", (long long)cap, (long long)p.tiles);
+    out[0] = (int64_t)ND_QM * p.rt, out[1] = p.tiles, out[2] = p.blocks, out[3] = p.tiles, out[4] = (int64_t)p.lds;
+    out[5] = (int64_t)p.scratch;
+    if (tiles)
+        for (int64_t t = 0; t < p.tiles; ++t) {
+            const NdTile &e = list[(size_t)t];
+            tiles[4 * t] = e.q0, tiles[4 * t + 1] = e.rows, tiles[4 * t + 2] = e.cb0, tiles[4 * t + 3] = e.blocks;
+        }
+    return ACAV_OK;
+}
+
+ACAV_EXPORT int acav_rows_crossdup(int device, const float *x, int64_t n, const float *y, int64_t m, int d, const int64_t *labels_x,
+                                   const int64_t *labels_y, int k, double *best, int64_t *partner, void *stream)
+{
+    ACAV_REQUIRE(x && y && best && partner, ACAV_EINVAL, "NULL argument");
+    ACAV_REQUIRE(n >= 1 && n <= ND_MAX_N, ACAV_EINVAL, "n=%lld must be in [1, 2^31): positions are 32-bit", (long long)n);
+    ACAV_REQUIRE(m >= 1 && m <= ND_MAX_N, ACAV_EINVAL, "m=%lld must be in [1, 2^31): positions are 32-bit", (long long)m);
+    ACAV_REQUIRE(d >= 1 && d <= ND_MAX_D, ACAV_EINVAL, "d=%d must be in [1, %d]", d, ND_MAX_D);
+    ACAV_REQUIRE(k >= 1, ACAV_EINVAL, "k=%d must be at least 1", k);
+    const bool blocked = labels_x != nullptr;
+    ACAV_REQUIRE(blocked == (labels_y != nullptr), ACAV_EINVAL, "labels_x and labels_y go together: both, or neither (no blocking)");
+    ACAV_REQUIRE(blocked || k == 1, ACAV_EINVAL, "k=%d without labels: no blocking is k = 1", k);
+    int cus = 0;
+    ACAV_TRY(use_device(device, &cus));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+
+    DevBuf stage_x, stage_y, stage_lx, stage_ly, bad, ints, nrm, dtiles, obest, opartner;
+    StreamDrain drain = {st};
+    const void *dx = nullptr, *dy = nullptr, *dlx = nullptr, *dly = nullptr;
+    const size_t total_x = (size_t)n * d, total_y = (size_t)m * d;
+    ACAV_TRY(to_device(x, sizeof(float) * total_x, stage_x, st, &dx));
+    ACAV_TRY(to_device(y, sizeof(float) * total_y, stage_y, st, &dy));
+    const float *xd = static_cast<const float *>(dx), *yd = static_cast<const float *>(dy);
+    // [0], [1] labels of x, of y out of range (the low words), [2], [3] values of x, of y that are not finite
+    ACAV_TRY(bad.ensure(sizeof(unsigned long long) * 4));
+    ACAV_HIP_TRY(hipMemsetAsync(bad.p, 0, sizeof(unsigned long long) * 4, st));
+    std::vector<int64_t> labx, laby;
+    if (blocked) {
+        ACAV_TRY(to_device(labels_x, sizeof(int64_t) * (size_t)n, stage_lx, st, &dlx));
+        ACAV_TRY(to_device(labels_y, sizeof(int64_t) * (size_t)m, stage_ly, st, &dly));
+        hipLaunchKernelGGL(k_nd_labels, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, st,
+                           static_cast<const int64_t *>(dlx), n, k, bad.as<unsigned>());
+        ACAV_HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_nd_labels, dim3((unsigned)std::min<int64_t>((m + 255) / 256, 4096)), dim3(256), 0, st,
+                           static_cast<const int64_t *>(dly), m, k, bad.as<unsigned>() + 2);
+        ACAV_HIP_TRY(hipGetLastError());
+        labx.resize((size_t)n), laby.resize((size_t)m);
+        ACAV_HIP_TRY(hipMemcpyAsync(labx.data(), dlx, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+        ACAV_HIP_TRY(hipMemcpyAsync(laby.data(), dly, sizeof(int64_t) * (size_t)m, hipMemcpyDeviceToHost, st));
+    }
+    hipLaunchKernelGGL(k_nd_finite, dim3((unsigned)std::min<size_t>((total_x + 255) / 256, (size_t)cus * 8)), dim3(256), 0, st, xd,
+                       total_x, bad.as<unsigned long long>() + 2);
+    ACAV_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_nd_finite, dim3((unsigned)std::min<size_t>((total_y + 255) / 256, (size_t)cus * 8)), dim3(256), 0, st, yd,
+                       total_y, bad.as<unsigned long long>() + 3);
+    ACAV_HIP_TRY(hipGetLastError());
+    unsigned long long nbad[4] = {0, 0, 0, 0};
+    ACAV_HIP_TRY(hipMemcpyAsync(nbad, bad.p, sizeof(nbad), hipMemcpyDeviceToHost, st));
+    ACAV_HIP_TRY(hipStreamSynchronize(st));
+    ACAV_REQUIRE(nbad[0] == 0, ACAV_EINVAL, "%llu of the %lld labels of x are outside [0, %d)", nbad[0], (long long)n, k);
+    ACAV_REQUIRE(nbad[1] == 0, ACAV_EINVAL, "%llu of the %lld labels of y are outside [0, %d)", nbad[1], (long long)m, k);
+    ACAV_REQUIRE(nbad[2] == 0, ACAV_EINVAL, "%llu of the %lld x %d values of x are not finite (inf or NaN)", nbad[2], (long long)n, d);
+    ACAV_REQUIRE(nbad[3] == 0, ACAV_EINVAL, "%llu of the %lld x %d values of y are not finite (inf or NaN)", nbad[3], (long long)m, d);
+
+    // both arrays' positions by label, stably; per sorted pool position the run of its label in y's sorted order; the two
+    // histograms over the labels that occur (in either array, ascending) for the tile list
+    std::vector<int> host((size_t)(3 * n + m));
+    int *permx = host.data(), *ylo = permx + n, *yhi = ylo + n, *permy = yhi + n;
+    std::vector<int64_t> hx, hy;
+    if (!blocked) {
+        std::iota(permx, permx + n, 0);
+        std::iota(permy, permy + m, 0);
+        std::fill(ylo, ylo + n, 0);
+        std::fill(yhi, yhi + n, (int)m);
+        hx.push_back(n), hy.push_back(m);
+    } else {
+        sort_by_label(labx, n, k, permx);
+        sort_by_label(laby, m, k, permy);
+        for (int64_t i = 0, j = 0; i < n || j < m;) {
+            const int64_t c = i < n && (j >= m || labx[(size_t)permx[i]] <= laby[(size_t)permy[j]]) ? labx[(size_t)permx[i]]
+                                                                                                    : laby[(size_t)permy[j]];
+            int64_t i1 = i, j1 = j;
+            while (i1 < n && labx[(size_t)permx[i1]] == c) ++i1;
+            while (j1 < m && laby[(size_t)permy[j1]] == c) ++j1;
+            std::fill(ylo + i, ylo + i1, (int)j);
+            std::fill(yhi + i, yhi + i1, (int)j1);
+            hx.push_back(i1 - i), hy.push_back(j1 - j);
+            i = i1, j = j1;
+        }
+    }
+    std::vector<NdTile> list;
+    const NdPlan plan = crossdup_tiles(hx.data(), hy.data(), (int)hx.size(), d, cus, &list);
+
+    const bool best_dev = is_device_ptr(best), partner_dev = is_device_ptr(partner);
+    ACAV_TRY(upload(ints, host.data(), sizeof(int) * host.size(), st));
+    ACAV_TRY(upload(dtiles, list.data(), sizeof(NdTile) * list.size(), st));
+    ACAV_TRY(nrm.ensure(sizeof(double) * (size_t)(n + m)));
+    if (!best_dev) ACAV_TRY(obest.ensure(sizeof(double) * (size_t)n));
+    if (!partner_dev) ACAV_TRY(opartner.ensure(sizeof(int64_t) * (size_t)n));
+    double *dbest = best_dev ? best : obest.as<double>();
+    int64_t *dpartner = partner_dev ? partner : opartner.as<int64_t>();
+    const int *dpermx = ints.as<int>(), *dylo = dpermx + n, *dyhi = dylo + n, *dpermy = dyhi + n;
+    double *nrmx = nrm.as<double>(), *nrmy = nrmx + n;
+    const bool vec = d % 4 == 0 && ((reinterpret_cast<uintptr_t>(xd) | reinterpret_cast<uintptr_t>(yd)) & 15) == 0;
+    hipLaunchKernelGGL(k_nd_norms, dim3((unsigned)n), dim3(64), 0, st, xd, d, dpermx, nrmx);
+    ACAV_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_nd_norms, dim3((unsigned)m), dim3(64), 0, st, yd, d, dpermy, nrmy);
+    ACAV_HIP_TRY(hipGetLastError());
+    if (plan.rt == 2)
+        ACAV_TRY(launch_cross<2>(plan, vec, st, xd, yd, d, (int)m, dpermx, dpermy, dylo, dyhi, nrmx, nrmy, dtiles.as<NdTile>(), dbest,
+                                 dpartner));
+    else
+        ACAV_TRY(launch_cross<1>(plan, vec, st, xd, yd, d, (int)m, dpermx, dpermy, dylo, dyhi, nrmx, nrmy, dtiles.as<NdTile>(), dbest,
+                                 dpartner));
     if (!best_dev) ACAV_HIP_TRY(hipMemcpyAsync(best, obest.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
     if (!partner_dev) ACAV_HIP_TRY(hipMemcpyAsync(partner, opartner.p, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, st));
     ACAV_HIP_TRY(hipStreamSynchronize(st));
