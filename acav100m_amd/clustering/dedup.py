@@ -49,7 +49,20 @@ sweep).  blocking=cluster compares a pool row only with the held-out rows calc_b
 for a held-out set too large for n m (an earlier release); a bitwise copy always gets its source's label.  Both sets go
 through the front-end of the cache, so a threshold read off an in-cluster run's similarity grid means the same here.  The csv
 has the same layout, the partner columns naming the HELD-OUT clip; the json is summarise_against's dictionary plus view, epoch,
-feature_path, clusters_path, against_path, blocking, pool_zero_rows and against_zero_rows."""
+feature_path, clusters_path, against_path, blocking, pool_zero_rows and against_zero_rows.
+
+Multi-probe (`--dedup.probes=m`, KMeans.probe_centers, acav_kmeans_probes, acav_rows_probedup): how large the price of the
+cluster borders is, and a switch that lowers it -- the inverted file's nprobe.  A row is compared with the rows of its own
+cluster and of the m - 1 centres next nearest to it (float64 distances, ties to the lower centre):
+  E_i(p)     = { j : l_j = probes[i][p], ||y_j|| > 0, and j < i in the in-cluster mode }
+  best[i]    = max over p < m and E_i(p) of cos(i, j);  partner[i] = the lowest such j that attains it, whatever its label
+m in [1, min(16, K)], default 1: the run of today, through acav_rows_neardup / acav_rows_crossdup, byte for byte.  Valid in the
+in-cluster mode and with --dedup.blocking=cluster (the pool still streams, the lists of a pool piece are computed per row
+group); refused with blocking=none, where there is nothing to probe.  The csv keeps its layout.  With m > 1 the report gains
+probes, pairs (compared) and flagged_by_probes [m]: entry p - 1 counts the rows whose best over their first p probed clusters
+reaches the threshold -- entry 0 is what probes=1 flags, and where the curve flattens a further probe no longer pays; the verb
+prints it under the similarity grid, so one run at a generous m is enough to pick m.  tests/_probedup_np.py restates both
+definitions."""
 import csv
 import json
 import numbers
@@ -65,9 +78,19 @@ from .silhouette import _labels
 SIMILARITY_GRID = (0.5, 0.6, 0.7, 0.8, 0.9, 0.95, 0.98, 0.99, 0.999, 0.9999)
 
 
-def nearest_earlier(x, labels, k=None, device="cuda"):
+def _probe_lists(probes, n):
+    """probes [n, m] (numpy or torch, host or device) as a contiguous int64 array the library reads, and m"""
+    shape = tuple(probes.shape) if hasattr(probes, "shape") else np.shape(probes)
+    if len(shape) != 2 or shape[0] != n:
+        raise ValueError("expected [{}, m] probe lists, got shape {}".format(n, shape))
+    return _labels(probes.reshape(-1) if hasattr(probes, "reshape") else np.asarray(probes, np.int64).reshape(-1), n * shape[1]), shape[1]
+
+
+def nearest_earlier(x, labels, k=None, device="cuda", probes=None, each=False):
     """(best float64 [n], partner int64 [n]) of x [n, d] with labels [n] in [0, k) (k=None: max label + 1): acav_rows_neardup.
-    x and labels: numpy or torch, host or device."""
+    x and labels: numpy or torch, host or device.  probes [n, m] (KMeans.probe_centers; -1: no such slot): the earlier rows of
+    the m probed clusters of every row instead of its own alone, acav_rows_probedup with y = x and before[i] = i; each=True
+    (with probes) adds best_each float64 [n, m], the best of every probed cluster on its own."""
     keep, xp, n, on_gpu = _as_f32_2d(x)
     d = int(keep.shape[1])
     lab = _labels(labels, n)
@@ -76,17 +99,30 @@ def nearest_earlier(x, labels, k=None, device="cuda"):
     best, partner = np.empty(n, np.float64), np.empty(n, np.int64)
     lib = _lib.load_library()
     dev = keep.device.index if on_gpu else _device_index(device)
-    _lib.check(lib.acav_rows_neardup(dev, xp, n, d, _lib.ptr(lab), int(k), _lib.ptr(best), _lib.ptr(partner), None))
-    return best, partner
+    if probes is None:
+        if each:
+            raise ValueError("each=True needs probes: without them there is one cluster per row")
+        _lib.check(lib.acav_rows_neardup(dev, xp, n, d, _lib.ptr(lab), int(k), _lib.ptr(best), _lib.ptr(partner), None))
+        return best, partner
+    lists, m = _probe_lists(probes, n)
+    best_each = np.empty((n, m), np.float64) if each else None
+    before = np.arange(n, dtype=np.int64)
+    _lib.check(lib.acav_rows_probedup(dev, xp, n, xp, n, d, _lib.ptr(lists), int(m), _lib.ptr(lab), _lib.ptr(before), int(k),
+                                      _lib.ptr(best), _lib.ptr(partner), _lib.ptr(best_each), None))
+    return (best, partner, best_each) if each else (best, partner)
 
 
-def nearest_in(x, y, labels_x=None, labels_y=None, k=None, device="cuda"):
+def nearest_in(x, y, labels_x=None, labels_y=None, k=None, device="cuda", probes_x=None, each=False):
     """(best float64 [n], partner int64 [n]) of the rows of x [n, d] against the held-out rows y [m, d]: acav_rows_crossdup.
     labels_x [n] and labels_y [m] in [0, k) (k=None: the largest label of either + 1) block the pairs; both None: every pair.
-    x, y and the labels: numpy or torch, host or device; a device y is used where it lies, not copied."""
+    x, y and the labels: numpy or torch, host or device; a device y is used where it lies, not copied.  probes_x [n, m]
+    (KMeans.probe_centers of x; needs labels_y): the rows of y in the m probed clusters of every row, acav_rows_probedup;
+    labels_x is then only used for k=None.  each=True (with probes_x) adds best_each float64 [n, m]."""
     keep_x, xp, n, x_gpu = _as_f32_2d(x)
     d = int(keep_x.shape[1])
     keep_y, yp, m, y_gpu = _as_f32_2d(y, width=d)
+    if probes_x is not None and labels_x is None and labels_y is not None:
+        labels_x = probes_x[:, 0]
     if (labels_x is None) != (labels_y is None):
         raise ValueError("labels_x and labels_y go together: both, or neither (no blocking)")
     lab_x = lab_y = None
@@ -99,9 +135,19 @@ def nearest_in(x, y, labels_x=None, labels_y=None, k=None, device="cuda"):
     best, partner = np.empty(n, np.float64), np.empty(n, np.int64)
     lib = _lib.load_library()
     dev = keep_y.device.index if y_gpu else keep_x.device.index if x_gpu else _device_index(device)
-    _lib.check(lib.acav_rows_crossdup(dev, xp, n, yp, m, d, _lib.ptr(lab_x), _lib.ptr(lab_y), int(k), _lib.ptr(best),
-                                      _lib.ptr(partner), None))
-    return best, partner
+    if probes_x is None:
+        if each:
+            raise ValueError("each=True needs probes_x: without them there is one cluster per row")
+        _lib.check(lib.acav_rows_crossdup(dev, xp, n, yp, m, d, _lib.ptr(lab_x), _lib.ptr(lab_y), int(k), _lib.ptr(best),
+                                          _lib.ptr(partner), None))
+        return best, partner
+    if lab_y is None:
+        raise ValueError("probes_x need labels_y: without blocking there is nothing to probe")
+    lists, mp = _probe_lists(probes_x, n)
+    best_each = np.empty((n, mp), np.float64) if each else None
+    _lib.check(lib.acav_rows_probedup(dev, xp, n, yp, m, d, _lib.ptr(lists), int(mp), _lib.ptr(lab_y), None, int(k),
+                                      _lib.ptr(best), _lib.ptr(partner), _lib.ptr(best_each), None))
+    return (best, partner, best_each) if each else (best, partner)
 
 
 def flag(best, threshold):
@@ -109,11 +155,44 @@ def flag(best, threshold):
     return np.asarray(best, np.float64) >= float(threshold)
 
 
-def summarise(best, partner, labels, k, threshold):
+def probe_pairs(probes, labels_y, before=None):
+    """the pairs acav_rows_probedup compares (pure numpy): over the slots of probes [n, m] that count (not -1, not a label
+    repeated in the row's list) the rows of labels_y [my] with the slot's label at positions below before[i] (all: None)"""
+    lists, ly = np.asarray(probes, np.int64), np.asarray(labels_y, np.int64)
+    n, m = lists.shape
+    counts = lists >= 0
+    for p in range(1, m):
+        counts[:, p] &= ~(lists[:, :p] == lists[:, p:p + 1]).any(1)
+    span = len(ly) + 1
+    keys = np.sort(ly * span + np.arange(len(ly)))  # by label, then position
+    cut = np.full(n, len(ly), np.int64) if before is None else np.clip(np.asarray(before, np.int64), 0, len(ly))
+    c = np.where(counts, lists, 0)
+    rows = np.searchsorted(keys, c * span + cut[:, None]) - np.searchsorted(keys, c * span)
+    return int(rows[counts].sum())
+
+
+def _probe_keys(best_each, threshold, pairs):
+    """the keys a report gains with probes > 1: entry p - 1 of flagged_by_probes counts the rows whose best over their first p
+    probed clusters reaches the threshold -- entry 0 is what probes=1 flags, and where the curve flattens a further probe no
+    longer pays"""
+    each = np.asarray(best_each, np.float64)
+    upto = np.maximum.accumulate(each, axis=1)
+    return [('probes', int(each.shape[1])), ('pairs', int(pairs)),
+            ('flagged_by_probes', [int(c) for c in (upto >= float(threshold)).sum(0)])]
+
+
+def summarise(best, partner, labels, k, threshold, probes=None, best_each=None):
     """the report of one run (pure numpy): n, K, threshold, flagged and flagged_share, flagged_by_cluster [K], zero_rows -- the
     rows that have an earlier row in their cluster and yet no partner: all-zero rows, or rows all of whose earlier cluster mates
     are all-zero -- and similarity_counts: the rows with best >= g for every g of SIMILARITY_GRID, so that a threshold can be
-    picked from one run"""
+    picked from one run.  probes [n, m] and best_each [n, m] of a multi-probe run with m > 1 (nearest_earlier(probes=,
+    each=True)) add probes = m, pairs (compared) and flagged_by_probes [m]; without them, and at m = 1, the keys are today's"""
+    if probes is not None and np.shape(probes)[1] > 1:
+        if best_each is None or np.shape(best_each) != np.shape(probes):
+            raise ValueError("probes {} need best_each of the same shape".format(np.shape(probes)))
+        report = summarise(best, partner, labels, k, threshold)
+        report.update(_probe_keys(best_each, threshold, probe_pairs(probes, labels, np.arange(report['n']))))
+        return report
     best, partner = np.asarray(best, np.float64), np.asarray(partner, np.int64)
     lab, k = np.asarray(labels, np.int64), int(k)
     n = int(best.shape[0])
@@ -132,13 +211,24 @@ def summarise(best, partner, labels, k, threshold):
     }
 
 
-def summarise_against(best, partner, labels_x, hist_y, k, threshold, m):
+def summarise_against(best, partner, labels_x, hist_y, k, threshold, m, probes_x=None, best_each=None):
     """the report of one run against a held-out set of m rows (pure numpy).  labels_x [n] and hist_y [k] (the held-out rows per
     cluster): blocking=cluster; both None and k = 1: no blocking.  n, m, K, threshold, flagged and flagged_share,
     flagged_by_cluster [K] (blocked only), similarity_counts as in summarise, pairs = sum over the clusters of (pool rows) x
     (held-out rows), n m when unblocked, and without_candidates: the pool rows whose cluster holds no non-zero held-out row --
     counted as the rows of the clusters in which no pool row has a partner (a cluster all of whose pool rows are all-zero
-    counts too: pool_zero_rows of the verb's report tells)"""
+    counts too: pool_zero_rows of the verb's report tells).  probes_x [n, mp] and best_each [n, mp] of a multi-probe run with
+    mp > 1 (nearest_in(probes_x=, each=True), blocked only) add probes = mp and flagged_by_probes [mp] and make pairs the
+    pairs of all probed clusters; without them, and at mp = 1, the keys and values are today's"""
+    if probes_x is not None and np.shape(probes_x)[1] > 1:
+        if labels_x is None or best_each is None or np.shape(best_each) != np.shape(probes_x):
+            raise ValueError("probes_x {} need labels_x, hist_y and best_each of the same shape".format(np.shape(probes_x)))
+        report = summarise_against(best, partner, labels_x, hist_y, k, threshold, m)
+        ly = np.repeat(np.arange(int(k)), np.asarray(hist_y, np.int64))  # any labels with this histogram: no cut, only counts
+        keys = OrderedDict(_probe_keys(best_each, threshold, probe_pairs(probes_x, ly)))
+        report['pairs'] = keys.pop('pairs')
+        report.update(keys)
+        return report
     best, partner, k, m = np.asarray(best, np.float64), np.asarray(partner, np.int64), int(k), int(m)
     n = int(best.shape[0])
     blocked = labels_x is not None
@@ -184,12 +274,35 @@ def check_against_options(opts):
     return path, str(meta), blocking
 
 
-def check_options(opts, views=None, epoch=None):
+PROBES_MAX = 16  # ACAV_PROBES_MAX (include/acav_hip.h)
+
+
+def check_probes(opts, k=None):
+    """dedup.probes -> m, 1 when the key is absent: an integer in [1, min(16, K)] (k: K once the cache is known), valid in the
+    in-cluster mode and with dedup.blocking=cluster -- without blocking there is nothing to probe.  Pure: no device, no file"""
+    opts = opts or {}
+    m = opts.get('probes')
+    if m is None:
+        return 1
+    if isinstance(m, bool) or not isinstance(m, numbers.Integral) or not 1 <= int(m) <= PROBES_MAX:
+        raise ValueError("dedup.probes must be an integer in [1, min({}, K)], not {!r}".format(PROBES_MAX, m))
+    if k is not None and int(m) > int(k):
+        raise ValueError("dedup.probes={} exceeds the K={} clusters of the run: there are no more centres to probe".format(m, k))
+    path, _meta, blocking = check_against_options(opts)
+    if int(m) > 1 and path is not None and blocking != 'cluster':  # one probe is the default: the run of today
+        raise ValueError("dedup.probes is refused with dedup.blocking=none: every pool row is compared with every held-out row "
+                         "already, there is nothing to probe; use --dedup.blocking=cluster")
+    return int(m)
+
+
+def check_options(opts, views=None, epoch=None, k=None):
     """the `dedup` options -> (threshold, view, out_path, report_path).  Pure: no device, no file.  views: the names
     "<model_key>/<layer>" the cache holds, once it is known (None: dedup.view is only checked for its form); epoch:
-    clustering.cached_epoch, when given exactly one epoch is required"""
+    clustering.cached_epoch, when given exactly one epoch is required; k: the K of the cluster run, once it is known
+    (dedup.probes is checked against it, check_probes)"""
     opts = opts or {}
     check_against_options(opts)
+    check_probes(opts, k)
     thr = opts.get('threshold')
     if thr is None:
         raise ValueError("dedup needs --dedup.threshold=<t in (0, 1]>: the cosine from which a row counts as a duplicate of an "
@@ -257,9 +370,11 @@ def dedup(args):
     km.args = None  # one process, one GPU, whatever run wrote the cache
     km = km.to(dev)
     K = km.centers.shape[0]
+    probes = check_probes(opts, K)
     against = check_against_options(opts)
     if against[0] is not None:
-        return _dedup_against(args, against, paths, sizes, view_dims, v, dt, km, threshold, view, epoch, out_path, report_path)
+        return _dedup_against(args, against, paths, sizes, view_dims, v, dt, km, threshold, view, epoch, out_path, report_path,
+                              probes)
 
     n_total = sum(int(sizes[p.stem]) for p in paths)
     need = 4 * n_total * d
@@ -287,18 +402,31 @@ def dedup(args):
         raise RuntimeError("the shards delivered {} rows, their metadata states {}: fix the metadata or drop the unreadable shards "
                            "from the list".format(base, n_total))
     labels, _ = km.calc_best(x, need_mean=False)  # a row's label is a pure function of the row and the state
-    best, partner = nearest_earlier(x, labels, k=K)
+    lists = each = None
+    if probes == 1:
+        best, partner = nearest_earlier(x, labels, k=K)
+    else:  # the earlier rows of the m nearest centres' clusters: a partner may carry another label
+        lists = km.probe_centers(x, probes, labels)
+        best, partner, each = nearest_earlier(x, labels, k=K, probes=lists, each=True)
     labels = labels.cpu().numpy() if hasattr(labels, "cpu") else np.asarray(labels)
 
-    report = summarise(best, partner, labels, K, threshold)
+    report = summarise(best, partner, labels, K, threshold, probes=lists, best_each=each)
     report.update(view=view, epoch=int(epoch), feature_path=str(args.data.path), clusters_path=str(args.data.output.path))
     out_path = _write_csv(out_path, best, partner, threshold, (shard_name, filename), (shard_name, filename))
     print("dedup: view {} epoch {}: {} of {} rows ({:.3f}%) have an earlier row of their cluster at cosine >= {!r}; {} zero rows; "
           "wrote {}".format(view, epoch, report['flagged'], report['n'], 100.0 * report['flagged_share'], threshold,
                             report['zero_rows'], out_path))
     print("rows with best >= " + "  ".join("{}: {}".format(g, c) for g, c in report['similarity_counts'].items()))
+    _print_probe_curve(report)
     _write_report(report_path, report)
     return report
+
+
+def _print_probe_curve(report):
+    """under the similarity grid: what each further probe finds (multi-probe runs only)"""
+    if 'flagged_by_probes' in report:
+        print("flagged within the first p probed clusters  " + "  ".join(
+            "{}: {}".format(p + 1, c) for p, c in enumerate(report['flagged_by_probes'])) + "  ({} pairs compared)".format(report['pairs']))
 
 
 def _host(labels):
@@ -325,8 +453,9 @@ def _write_report(report_path, report):
             json.dump(report, f, indent=1)
 
 
-def _dedup_against(args, against, paths, sizes, view_dims, v, dt, km, threshold, view, epoch, out_path, report_path):
-    """the against mode of the verb: the held-out view resident in one device buffer, one pass over the pool's row groups"""
+def _dedup_against(args, against, paths, sizes, view_dims, v, dt, km, threshold, view, epoch, out_path, report_path, probes=1):
+    """the against mode of the verb: the held-out view resident in one device buffer, one pass over the pool's row groups;
+    probes > 1 (blocking=cluster): the probe lists of a pool piece are computed per row group, the pool still streams"""
     import torch
     from .. import shards as io
     from .frontend import FrontEnd
@@ -387,14 +516,19 @@ def _dedup_against(args, against, paths, sizes, view_dims, v, dt, km, threshold,
     print("dedup: view {} epoch {}: {} pool rows against {} held-out rows, blocking={}{}".format(
         view, epoch, n_total, m_total, blocking, ": {} pairs".format(pairs) if pairs is not None else ""))
 
-    best, partner, labels_x, pool_zero, shard_name, filename = [], [], [], 0, [], []
+    best, partner, labels_x, pool_zero, shard_name, filename, lists, each = [], [], [], 0, [], [], [], []
     for _gi, table, rows in pool.iterate(views={v}):
         part = rows[v]
         lab = None
         if blocking == 'cluster':
             lab, _ = km.calc_best(part, need_mean=False)
             labels_x.append(_host(lab))
-        b, p = nearest_in(part, y, lab, labels_y, k=K)
+        if probes == 1:
+            b, p = nearest_in(part, y, lab, labels_y, k=K)
+        else:
+            lists.append(km.probe_centers(part, probes, lab))
+            b, p, e = nearest_in(part, y, lab, labels_y, k=K, probes_x=lists[-1], each=True)
+            each.append(e)
         best.append(b)
         partner.append(p)
         pool_zero += int((torch.count_nonzero(part, dim=1) == 0).sum())
@@ -406,7 +540,8 @@ def _dedup_against(args, against, paths, sizes, view_dims, v, dt, km, threshold,
                            "from the list".format(len(best), n_total))
     labels_x = np.concatenate(labels_x) if blocking == 'cluster' else None
 
-    report = summarise_against(best, partner, labels_x, hist_y, K, threshold, m_total)
+    report = summarise_against(best, partner, labels_x, hist_y, K, threshold, m_total,
+                               probes_x=np.concatenate(lists) if lists else None, best_each=np.concatenate(each) if each else None)
     report.update(view=view, epoch=int(epoch), feature_path=str(args.data.path), clusters_path=str(args.data.output.path),
                   against_path=str(against_path), blocking=blocking, pool_zero_rows=pool_zero, against_zero_rows=against_zero)
     out_path = _write_csv(out_path, best, partner, threshold, (shard_name, filename), (hshard, hfile))
@@ -414,5 +549,6 @@ def _dedup_against(args, against, paths, sizes, view_dims, v, dt, km, threshold,
           "without candidates); wrote {}".format(view, epoch, report['flagged'], report['n'], 100.0 * report['flagged_share'],
                                                   threshold, report['pairs'], report['without_candidates'], out_path))
     print("rows with best >= " + "  ".join("{}: {}".format(g, c) for g, c in report['similarity_counts'].items()))
+    _print_probe_curve(report)
     _write_report(report_path, report)
     return report

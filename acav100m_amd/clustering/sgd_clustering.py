@@ -316,30 +316,56 @@ class KMeans:
             labels, _ = self.calc_best(batch, need_mean=False)
         return silhouette_samples(batch, labels, k=self._shape[0], device="cuda:{}".format(self._device))
 
-    def near_duplicates(self, batch, labels=None):
+    def probe_centers(self, batch, m, labels=None, dists=False):
+        """The m nearest centres of every row (acav_kmeans_probes; the probe lists of the multi-probe dedup) -> probes int64
+        [b, m]: column 0 the row's label, column p >= 1 the centre with the p-th smallest float64 distance among the others
+        (ties to the lower index), -1 past k - 1; with dists=True also their distances float64 [b, m] (+inf for a -1 slot),
+        columns 0 and 1 being quality(rows=True)'s a2 and b2 bit for bit.  labels=None: calc_best(batch, need_mean=False)'s.
+        m in [1, 16].  A row's list does not depend on how the rows are split into calls.  Refused during the warm-up."""
+        from .silhouette import _labels
+        h = self._require_handle()
+        if isinstance(m, bool) or not isinstance(m, (int, np.integer)):
+            raise ValueError("m must be an integer in [1, 16], not {!r}".format(m))
+        keep, xp, b, _ = _as_f32_2d(batch, self._shape[1])
+        if labels is None:
+            labels, _ = self.calc_best(batch, need_mean=False)
+        lab = _labels(labels, b)
+        probes = np.empty((b, max(int(m), 0)), np.int64)
+        dist = np.empty(probes.shape, np.float64) if dists else None
+        _lib.check(_lib._lib.acav_kmeans_probes(h, xp, b, _lib.ptr(lab), int(m), _lib.ptr(probes), _lib.ptr(dist)))
+        return (probes, dist) if dists else probes
+
+    def near_duplicates(self, batch, labels=None, probes=1):
         """For every row the largest cosine to an earlier row of its own cluster and that row (clustering/dedup.py,
         acav_rows_neardup: every such pair in float64) -> (best float64 [b], partner int64 [b]; -inf and -1 for a row without
-        one).  labels=None: calc_best(batch, need_mean=False)'s, as for quality.  The centres enter through the labels alone."""
+        one).  labels=None: calc_best(batch, need_mean=False)'s, as for quality.  The centres enter through the labels alone.
+        probes=m > 1: the earlier rows of the clusters of probe_centers(batch, m, labels) (acav_rows_probedup): pairs that a
+        cluster border splits are seen too, a partner may carry another label."""
         from .dedup import nearest_earlier
         self._require_handle()
         if labels is None:
             labels, _ = self.calc_best(batch, need_mean=False)
-        return nearest_earlier(batch, labels, k=self._shape[0], device="cuda:{}".format(self._device))
+        lists = self.probe_centers(batch, probes, labels) if probes != 1 else None
+        return nearest_earlier(batch, labels, k=self._shape[0], device="cuda:{}".format(self._device), probes=lists)
 
-    def near_duplicates_in(self, batch, other, blocking='cluster'):
+    def near_duplicates_in(self, batch, other, blocking='cluster', probes=1):
         """For every row of batch the largest cosine to a row of the held-out rows `other` and that row (clustering/dedup.py,
         acav_rows_crossdup) -> (best float64 [b], partner int64 [b], a position in other; -inf and -1 for a row without one).
-        blocking='cluster': only the rows of other that calc_best(., need_mean=False) gives the same label; 'none': all."""
+        blocking='cluster': only the rows of other that calc_best(., need_mean=False) gives the same label; 'none': all.
+        probes=m > 1 (blocking='cluster' only): the rows of other in the clusters of probe_centers(batch, m)."""
         from .dedup import nearest_in
         self._require_handle()
         if blocking not in ('cluster', 'none'):
             raise ValueError("blocking must be 'cluster' or 'none', not {!r}".format(blocking))
+        if probes != 1 and blocking != 'cluster':
+            raise ValueError("probes={!r} needs blocking='cluster': without blocking there is nothing to probe".format(probes))
         lab_x = lab_y = None
         if blocking == 'cluster':
             lab_x, _ = self.calc_best(batch, need_mean=False)
             lab_y, _ = self.calc_best(other, need_mean=False)
+        lists = self.probe_centers(batch, probes, lab_x) if probes != 1 else None
         return nearest_in(batch, other, lab_x, lab_y, k=self._shape[0] if blocking == 'cluster' else 1,
-                          device="cuda:{}".format(self._device))
+                          device="cuda:{}".format(self._device), probes_x=lists)
 
     def train_stats(self):
         """(bulk training calls that ran as one persistent launch, launches that gave up and were re-run per step)"""

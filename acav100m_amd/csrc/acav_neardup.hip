@@ -34,6 +34,16 @@
 // label, one contiguous range per tile, possibly empty.  k_crossdup is k_neardup's stage loop with the columns taken from y;
 // crossdup_tiles builds its tile list from the two histograms.  A pool row's result depends on no other pool row, so the pool
 // may come in pieces of any length: only y has to be resident.
+//
+// Multi-probe (acav_rows_probedup; dedup.nearest_earlier / nearest_in with probes, `dedup --dedup.probes=m`): a pair that a
+// cluster border splits is missed by both sweeps above.  Here a row is compared with the rows of y in the m clusters its probe
+// list names (acav_kmeans_probes: its own and the m - 1 centres next nearest).  The queries are (probed cluster, row) ENTRIES,
+// sorted by cluster and then by row; an entry's columns are a prefix [ystart[c], ystart[c] + r) of the cluster's run in y's
+// sorted order (r: the rows of the cluster below before[i]; all without a cut), which is k_crossdup's pair of bounds per
+// position -- the sweep is k_crossdup over entries (its ENTRY instantiation keeps the results by entry), and k_pd_fold merges
+// a row's at most m entry results in slot order, the larger cosine first, then the lower position.  In the in-set use a tile
+// of entries late in a cluster walks a prefix of the run: the triangle, m times.  probedup_entries and probedup_tiles build
+// entries and tile list on the host; acav_rows_probedup_plan exposes them, the entry point launches from them.
 #include <algorithm>
 #include <cmath>
 #include <numeric>
@@ -366,8 +376,9 @@ NdPlan crossdup_tiles(const int64_t *hist_x, const int64_t *hist_y, int k, int d
 // permx[q] / permy[c]: the input position of sorted position q of x / c of y; ylo[q], yhi[q]: the run of q's label in y's sorted
 // order; nrmx / nrmy: ||.||^2 by sorted position.  tiles[b]: the tile workgroup b takes.  best / partner: by INPUT position of
 // x, partner an input position of y.  k_neardup's stages, operands and accumulators; positions past 2^31 - 64 are compared
-// unsigned
-template <int RT, bool VEC>
+// unsigned.  ENTRY (acav_rows_probedup): the sorted positions are (probed cluster, row) entries, permx[q] the row of entry q,
+// and best / partner are kept by ENTRY q for k_pd_fold
+template <int RT, bool VEC, bool ENTRY = false>
 __global__ __launch_bounds__(256, 2) void k_crossdup(const float *__restrict__ x, const float *__restrict__ y, int d, int m,
                                                      const int *__restrict__ permx, const int *__restrict__ permy,
                                                      const int *__restrict__ ylo, const int *__restrict__ yhi,
@@ -484,26 +495,166 @@ __global__ __launch_bounds__(256, 2) void k_crossdup(const float *__restrict__ x
         }
     }
     if (walker) {
-        const size_t o = (size_t)permx[my_pos];
+        const size_t o = ENTRY ? (size_t)my_pos : (size_t)permx[my_pos];
         best[o] = top;
         partner[o] = arg >= 0 ? (int64_t)permy[arg] : (int64_t)-1;
     }
 }
 
-template <int RT>
+template <int RT, bool ENTRY = false>
 int launch_cross(const NdPlan &plan, bool vec, hipStream_t st, const float *x, const float *y, int d, int m, const int *permx,
                  const int *permy, const int *ylo, const int *yhi, const double *nrmx, const double *nrmy, const NdTile *tiles,
                  double *best, int64_t *partner)
 {
-    const void *fn = vec ? reinterpret_cast<const void *>(k_crossdup<RT, true>) : reinterpret_cast<const void *>(k_crossdup<RT, false>);
+    const void *fn = vec ? reinterpret_cast<const void *>(k_crossdup<RT, true, ENTRY>)
+                         : reinterpret_cast<const void *>(k_crossdup<RT, false, ENTRY>);
     ACAV_HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)neardup_lds(RT)));
     if (vec)
-        hipLaunchKernelGGL((k_crossdup<RT, true>), dim3((unsigned)plan.tiles), dim3(256), plan.lds, st, x, y, d, m, permx, permy, ylo,
-                           yhi, nrmx, nrmy, tiles, best, partner);
+        hipLaunchKernelGGL((k_crossdup<RT, true, ENTRY>), dim3((unsigned)plan.tiles), dim3(256), plan.lds, st, x, y, d, m, permx, permy,
+                           ylo, yhi, nrmx, nrmy, tiles, best, partner);
     else
-        hipLaunchKernelGGL((k_crossdup<RT, false>), dim3((unsigned)plan.tiles), dim3(256), plan.lds, st, x, y, d, m, permx, permy, ylo,
-                           yhi, nrmx, nrmy, tiles, best, partner);
+        hipLaunchKernelGGL((k_crossdup<RT, false, ENTRY>), dim3((unsigned)plan.tiles), dim3(256), plan.lds, st, x, y, d, m, permx, permy,
+                           ylo, yhi, nrmx, nrmy, tiles, best, partner);
     ACAV_HIP_TRY(hipGetLastError());
+    return ACAV_OK;
+}
+
+// ---- acav_rows_probedup: the rows of x [n] against the rows of y [my] in the m probed clusters of each
+
+// the queries of a probe sweep.  An ENTRY is a (probed cluster c, row i) pair; the entries are sorted by c, then by i, so that
+// -- y being label-sorted -- consecutive entries walk the same run of y.  Per entry: the row, and its column range [lo, hi) in
+// y's sorted order, lo = ystart[c], hi = lo + (the rows of y labelled c at input positions below before[i]; all when before is
+// NULL): ascending sorted position being ascending input position inside a run, that is a prefix of the run
+struct PdEntries {
+    std::vector<int> erow, elo, ehi;  // [entries]
+    std::vector<int> eidx;            // [n][m]: the entry of slot p of row i; -1 for a -1 slot and for a label repeated in the list
+    std::vector<int> permy;           // [my]: y's positions by label, stably
+    int64_t pairs = 0;                // sum of hi - lo
+};
+
+// ACAV_EINVAL for a probe outside [-1, k) or a label of y outside [0, k): checked before anything is indexed with one
+int probedup_entries(const int64_t *probes, int64_t n, int m, const std::vector<int64_t> &laby, int64_t my, const int64_t *before, int k,
+                     PdEntries *E)
+{
+    int64_t bad = 0;
+    for (int64_t j = 0; j < my; ++j) bad += (laby[(size_t)j] < 0 || laby[(size_t)j] >= k) ? 1 : 0;
+    ACAV_REQUIRE(bad == 0, ACAV_EINVAL, "%lld of the %lld labels of y are outside [0, %d)", (long long)bad, (long long)my, k);
+    for (int64_t c = 0; c < n * m; ++c) bad += (probes[c] < -1 || probes[c] >= k) ? 1 : 0;
+    ACAV_REQUIRE(bad == 0, ACAV_EINVAL, "%lld of the %lld x %d probes of x are outside [-1, %d)", (long long)bad, (long long)n, m, k);
+    E->permy.resize((size_t)my);
+    sort_by_label(laby, my, k, E->permy.data());
+
+    // the cells (i, p) that are entries, in (i, p) order, and their clusters; then the order by cluster, stably: by i inside one
+    std::vector<int64_t> key;
+    std::vector<int> cell;
+    key.reserve((size_t)(n * m)), cell.reserve((size_t)(n * m));
+    for (int64_t i = 0; i < n; ++i)
+        for (int p = 0; p < m; ++p) {
+            const int64_t c = probes[i * m + p];
+            bool entry = c >= 0;
+            for (int q = 0; entry && q < p; ++q) entry = probes[i * m + q] != c;  // a repeated label counts once, at its first slot
+            if (entry) key.push_back(c), cell.push_back((int)(i * m + p));
+        }
+    const int64_t ne = (int64_t)key.size();
+    std::vector<int> order((size_t)ne);
+    sort_by_label(key, ne, k, order.data());
+    E->erow.resize((size_t)ne), E->elo.resize((size_t)ne), E->ehi.resize((size_t)ne);
+    E->eidx.assign((size_t)(n * m), -1);
+    E->pairs = 0;
+    const int *py = E->permy.data();
+    int64_t ys = 0, ye = 0, cur = -1;  // the run of cluster `cur` in y's sorted order
+    for (int64_t e = 0; e < ne; ++e) {
+        const int at = order[(size_t)e], cl = cell[(size_t)at];
+        const int64_t c = key[(size_t)at], i = cl / m;
+        if (c != cur) {
+            for (ys = ye; ys < my && laby[(size_t)py[ys]] < c; ++ys) {}
+            for (ye = ys; ye < my && laby[(size_t)py[ye]] == c; ++ye) {}
+            cur = c;
+        }
+        const int64_t r = before ? std::lower_bound(py + ys, py + ye, before[i], [](int a, int64_t b) { return (int64_t)a < b; }) - (py + ys)
+                                 : ye - ys;
+        E->erow[(size_t)e] = (int)i, E->elo[(size_t)e] = (int)ys, E->ehi[(size_t)e] = (int)(ys + r);
+        E->eidx[(size_t)cl] = (int)e;
+        E->pairs += r;
+    }
+    return ACAV_OK;
+}
+
+// the tiles of the entries: tile t holds the entries [t QM, min(entries, (t + 1) QM)) and walks the column blocks of y's sorted
+// order from the first one any of its non-empty ranges touches to the last one (lo does not decrease along the entries: the
+// first non-empty range has the lowest lo); 0 blocks, at first block floor(lo of its first entry / 64), when all its ranges are
+// empty.  list (NULL: skipped): the tiles by descending blocks, ties by ascending t.  Returns the plan.
+NdPlan probedup_tiles(const PdEntries &E, int64_t n, int m, int64_t my, int cus, std::vector<NdTile> *list)
+{
+    const int64_t ne = (int64_t)E.erow.size();
+    NdPlan p;
+    p.rt = neardup_rt(ne, cus);
+    const int64_t qm = (int64_t)ND_QM * p.rt;
+    p.tiles = (ne + qm - 1) / qm;
+    p.blocks = 0;
+    if (list) list->clear(), list->reserve((size_t)p.tiles);
+    for (int64_t t = 0; t < p.tiles; ++t) {
+        const int64_t q0 = t * qm, q1 = std::min(ne, q0 + qm);
+        int64_t first = -1, end = 0;
+        for (int64_t e = q0; e < q1; ++e)
+            if (E.ehi[(size_t)e] > E.elo[(size_t)e]) {
+                if (first < 0) first = E.elo[(size_t)e] / ND_CN;
+                end = std::max<int64_t>(end, (E.ehi[(size_t)e] + ND_CN - 1) / ND_CN);
+            }
+        const int64_t cb0 = first < 0 ? E.elo[(size_t)q0] / ND_CN : first, blocks = first < 0 ? 0 : end - first;
+        p.blocks += blocks;
+        if (list) list->push_back(NdTile{(int)q0, (int)(q1 - q0), (int)cb0, (int)blocks});
+    }
+    if (list) std::stable_sort(list->begin(), list->end(), [](const NdTile &a, const NdTile &c) { return a.blocks > c.blocks; });
+    p.lds = neardup_lds(p.rt);
+    // per entry the row and two bounds, y's sorted positions, the entry of every (row, slot); the norms by entry and of y; the
+    // tile list; (best, partner) per entry and per row; best_each
+    p.scratch = sizeof(int) * (3 * (size_t)ne + (size_t)my + (size_t)(n * m)) + sizeof(double) * (size_t)(ne + my) +
+                sizeof(NdTile) * (size_t)p.tiles + (sizeof(double) + sizeof(int64_t)) * (size_t)(ne + n) + sizeof(double) * (size_t)(n * m);
+    return p;
+}
+
+// one thread per row: its at most m entry results in slot order, the larger cosine first, then the lower position of y
+__global__ __launch_bounds__(256) void k_pd_fold(int n, int m, const int *__restrict__ eidx, const double *__restrict__ ebest,
+                                                 const int64_t *__restrict__ epartner, double *__restrict__ best,
+                                                 int64_t *__restrict__ partner, double *__restrict__ best_each)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double top = -__builtin_inf();
+    int64_t arg = -1;
+    for (int p = 0; p < m; ++p) {
+        const int e = eidx[(size_t)i * m + p];
+        const double v = e >= 0 ? ebest[e] : -__builtin_inf();
+        const int64_t j = e >= 0 ? epartner[e] : (int64_t)-1;
+        if (best_each) best_each[(size_t)i * m + p] = v;
+        if (j >= 0 && (v > top || (v == top && j < arg))) top = v, arg = j;
+    }
+    best[i] = top;
+    partner[i] = arg;
+}
+
+// count int64 values of p (host or device) on the host
+int fetch_i64(const int64_t *p, int64_t count, std::vector<int64_t> *out, hipStream_t st)
+{
+    out->resize((size_t)count);
+    if (is_device_ptr(p)) {
+        ACAV_HIP_TRY(hipMemcpyAsync(out->data(), p, sizeof(int64_t) * (size_t)count, hipMemcpyDeviceToHost, st));
+        ACAV_HIP_TRY(hipStreamSynchronize(st));
+    } else {
+        std::copy(p, p + count, out->begin());
+    }
+    return ACAV_OK;
+}
+
+int check_probedup_sizes(int64_t n, int64_t my, int d, int m, int k)
+{
+    ACAV_REQUIRE(n >= 1 && n <= ND_MAX_N, ACAV_EINVAL, "n=%lld must be in [1, 2^31): positions are 32-bit", (long long)n);
+    ACAV_REQUIRE(my >= 1 && my <= ND_MAX_N, ACAV_EINVAL, "my=%lld must be in [1, 2^31): positions are 32-bit", (long long)my);
+    ACAV_REQUIRE(d >= 1 && d <= ND_MAX_D, ACAV_EINVAL, "d=%d must be in [1, %d]", d, ND_MAX_D);
+    ACAV_REQUIRE(k >= 1, ACAV_EINVAL, "k=%d must be at least 1", k);
+    ACAV_REQUIRE(m >= 1 && m <= ACAV_PROBES_MAX, ACAV_EINVAL, "m=%d must be in [1, %d]", m, ACAV_PROBES_MAX);
+    ACAV_REQUIRE(n * m <= ND_MAX_N, ACAV_EINVAL, "n m = %lld entries must be below 2^31: entries are 32-bit", (long long)(n * m));
     return ACAV_OK;
 }
 
@@ -741,6 +892,115 @@ ACAV_EXPORT int acav_rows_crossdup(int device, const float *x, int64_t n, const 
                                  dpartner));
     if (!best_dev) ACAV_HIP_TRY(hipMemcpyAsync(best, obest.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
     if (!partner_dev) ACAV_HIP_TRY(hipMemcpyAsync(partner, opartner.p, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+    ACAV_HIP_TRY(hipStreamSynchronize(st));
+    return ACAV_OK;
+}
+
+ACAV_EXPORT int acav_rows_probedup_plan(const int64_t *probes_x, int64_t n, int m, const int64_t *labels_y, int64_t my,
+                                        const int64_t *before, int k, int d, int cus, int64_t *out, int64_t *tiles, int64_t cap)
+{
+    ACAV_REQUIRE(probes_x && labels_y && out, ACAV_EINVAL, "NULL argument");
+    ACAV_REQUIRE(cus > 0, ACAV_EINVAL, "bad sizes");
+    ACAV_TRY(check_probedup_sizes(n, my, d, m, k));
+    PdEntries E;
+    ACAV_TRY(probedup_entries(probes_x, n, m, std::vector<int64_t>(labels_y, labels_y + my), my, before, k, &E));
+    std::vector<NdTile> list;
+    const NdPlan p = probedup_tiles(E, n, m, my, cus, tiles ? &list : nullptr);
+    ACAV_REQUIRE(!tiles || cap >= p.tiles, ACAV_EINVAL, "room for %lld tiles, the entries are cut into %lld", (long long)cap, (long long)p.tiles);
+    out[0] = (int64_t)ND_QM * p.rt, out[1] = p.tiles, out[2] = p.blocks, out[3] = p.tiles, out[4] = (int64_t)p.lds;
+    out[5] = (int64_t)p.scratch;
+    if (tiles)
+        for (int64_t t = 0; t < p.tiles; ++t) {
+            const NdTile &e = list[(size_t)t];
+            tiles[4 * t] = e.q0, tiles[4 * t + 1] = e.rows, tiles[4 * t + 2] = e.cb0, tiles[4 * t + 3] = e.blocks;
+        }
+    return ACAV_OK;
+}
+
+ACAV_EXPORT int acav_rows_probedup(int device, const float *x, int64_t n, const float *y, int64_t my, int d, const int64_t *probes_x,
+                                   int m, const int64_t *labels_y, const int64_t *before, int k, double *best, int64_t *partner,
+                                   double *best_each, void *stream)
+{
+    ACAV_REQUIRE(x && y && probes_x && labels_y && best && partner, ACAV_EINVAL, "NULL argument");
+    ACAV_TRY(check_probedup_sizes(n, my, d, m, k));
+    int cus = 0;
+    ACAV_TRY(use_device(device, &cus));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+
+    DevBuf stage_x, stage_y, bad, ints, nrm, dtiles, eres, obest, opartner, oeach;
+    StreamDrain drain = {st};
+    const void *dx = nullptr, *dy = nullptr;
+    const size_t total_x = (size_t)n * d, total_y = (size_t)my * d, cells = (size_t)n * m;
+    ACAV_TRY(to_device(x, sizeof(float) * total_x, stage_x, st, &dx));
+    if (y == x && my == n)
+        dy = dx;  // the in-set use: one copy
+    else
+        ACAV_TRY(to_device(y, sizeof(float) * total_y, stage_y, st, &dy));
+    const float *xd = static_cast<const float *>(dx), *yd = static_cast<const float *>(dy);
+    ACAV_TRY(bad.ensure(sizeof(unsigned long long) * 2));  // values of x, of y that are not finite
+    ACAV_HIP_TRY(hipMemsetAsync(bad.p, 0, sizeof(unsigned long long) * 2, st));
+    hipLaunchKernelGGL(k_nd_finite, dim3((unsigned)std::min<size_t>((total_x + 255) / 256, (size_t)cus * 8)), dim3(256), 0, st, xd,
+                       total_x, bad.as<unsigned long long>());
+    ACAV_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_nd_finite, dim3((unsigned)std::min<size_t>((total_y + 255) / 256, (size_t)cus * 8)), dim3(256), 0, st, yd,
+                       total_y, bad.as<unsigned long long>() + 1);
+    ACAV_HIP_TRY(hipGetLastError());
+    unsigned long long nbad[2] = {0, 0};
+    ACAV_HIP_TRY(hipMemcpyAsync(nbad, bad.p, sizeof(nbad), hipMemcpyDeviceToHost, st));
+    std::vector<int64_t> probes, laby, cut;
+    ACAV_TRY(fetch_i64(probes_x, n * m, &probes, st));
+    ACAV_TRY(fetch_i64(labels_y, my, &laby, st));
+    if (before) ACAV_TRY(fetch_i64(before, n, &cut, st));
+    ACAV_HIP_TRY(hipStreamSynchronize(st));
+    ACAV_REQUIRE(nbad[0] == 0, ACAV_EINVAL, "%llu of the %lld x %d values of x are not finite (inf or NaN)", nbad[0], (long long)n, d);
+    ACAV_REQUIRE(nbad[1] == 0, ACAV_EINVAL, "%llu of the %lld x %d values of y are not finite (inf or NaN)", nbad[1], (long long)my, d);
+
+    // the entries by (probed cluster, row) with their column ranges, y's positions by label, the tile list: the plan's
+    PdEntries E;
+    ACAV_TRY(probedup_entries(probes.data(), n, m, laby, my, before ? cut.data() : nullptr, k, &E));
+    std::vector<NdTile> list;
+    const NdPlan plan = probedup_tiles(E, n, m, my, cus, &list);
+    const size_t ne = E.erow.size();
+
+    std::vector<int> host(3 * ne + (size_t)my + cells);
+    std::copy(E.erow.begin(), E.erow.end(), host.begin());
+    std::copy(E.elo.begin(), E.elo.end(), host.begin() + ne);
+    std::copy(E.ehi.begin(), E.ehi.end(), host.begin() + 2 * ne);
+    std::copy(E.permy.begin(), E.permy.end(), host.begin() + 3 * ne);
+    std::copy(E.eidx.begin(), E.eidx.end(), host.begin() + 3 * ne + (size_t)my);
+    const bool best_dev = is_device_ptr(best), partner_dev = is_device_ptr(partner), each_dev = best_each && is_device_ptr(best_each);
+    ACAV_TRY(upload(ints, host.data(), sizeof(int) * host.size(), st));
+    if (ne) ACAV_TRY(upload(dtiles, list.data(), sizeof(NdTile) * list.size(), st));
+    ACAV_TRY(nrm.ensure(sizeof(double) * (ne + (size_t)my)));
+    ACAV_TRY(eres.ensure((sizeof(double) + sizeof(int64_t)) * std::max<size_t>(ne, 1)));
+    if (!best_dev) ACAV_TRY(obest.ensure(sizeof(double) * (size_t)n));
+    if (!partner_dev) ACAV_TRY(opartner.ensure(sizeof(int64_t) * (size_t)n));
+    if (best_each && !each_dev) ACAV_TRY(oeach.ensure(sizeof(double) * cells));
+    double *dbest = best_dev ? best : obest.as<double>();
+    int64_t *dpartner = partner_dev ? partner : opartner.as<int64_t>();
+    double *deach = !best_each ? (double *)nullptr : each_dev ? best_each : oeach.as<double>();
+    const int *derow = ints.as<int>(), *delo = derow + ne, *dehi = delo + ne, *dpermy = dehi + ne, *deidx = dpermy + my;
+    double *nrme = nrm.as<double>(), *nrmy = nrme + ne, *ebest = eres.as<double>();
+    int64_t *epartner = reinterpret_cast<int64_t *>(ebest + std::max<size_t>(ne, 1));
+    const bool vec = d % 4 == 0 && ((reinterpret_cast<uintptr_t>(xd) | reinterpret_cast<uintptr_t>(yd)) & 15) == 0;
+    if (ne) {
+        hipLaunchKernelGGL(k_nd_norms, dim3((unsigned)ne), dim3(64), 0, st, xd, d, derow, nrme);  // an entry's norm is its row's
+        ACAV_HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_nd_norms, dim3((unsigned)my), dim3(64), 0, st, yd, d, dpermy, nrmy);
+        ACAV_HIP_TRY(hipGetLastError());
+        if (plan.rt == 2)
+            ACAV_TRY((launch_cross<2, true>(plan, vec, st, xd, yd, d, (int)my, derow, dpermy, delo, dehi, nrme, nrmy, dtiles.as<NdTile>(),
+                                            ebest, epartner)));
+        else
+            ACAV_TRY((launch_cross<1, true>(plan, vec, st, xd, yd, d, (int)my, derow, dpermy, delo, dehi, nrme, nrmy, dtiles.as<NdTile>(),
+                                            ebest, epartner)));
+    }
+    hipLaunchKernelGGL(k_pd_fold, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (int)n, m, deidx, ebest, epartner, dbest, dpartner,
+                       deach);
+    ACAV_HIP_TRY(hipGetLastError());
+    if (!best_dev) ACAV_HIP_TRY(hipMemcpyAsync(best, obest.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
+    if (!partner_dev) ACAV_HIP_TRY(hipMemcpyAsync(partner, opartner.p, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+    if (best_each && !each_dev) ACAV_HIP_TRY(hipMemcpyAsync(best_each, oeach.p, sizeof(double) * cells, hipMemcpyDeviceToHost, st));
     ACAV_HIP_TRY(hipStreamSynchronize(st));
     return ACAV_OK;
 }
