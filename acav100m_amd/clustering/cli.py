@@ -4,7 +4,8 @@
 clusterings of such a run on the same feature shards.
 `python cli.py dedup ... --clustering.cached_epoch=<e> --dedup.threshold=<t> --dedup.out_path=<csv>` (ours, clustering/dedup.py):
 near-duplicates inside the clusters of one view of such a run; with `--dedup.against_path=<brace glob .pkl>
---dedup.against_meta_path=<dir> [--dedup.blocking=none|cluster]` the copies of a held-out set's clips in the (streamed) pool."""
+--dedup.against_meta_path=<dir> [--dedup.blocking=none|cluster]` the copies of a held-out set's clips in the (streamed) pool; with
+`--dedup.groups=True [--dedup.keep=first|central]` the groups that cosines over the threshold connect, one kept row per group."""
 import sys
 
 from .. import shards as io

@@ -62,7 +62,28 @@ group); refused with blocking=none, where there is nothing to probe.  The csv ke
 probes, pairs (compared) and flagged_by_probes [m]: entry p - 1 counts the rows whose best over their first p probed clusters
 reaches the threshold -- entry 0 is what probes=1 flags, and where the curve flattens a further probe no longer pays; the verb
 prints it under the similarity grid, so one run at a generous m is enough to pick m.  tests/_probedup_np.py restates both
-definitions."""
+definitions.
+
+Duplicate groups (`--dedup.groups=True`, pairs_earlier / components / choose_kept, KMeans.duplicate_groups,
+acav_rows_neardup_pairs, acav_pairs_components): the rule above gives one number per row and depends on the row order.  Rows
+a < b < c of one cluster with cos(a, c) >= t, cos(b, c) >= t and cos(a, b) < t: a and b both stay and c goes; had c come
+first, c would stay and a and b go.  The groups mode takes the full graph instead of its nearest-earlier forest:
+  P_i        = { j in E_i : cos(i, j) >= t }: every pair, listed at its later row (offsets [n + 1], pair_j, pair_cos)
+  root[i]    = the lowest row of the connected component of i in the graph of all pairs; a group: a component of >= 2 rows
+  kept[i]    = True outside the groups and for one row per group: its root (keep=first) or the member with the smallest
+               squared distance to its centre (keep=central; KMeans.quality's a2, ties to the lower row)
+The groups as sets of rows do not depend on the order of the rows, and every row the nearest-earlier rule flags is removed.
+
+    python -m acav100m_amd.clustering.cli dedup <the keys of the in-cluster run> --dedup.groups=True \\
+        [--dedup.keep=first|central] [--dedup.max_pairs=<N>] [--dedup.groups_path=<csv>]
+
+dedup.out_path then lists every row that is NOT kept, in global row order: shard_name,filename,kept_shard_name,kept_filename,
+similarity (the largest cosine among the row's pairs, earlier or later),group_size -- still a file --exclude_path accepts.
+dedup.groups_path lists every member of every group, kept ones included, by group and row: group (the global row number of the
+root),group_size,kept,shard_name,filename.  The json is summarise_groups' dictionary plus the keys above.  More than
+dedup.max_pairs pairs (default 2^27) are refused with the total and the five clusters that hold the most.  The three keys need
+dedup.groups; the mode is refused with dedup.against_path (a bipartite question: no groups among pool rows) and with
+dedup.probes > 1 (the pairs of probed clusters are a follow-up).  tests/_dupgroups_np.py restates the definition."""
 import csv
 import json
 import numbers
@@ -148,6 +169,130 @@ def nearest_in(x, y, labels_x=None, labels_y=None, k=None, device="cuda", probes
     _lib.check(lib.acav_rows_probedup(dev, xp, n, yp, m, d, _lib.ptr(lists), int(mp), _lib.ptr(lab_y), None, int(k),
                                       _lib.ptr(best), _lib.ptr(partner), _lib.ptr(best_each), None))
     return (best, partner, best_each) if each else (best, partner)
+
+
+MAX_PAIRS = 2 ** 27   # the default dedup.max_pairs: at 16 bytes per pair 2 GiB on the device and 2 GiB on the host
+FIRST_CAP = 2 ** 20   # the room of the first call: pairs are normally far fewer than rows
+
+
+def pairs_earlier(x, labels, threshold, k=None, device="cuda", max_pairs=None):
+    """every pair of a cluster at cosine >= threshold, listed at its later row (acav_rows_neardup_pairs) -> (best float64 [n],
+    partner int64 [n], offsets int64 [n + 1], pair_j int64 [P], pair_cos float64 [P]), P = offsets[n]: row i's earlier
+    partners are pair_j[offsets[i]:offsets[i + 1]] in ascending position; best and partner are nearest_earlier's bytes.  The
+    first call has room for min(max_pairs, max(n, 2^20)) pairs, a second one with the exact size runs only when that is
+    exceeded.  More than max_pairs (None: 2^27) pairs: ValueError naming the total and the five clusters with the most."""
+    keep, xp, n, on_gpu = _as_f32_2d(x)
+    d = int(keep.shape[1])
+    lab = _labels(labels, n)
+    if k is None:
+        k = int(lab.max()) + 1 if n else 1
+    max_pairs = MAX_PAIRS if max_pairs is None else int(max_pairs)
+    if max_pairs < 0:
+        raise ValueError("max_pairs must not be negative, not {}".format(max_pairs))
+    best, partner, offsets = np.empty(n, np.float64), np.empty(n, np.int64), np.empty(n + 1, np.int64)
+    lib = _lib.load_library()
+    dev = keep.device.index if on_gpu else _device_index(device)
+
+    def sweep(cap):
+        pair_j, pair_cos = (np.empty(cap, np.int64), np.empty(cap, np.float64)) if cap else (None, None)
+        _lib.check(lib.acav_rows_neardup_pairs(dev, xp, n, d, _lib.ptr(lab), int(k), float(threshold), _lib.ptr(best),
+                                               _lib.ptr(partner), _lib.ptr(offsets), cap, _lib.ptr(pair_j), _lib.ptr(pair_cos), None))
+        return pair_j, pair_cos
+
+    cap = min(max_pairs, max(n, FIRST_CAP))
+    pair_j, pair_cos = sweep(cap)
+    total = int(offsets[n])
+    if total > max_pairs:
+        per = np.bincount(_host(lab), weights=np.diff(offsets), minlength=int(k)).astype(np.int64)
+        worst = np.argsort(-per, kind='stable')[:5]
+        raise ValueError("{} pairs at cosine >= {!r}, more than max_pairs = {}; the clusters with the most: {}; raise the "
+                         "threshold (or max_pairs)".format(total, float(threshold), max_pairs, ", ".join(
+                             "{}: {}".format(int(c), int(per[c])) for c in worst if per[c] > 0)))
+    if total > cap:
+        pair_j, pair_cos = sweep(total)
+    if pair_j is None:
+        pair_j, pair_cos = np.empty(0, np.int64), np.empty(0, np.float64)
+    return best, partner, offsets, pair_j[:total], pair_cos[:total]
+
+
+def components(n, offsets, pair_j):
+    """root int64 [n] of the pair list (offsets [n + 1], pair_j): the lowest position of every row's connected component, the
+    row itself where it is in no pair (acav_pairs_components: host only, no device)"""
+    offsets, pair_j = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(pair_j, np.int64)
+    if offsets.shape != (int(n) + 1,) or pair_j.ndim != 1 or (len(offsets) and int(offsets[-1]) != len(pair_j)):
+        raise ValueError("offsets {} and pair_j {} do not belong to {} rows".format(offsets.shape, pair_j.shape, n))
+    root = np.empty(int(n), np.int64)
+    if n:
+        _lib.check(_lib.load_library().acav_pairs_components(int(n), _lib.ptr(offsets), _lib.ptr(pair_j) if len(pair_j) else None,
+                                                             _lib.ptr(root)))
+    return root
+
+
+def choose_kept(root, keep, a2=None):
+    """kept bool [n]: True for the rows in no group and for one row of every group.  keep='first': the root, the group's lowest
+    position.  keep='central': the member with the smallest a2 [n] (KMeans.quality(rows=True)'s float64 squared distance to the
+    assigned centre; the members of a group share a cluster, so the values are comparable), ties to the lower position"""
+    root = np.asarray(root, np.int64)
+    n = len(root)
+    if keep == 'first':
+        return root == np.arange(n)
+    if keep != 'central':
+        raise ValueError("keep must be 'first' or 'central', not {!r}".format(keep))
+    if a2 is None or np.shape(a2) != (n,):
+        raise ValueError("keep='central' needs a2 [{}], the squared distances to the assigned centres".format(n))
+    order = np.lexsort((np.arange(n), np.asarray(a2, np.float64), root))  # by group, then a2, then position
+    head = np.ones(n, bool)
+    head[1:] = root[order[1:]] != root[order[:-1]]
+    kept = np.zeros(n, bool)
+    kept[order[head]] = True
+    return kept
+
+
+def pair_similarity(n, offsets, pair_j, pair_cos):
+    """float64 [n]: the largest cosine among a row's pairs, earlier or later; -inf for a row in no pair"""
+    sim = np.full(int(n), -np.inf)
+    later = np.repeat(np.arange(int(n)), np.diff(np.asarray(offsets, np.int64)))
+    np.maximum.at(sim, later, pair_cos)
+    np.maximum.at(sim, np.asarray(pair_j, np.int64), pair_cos)
+    return sim
+
+
+def _size_bins(sizes):
+    """group sizes >= 2 counted in the bins 2, 3-4, 5-8, ...: (2^(b-1), 2^b], up to the bin of the largest"""
+    sizes = np.asarray(sizes, np.int64)
+    bins = OrderedDict()
+    if len(sizes):
+        b = np.ceil(np.log2(sizes)).astype(np.int64)  # exact for the powers of two: log2 of a float64 power of two is exact
+        for e in range(1, int(b.max()) + 1):
+            bins["2" if e == 1 else "{}-{}".format(2 ** (e - 1) + 1, 2 ** e)] = int((b == e).sum())
+    return bins
+
+
+def summarise_groups(best, partner, labels, k, threshold, offsets, root, kept, keep='first'):
+    """the report of a groups run (pure numpy): summarise's dictionary and pairs (offsets[n]), groups (the components of two
+    rows or more), removed (the rows not kept), removed_beyond_nearest_rule (the removed rows the nearest-earlier rule does not
+    flag), group_size_counts (bins 2, 3-4, 5-8, ... by powers of two), largest_groups (the ten largest, ties to the lower
+    root: size, cluster, kept row) and keep"""
+    report = summarise(best, partner, labels, k, threshold)
+    n = report['n']
+    root, kept, lab = np.asarray(root, np.int64), np.asarray(kept, bool), np.asarray(labels, np.int64)
+    offsets = np.asarray(offsets, np.int64)
+    if root.shape != (n,) or kept.shape != (n,) or offsets.shape != (n + 1,):
+        raise ValueError("root {}, kept {} and offsets {} do not belong to {} rows".format(root.shape, kept.shape, offsets.shape, n))
+    size = np.bincount(root, minlength=n)  # at the roots
+    groups = np.flatnonzero(size >= 2)
+    if (kept[size[root] < 2] != True).any() or (np.bincount(root[kept], minlength=n)[groups] != 1).any():  # noqa: E712
+        raise ValueError("kept does not keep every row outside the groups and exactly one row of every group")
+    kept_of = np.full(n, -1, np.int64)
+    kept_of[root[kept]] = np.flatnonzero(kept)
+    largest = groups[np.argsort(-size[groups], kind='stable')[:10]]
+    report.update([
+        ('pairs', int(offsets[n])), ('groups', int(len(groups))), ('removed', int((~kept).sum())),
+        ('removed_beyond_nearest_rule', int((~kept & ~flag(best, threshold)).sum())),
+        ('group_size_counts', _size_bins(size[groups])),
+        ('largest_groups', [OrderedDict([('size', int(size[g])), ('cluster', int(lab[g])), ('kept', int(kept_of[g]))]) for g in largest]),
+        ('keep', keep)])
+    return report
 
 
 def flag(best, threshold):
@@ -295,6 +440,36 @@ def check_probes(opts, k=None):
     return int(m)
 
 
+def check_groups(opts):
+    """the keys of the groups mode -> (groups, keep, max_pairs, groups_path); groups False: the nearest-earlier run of today.
+    dedup.keep, dedup.max_pairs and dedup.groups_path are refused without dedup.groups=True, and dedup.groups with
+    dedup.against_path or dedup.probes > 1.  Pure: no device, no file"""
+    opts = opts or {}
+    groups, keep, max_pairs, groups_path = opts.get('groups'), opts.get('keep'), opts.get('max_pairs'), opts.get('groups_path')
+    if groups is not None and not isinstance(groups, bool):
+        raise ValueError("dedup.groups must be True or False, not {!r}".format(groups))
+    if not groups:
+        for key, value in (('keep', keep), ('max_pairs', max_pairs), ('groups_path', groups_path)):
+            if value is not None:
+                raise ValueError("dedup.{} is only valid with --dedup.groups=True".format(key))
+        return False, None, None, None
+    if opts.get('against_path') is not None:
+        raise ValueError("dedup.groups is refused with dedup.against_path: which pool rows copy a held-out row is a bipartite "
+                         "question, there are no groups among the pool rows")
+    probes = opts.get('probes')
+    if probes is not None and probes != 1:
+        raise ValueError("dedup.groups is refused with dedup.probes > 1: the pairs of the probed clusters are a follow-up; "
+                         "use dedup.probes=1, the pairs inside the clusters")
+    keep = 'first' if keep is None else keep
+    if keep not in ('first', 'central'):
+        raise ValueError("dedup.keep must be 'first' or 'central', not {!r}".format(keep))
+    if max_pairs is not None and (isinstance(max_pairs, bool) or not isinstance(max_pairs, numbers.Integral) or int(max_pairs) < 1):
+        raise ValueError("dedup.max_pairs must be a positive integer, not {!r}".format(max_pairs))
+    if groups_path is not None and (not isinstance(groups_path, str) or not groups_path):
+        raise ValueError("dedup.groups_path must be a csv path, not {!r}".format(groups_path))
+    return True, keep, MAX_PAIRS if max_pairs is None else int(max_pairs), groups_path
+
+
 def check_options(opts, views=None, epoch=None, k=None):
     """the `dedup` options -> (threshold, view, out_path, report_path).  Pure: no device, no file.  views: the names
     "<model_key>/<layer>" the cache holds, once it is known (None: dedup.view is only checked for its form); epoch:
@@ -303,6 +478,7 @@ def check_options(opts, views=None, epoch=None, k=None):
     opts = opts or {}
     check_against_options(opts)
     check_probes(opts, k)
+    check_groups(opts)
     thr = opts.get('threshold')
     if thr is None:
         raise ValueError("dedup needs --dedup.threshold=<t in (0, 1]>: the cosine from which a row counts as a duplicate of an "
@@ -402,6 +578,10 @@ def dedup(args):
         raise RuntimeError("the shards delivered {} rows, their metadata states {}: fix the metadata or drop the unreadable shards "
                            "from the list".format(base, n_total))
     labels, _ = km.calc_best(x, need_mean=False)  # a row's label is a pure function of the row and the state
+    groups_mode, keep, max_pairs, groups_path = check_groups(opts)
+    if groups_mode:
+        return _dedup_groups(args, km, x, labels, K, threshold, keep, max_pairs, view, epoch, out_path, groups_path, report_path,
+                             (shard_name, filename))
     lists = each = None
     if probes == 1:
         best, partner = nearest_earlier(x, labels, k=K)
@@ -420,6 +600,58 @@ def dedup(args):
     _print_probe_curve(report)
     _write_report(report_path, report)
     return report
+
+
+def _dedup_groups(args, km, x, labels, K, threshold, keep, max_pairs, view, epoch, out_path, groups_path, report_path, names):
+    """the groups mode of the verb: every pair over the threshold, their connected components, one kept row per group"""
+    best, partner, offsets, pair_j, pair_cos = pairs_earlier(x, labels, threshold, k=K, max_pairs=max_pairs)
+    n = len(best)
+    root = components(n, offsets, pair_j)
+    a2 = km.quality(x, labels, rows=True)[1][:, 0] if keep == 'central' else None
+    kept = choose_kept(root, keep, a2)
+    report = summarise_groups(best, partner, _host(labels), K, threshold, offsets, root, kept, keep)
+    report.update(view=view, epoch=int(epoch), feature_path=str(args.data.path), clusters_path=str(args.data.output.path))
+    out_path = _write_removed_csv(out_path, root, kept, pair_similarity(n, offsets, pair_j, pair_cos), names)
+    if groups_path is not None:
+        _write_groups_csv(groups_path, root, kept, names)
+    print("dedup: view {} epoch {}: {} groups at cosine >= {!r} ({} pairs), {} of {} rows removed (keep={}), {} of them beyond the "
+          "nearest-earlier rule; wrote {}".format(view, epoch, report['groups'], threshold, report['pairs'], report['removed'],
+                                                  report['n'], keep, report['removed_beyond_nearest_rule'], out_path))
+    print("groups of size " + "  ".join("{}: {}".format(b, c) for b, c in report['group_size_counts'].items()))
+    _write_report(report_path, report)
+    return report
+
+
+def _write_removed_csv(out_path, root, kept, similarity, names):
+    """the rows that are not kept, in row order: shard_name,filename of the row, then of the kept row of its group, then
+    repr(similarity) -- the largest cosine among the row's pairs -- and the group's size; overwritten"""
+    out_path = Path(out_path)
+    out_path.parent.mkdir(parents=True, exist_ok=True)
+    n = len(root)
+    size = np.bincount(root, minlength=n)
+    kept_of = np.full(n, -1, np.int64)
+    kept_of[root[kept]] = np.flatnonzero(kept)
+    with open(out_path, 'w', newline='') as f:
+        writer = csv.writer(f)
+        for i in np.flatnonzero(~np.asarray(kept, bool)):
+            j = int(kept_of[root[i]])
+            writer.writerow([names[0][i], names[1][i], names[0][j], names[1][j], repr(float(similarity[i])), int(size[root[i]])])
+    return out_path
+
+
+def _write_groups_csv(groups_path, root, kept, names):
+    """every member of every group, kept ones included, by group (the row number of its root) and then by row:
+    group,group_size,kept (1 or 0),shard_name,filename; overwritten"""
+    groups_path = Path(groups_path)
+    groups_path.parent.mkdir(parents=True, exist_ok=True)
+    n = len(root)
+    size = np.bincount(root, minlength=n)
+    members = np.flatnonzero(size[root] >= 2)
+    with open(groups_path, 'w', newline='') as f:
+        writer = csv.writer(f)
+        for i in members[np.argsort(root[members], kind='stable')]:
+            writer.writerow([int(root[i]), int(size[root[i]]), int(bool(kept[i])), names[0][i], names[1][i]])
+    return groups_path
 
 
 def _print_probe_curve(report):

@@ -348,6 +348,24 @@ class KMeans:
         lists = self.probe_centers(batch, probes, labels) if probes != 1 else None
         return nearest_earlier(batch, labels, k=self._shape[0], device="cuda:{}".format(self._device), probes=lists)
 
+    def duplicate_groups(self, batch, threshold, labels=None, keep='first'):
+        """The groups of rows that cosines >= threshold inside a cluster connect (clustering/dedup.py: pairs_earlier,
+        components, choose_kept) -> (root int64 [b]: the lowest row of every row's group, the row itself outside the groups;
+        kept bool [b]: True outside the groups and for one row per group).  keep='first': the root; 'central': the member
+        nearest to its centre (quality(rows=True)'s a2, ties to the lower row).  labels=None: calc_best(batch,
+        need_mean=False)'s.  Unlike near_duplicates' flags the groups do not depend on the order of the rows."""
+        from .dedup import choose_kept, components, pairs_earlier
+        self._require_handle()
+        if keep not in ('first', 'central'):
+            raise ValueError("keep must be 'first' or 'central', not {!r}".format(keep))
+        if labels is None:
+            labels, _ = self.calc_best(batch, need_mean=False)
+        _best, _partner, offsets, pair_j, _cos = pairs_earlier(batch, labels, threshold, k=self._shape[0],
+                                                               device="cuda:{}".format(self._device))
+        root = components(len(offsets) - 1, offsets, pair_j)
+        a2 = self.quality(batch, labels, rows=True)[1][:, 0] if keep == 'central' else None
+        return root, choose_kept(root, keep, a2)
+
     def near_duplicates_in(self, batch, other, blocking='cluster', probes=1):
         """For every row of batch the largest cosine to a row of the held-out rows `other` and that row (clustering/dedup.py,
         acav_rows_crossdup) -> (best float64 [b], partner int64 [b], a position in other; -inf and -1 for a row without one).

@@ -199,6 +199,12 @@ CLUSTERING_DEFAULTS = {
     #   dedup.against_meta_path  required with against_path: the metadata directory of the held-out shards
     #   dedup.blocking           only with against_path: none (default; every pair, n m of them) or cluster (a pool row meets
     #                            only the held-out rows that calc_best gives its label)
+    #   dedup.groups       True: every pair of a cluster at cosine >= threshold, their connected components, one kept row per
+    #                      group; out_path then lists the rows NOT kept: shard_name,filename,kept_shard_name,kept_filename,
+    #                      similarity,group_size.  Refused with against_path and with probes > 1.  The next three need it:
+    #   dedup.keep         first (default: a group's first row in shard order) or central (the member nearest to its centre)
+    #   dedup.max_pairs    the most pairs a run may hold (default 2^27, 16 bytes each on the device and on the host)
+    #   dedup.groups_path  optional: every member of every group, group,group_size,kept,shard_name,filename
     'debug': False,
 }
 

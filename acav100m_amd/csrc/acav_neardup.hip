@@ -44,6 +44,14 @@
 // a row's at most m entry results in slot order, the larger cosine first, then the lower position.  In the in-set use a tile
 // of entries late in a cluster walks a prefix of the run: the triangle, m times.  probedup_entries and probedup_tiles build
 // entries and tile list on the host; acav_rows_probedup_plan exposes them, the entry point launches from them.
+//
+// Every pair over a threshold (acav_rows_neardup_pairs; dedup.pairs_earlier, `dedup --dedup.groups=True`): the graph of which
+// (best, partner) is the nearest-earlier forest, in two sweeps of k_neardup's stage loop (k_neardup_pairs, a sibling kernel:
+// k_neardup is the text it was).  COUNT: the walker of a row also counts the columns of its range at cosine >= threshold; the
+// host sums the counts over input positions into offsets.  EMIT, over the tiles that hold a row with pairs (pairs_tiles filters
+// the count sweep's list, order kept): the walker stores those columns in ascending position from offsets[i] on, never at or
+// beyond offsets[i + 1]; a count that differs from the first raises a flag (ACAV_ESTATE).  No atomics, no sort; a pair's
+// cosine is the value the count sweep compared, the same chain.  acav_pairs_components: union-find on the host, no device.
 #include <algorithm>
 #include <cmath>
 #include <numeric>
@@ -289,6 +297,159 @@ __global__ __launch_bounds__(256, 2) void k_neardup(const float *__restrict__ x,
     }
 }
 
+// what the pair sweeps (acav_rows_neardup_pairs) carry beside k_neardup's arguments.  deg / offsets: by INPUT position
+struct NdPairs {
+    double threshold;
+    int *deg;                // count sweep: the columns of a row's range at cosine >= threshold
+    const int64_t *offsets;  // emit sweep [n + 1]: row i's pairs go to [offsets[i], offsets[i + 1])
+    int64_t *pair_j;         // emit sweep: the input position of the column
+    double *pair_cos;        // emit sweep: its cosine (NULL: not wanted)
+    int *mismatch;           // emit sweep: set when a row's count differs from offsets[i + 1] - offsets[i]
+};
+
+enum { ND_COUNT = 1, ND_EMIT = 2 };
+
+// the count sweep (MODE ND_COUNT) and the emit sweep (ND_EMIT) of acav_rows_neardup_pairs: k_neardup's arguments, stage loop,
+// operands and cosine tile -- a cosine is the same chain in all three.  Count: the walker of a row keeps (top, arg) as k_neardup
+// does and counts the columns of its range at cosine >= threshold into pr.deg.  Emit, over the tiles that hold a row with
+// pairs: the walker writes those columns in ascending position from offsets[i] on; best and partner are not touched
+template <int RT, bool VEC, int MODE>
+__global__ __launch_bounds__(256, 2) void k_neardup_pairs(const float *__restrict__ x, int d, int n, const int *__restrict__ perm,
+                                                          const int *__restrict__ rstart, const double *__restrict__ nrm,
+                                                          const NdTile *__restrict__ tiles, double *__restrict__ best,
+                                                          int64_t *__restrict__ partner, const NdPairs pr)
+{
+    constexpr int QM = ND_QM * RT;
+    extern __shared__ double nd_smem[];
+    double *cosv = nd_smem;                          // [QM][ND_CS], after the last chunk of a block
+    float *qs = reinterpret_cast<float *>(nd_smem);  // [QM][ND_ST]
+    float *cs = qs + QM * ND_ST;                     // [ND_CN][ND_ST]
+
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int fr = lane & 15, fq = lane >> 4;  // fragment row (A) / column (B) and k index of this lane
+    const int lq = t & 7, lr = t >> 3;         // this thread stages columns 4 lq .. 4 lq + 3 of the rows lr + 32 u
+    const NdTile tile = tiles[blockIdx.x];
+    const int q0 = tile.q0, q1 = tile.q0 + tile.rows;  // q1 <= n
+    const double inf = __builtin_inf();
+
+    // the query rows this thread stages, and the ones whose results it holds
+    const float *qrow[2 * RT];
+    bool qok[2 * RT];
+#pragma unroll
+    for (int u = 0; u < 2 * RT; ++u) {
+        const int q = q0 + lr + 32 * u;
+        qok[u] = q < q1;
+        qrow[u] = x + (size_t)perm[qok[u] ? q : q0] * d;
+    }
+    double qn[RT][4];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {  // C/D of the f64 MFMA: column = lane & 15, row = (lane >> 4) + 4 * register
+            const int q = q0 + wave * 16 * RT + rt * 16 + fq + 4 * r;
+            qn[rt][r] = nrm[q < q1 ? q : q0];
+        }
+    // the walk: thread t < QM owns query row t of the tile; a zero row has no partner and is none
+    const int my_pos = q0 + t;
+    const bool walker = t < QM && my_pos < q1;
+    const int my_lo = walker && nrm[my_pos] > 0.0 ? rstart[my_pos] : n;  // its columns: the sorted positions [my_lo, my_pos)
+    double top = -inf;
+    int arg = -1;
+    int cnt = 0;              // the columns met so far at cosine >= threshold
+    int64_t at = 0, end = 0;  // ND_EMIT: where the next pair goes, and where the row's room ends
+    if (MODE == ND_EMIT && walker) {
+        const size_t o = (size_t)perm[my_pos];
+        at = pr.offsets[o], end = pr.offsets[o + 1];
+    }
+
+    for (int cb = tile.cb0; cb < tile.cb0 + tile.blocks; ++cb) {
+        const int c0 = cb * ND_CN;  // c0 <= q1 - 1 < n
+        const float *crow[2];
+        bool cok[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int c = c0 + lr + 32 * u;
+            cok[u] = c < n;
+            crow[u] = x + (size_t)perm[cok[u] ? c : c0] * d;
+        }
+        f64x4 acc[RT][4];
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+            for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = f64x4{0.0, 0.0, 0.0, 0.0};
+        float4 pq[2 * RT], pc[2];  // the next chunk, in flight while the current one is multiplied
+#pragma unroll
+        for (int u = 0; u < 2 * RT; ++u) pq[u] = nd_fetch<VEC>(qrow[u], d, 4 * lq);
+#pragma unroll
+        for (int u = 0; u < 2; ++u) pc[u] = nd_fetch<VEC>(crow[u], d, 4 * lq);
+        for (int j0 = 0; j0 < d; j0 += ND_DK) {
+            __syncthreads();  // the previous stage has been read (and the previous block's cosine tile walked)
+#pragma unroll
+            for (int u = 0; u < 2 * RT; ++u)
+                *reinterpret_cast<float4 *>(&qs[(lr + 32 * u) * ND_ST + 4 * lq]) = nd_mask(pq[u], qok[u], d, j0 + 4 * lq);
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+                *reinterpret_cast<float4 *>(&cs[(lr + 32 * u) * ND_ST + 4 * lq]) = nd_mask(pc[u], cok[u], d, j0 + 4 * lq);
+            __syncthreads();
+            if (j0 + ND_DK < d) {
+#pragma unroll
+                for (int u = 0; u < 2 * RT; ++u) pq[u] = nd_fetch<VEC>(qrow[u], d, j0 + ND_DK + 4 * lq);
+#pragma unroll
+                for (int u = 0; u < 2; ++u) pc[u] = nd_fetch<VEC>(crow[u], d, j0 + ND_DK + 4 * lq);
+            }
+#pragma unroll
+            for (int kk = 0; kk < ND_DK / 4; ++kk) {
+                double a[RT], b[4];
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt) a[rt] = (double)qs[(wave * 16 * RT + rt * 16 + fr) * ND_ST + kk * 4 + fq];
+#pragma unroll
+                for (int ct = 0; ct < 4; ++ct) b[ct] = (double)cs[(ct * 16 + fr) * ND_ST + kk * 4 + fq];
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                    for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[rt], b[ct], acc[rt][ct], 0, 0, 0);
+            }
+        }
+        __syncthreads();  // every wave has read the last stage: the cosine tile goes over it
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct) {
+            const int c = c0 + ct * 16 + fr;
+            const double cn = nrm[c < n ? c : n - 1];
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    cosv[(wave * 16 * RT + rt * 16 + fq + 4 * r) * ND_CS + ct * 16 + fr] =
+                        cn > 0.0 ? acc[rt][ct][r] / sqrt(qn[rt][r] * cn) : -inf;  // a zero row is never a partner
+        }
+        __syncthreads();
+        if (walker) {
+            const int lo = my_lo > c0 ? my_lo : c0, hi = my_pos < c0 + ND_CN ? my_pos : c0 + ND_CN;
+            const double *mine = cosv + t * ND_CS;
+            for (int c = lo; c < hi; ++c) {
+                const double v = mine[c - c0];
+                if (MODE == ND_COUNT && v > top) top = v, arg = c;  // strict: the lowest position keeps a tie
+                if (v >= pr.threshold) {
+                    if (MODE == ND_EMIT && at + cnt < end) {  // never at or beyond offsets[i + 1], whatever the counts say
+                        pr.pair_j[at + cnt] = (int64_t)perm[c];
+                        if (pr.pair_cos) pr.pair_cos[at + cnt] = v;
+                    }
+                    ++cnt;
+                }
+            }
+        }
+    }
+    if (walker) {
+        const size_t o = (size_t)perm[my_pos];
+        if (MODE == ND_COUNT) {
+            best[o] = top;
+            partner[o] = arg >= 0 ? (int64_t)perm[arg] : (int64_t)-1;
+            pr.deg[o] = cnt;
+        }
+        if (MODE == ND_EMIT && (int64_t)cnt != end - at) *pr.mismatch = 1;  // inconsistent inputs: the entry returns ACAV_ESTATE
+    }
+}
+
 int use_device(int device, int *cus)
 {
     int n = 0;
@@ -333,6 +494,37 @@ int launch(const NdPlan &plan, bool vec, hipStream_t st, const float *x, int d, 
                            tiles, best, partner);
     ACAV_HIP_TRY(hipGetLastError());
     return ACAV_OK;
+}
+
+// one of the two pair sweeps over `count` entries of `tiles`
+template <int RT, int MODE>
+int launch_pairs(int64_t count, bool vec, hipStream_t st, const float *x, int d, int n, const int *perm, const int *rstart,
+                 const double *nrm, const NdTile *tiles, double *best, int64_t *partner, const NdPairs &pr)
+{
+    const void *fn = vec ? reinterpret_cast<const void *>(k_neardup_pairs<RT, true, MODE>)
+                         : reinterpret_cast<const void *>(k_neardup_pairs<RT, false, MODE>);
+    ACAV_HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)neardup_lds(RT)));
+    if (vec)
+        hipLaunchKernelGGL((k_neardup_pairs<RT, true, MODE>), dim3((unsigned)count), dim3(256), neardup_lds(RT), st, x, d, n, perm,
+                           rstart, nrm, tiles, best, partner, pr);
+    else
+        hipLaunchKernelGGL((k_neardup_pairs<RT, false, MODE>), dim3((unsigned)count), dim3(256), neardup_lds(RT), st, x, d, n, perm,
+                           rstart, nrm, tiles, best, partner, pr);
+    ACAV_HIP_TRY(hipGetLastError());
+    return ACAV_OK;
+}
+
+// the emit sweep's tile list: the entries of the count sweep's list (descending blocks, ties by ascending tile) whose tile
+// holds a row with pairs, in that order.  has_pairs [tiles]: by TILE INDEX q0 / H, nonzero when the tile holds such a row.
+// Returns the column blocks the kept tiles walk together
+int64_t pairs_tiles(const std::vector<NdTile> &list, int rt, const unsigned char *has_pairs, std::vector<NdTile> *kept)
+{
+    const int qm = ND_QM * rt;
+    int64_t blocks = 0;
+    kept->clear();
+    for (const NdTile &e : list)
+        if (has_pairs[e.q0 / qm]) kept->push_back(e), blocks += e.blocks;
+    return blocks;
 }
 
 // ---- acav_rows_crossdup: the pool piece x [n] against the held-out set y [m]
@@ -671,6 +863,83 @@ int check_hist(const int64_t *hist, int k, const char *what, int64_t *sum)
     return ACAV_OK;
 }
 
+// what acav_rows_neardup and acav_rows_neardup_pairs do up to their sweep, and the way their (best, partner) come home: the rows
+// and labels on the device, the checks of labels and values, the positions by label with their run starts, the tile list, the
+// norms.  Declared AFTER the DevBufs an entry adds: its drain then idles the stream before any of them goes back to the pool
+struct NdSetup {
+    DevBuf stage_x, stage_lab, bad, ints, nrm, dtiles, obest, opartner;
+    StreamDrain drain;      // after the buffers: destroyed before them
+    std::vector<int> host;  // perm [n]: the positions by label, stably; rstart [n]: per sorted position the start of its run
+    std::vector<NdTile> list;
+    NdPlan plan;
+    const float *xd = nullptr;
+    const int *dperm = nullptr, *drstart = nullptr;
+    double *dbest = nullptr;
+    int64_t *dpartner = nullptr;
+    bool vec = false, best_dev = false, partner_dev = false;
+
+    explicit NdSetup(hipStream_t st) : drain{st} {}
+
+    // ACAV_EINVAL for a label outside [0, k) or a value that is not finite, before anything is indexed with a label
+    int prepare(const float *x, int64_t n, int d, const int64_t *labels, int k, int cus, double *best, int64_t *partner, hipStream_t st)
+    {
+        const void *dx = nullptr, *dl = nullptr;
+        const size_t total = (size_t)n * d;
+        ACAV_TRY(to_device(x, sizeof(float) * total, stage_x, st, &dx));
+        ACAV_TRY(to_device(labels, sizeof(int64_t) * (size_t)n, stage_lab, st, &dl));
+        xd = static_cast<const float *>(dx);
+        ACAV_TRY(bad.ensure(sizeof(unsigned long long) * 2));  // [0] labels out of range (its low word), [1] values not finite
+        ACAV_HIP_TRY(hipMemsetAsync(bad.p, 0, sizeof(unsigned long long) * 2, st));
+        hipLaunchKernelGGL(k_nd_labels, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, st,
+                           static_cast<const int64_t *>(dl), n, k, bad.as<unsigned>());
+        ACAV_HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_nd_finite, dim3((unsigned)std::min<size_t>((total + 255) / 256, (size_t)cus * 8)), dim3(256), 0, st, xd,
+                           total, bad.as<unsigned long long>() + 1);
+        ACAV_HIP_TRY(hipGetLastError());
+        unsigned long long nbad[2] = {0, 0};
+        std::vector<int64_t> lab((size_t)n);
+        ACAV_HIP_TRY(hipMemcpyAsync(nbad, bad.p, sizeof(nbad), hipMemcpyDeviceToHost, st));
+        ACAV_HIP_TRY(hipMemcpyAsync(lab.data(), dl, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+        ACAV_HIP_TRY(hipStreamSynchronize(st));
+        ACAV_REQUIRE(nbad[0] == 0, ACAV_EINVAL, "%llu of %lld labels are outside [0, %d)", nbad[0], (long long)n, k);
+        ACAV_REQUIRE(nbad[1] == 0, ACAV_EINVAL, "%llu of the %lld x %d values are not finite (inf or NaN)", nbad[1], (long long)n, d);
+
+        // the positions by label, stably; per sorted position the start of its run; the label histogram for the tile list
+        host.resize((size_t)(2 * n));
+        int *perm = host.data(), *rstart = perm + n;
+        sort_by_label(lab, n, k, perm);
+        std::vector<int64_t> runs;  // the histogram without its empty labels: the same tiles
+        for (int64_t c = 0, first = 0; c < n; ++c) {
+            if (c == 0 || lab[(size_t)perm[c]] != lab[(size_t)perm[c - 1]]) first = c, runs.push_back(0);
+            rstart[c] = (int)first;
+            ++runs.back();
+        }
+        plan = neardup_tiles(runs.data(), (int)runs.size(), d, cus, &list);
+
+        best_dev = is_device_ptr(best), partner_dev = is_device_ptr(partner);
+        ACAV_TRY(upload(ints, host.data(), sizeof(int) * host.size(), st));
+        ACAV_TRY(upload(dtiles, list.data(), sizeof(NdTile) * list.size(), st));
+        ACAV_TRY(nrm.ensure(sizeof(double) * (size_t)n));
+        if (!best_dev) ACAV_TRY(obest.ensure(sizeof(double) * (size_t)n));
+        if (!partner_dev) ACAV_TRY(opartner.ensure(sizeof(int64_t) * (size_t)n));
+        dbest = best_dev ? best : obest.as<double>();
+        dpartner = partner_dev ? partner : opartner.as<int64_t>();
+        dperm = ints.as<int>(), drstart = dperm + n;
+        vec = d % 4 == 0 && (reinterpret_cast<uintptr_t>(xd) & 15) == 0;
+        hipLaunchKernelGGL(k_nd_norms, dim3((unsigned)n), dim3(64), 0, st, xd, d, dperm, nrm.as<double>());
+        ACAV_HIP_TRY(hipGetLastError());
+        return ACAV_OK;
+    }
+
+    // (best, partner) to host pointers, async on st
+    int fetch(double *best, int64_t *partner, int64_t n, hipStream_t st)
+    {
+        if (!best_dev) ACAV_HIP_TRY(hipMemcpyAsync(best, obest.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
+        if (!partner_dev) ACAV_HIP_TRY(hipMemcpyAsync(partner, opartner.p, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+        return ACAV_OK;
+    }
+};
+
 }  // namespace
 
 ACAV_EXPORT int acav_rows_neardup_plan(const int64_t *hist, int k, int d, int cus, int64_t *out, int64_t *tiles, int64_t cap)
@@ -708,61 +977,158 @@ ACAV_EXPORT int acav_rows_neardup(int device, const float *x, int64_t n, int d, 
     ACAV_TRY(use_device(device, &cus));
     hipStream_t st = static_cast<hipStream_t>(stream);
 
-    DevBuf stage_x, stage_lab, bad, ints, nrm, dtiles, obest, opartner;
-    StreamDrain drain = {st};
-    const void *dx = nullptr, *dl = nullptr;
-    const size_t total = (size_t)n * d;
-    ACAV_TRY(to_device(x, sizeof(float) * total, stage_x, st, &dx));
-    ACAV_TRY(to_device(labels, sizeof(int64_t) * (size_t)n, stage_lab, st, &dl));
-    const float *xd = static_cast<const float *>(dx);
-    ACAV_TRY(bad.ensure(sizeof(unsigned long long) * 2));  // [0] labels out of range (its low word), [1] values not finite
-    ACAV_HIP_TRY(hipMemsetAsync(bad.p, 0, sizeof(unsigned long long) * 2, st));
-    hipLaunchKernelGGL(k_nd_labels, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, st,
-                       static_cast<const int64_t *>(dl), n, k, bad.as<unsigned>());
-    ACAV_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_nd_finite, dim3((unsigned)std::min<size_t>((total + 255) / 256, (size_t)cus * 8)), dim3(256), 0, st, xd, total,
-                       bad.as<unsigned long long>() + 1);
-    ACAV_HIP_TRY(hipGetLastError());
-    unsigned long long nbad[2] = {0, 0};
-    std::vector<int64_t> lab((size_t)n);
-    ACAV_HIP_TRY(hipMemcpyAsync(nbad, bad.p, sizeof(nbad), hipMemcpyDeviceToHost, st));
-    ACAV_HIP_TRY(hipMemcpyAsync(lab.data(), dl, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, st));
-    ACAV_HIP_TRY(hipStreamSynchronize(st));
-    ACAV_REQUIRE(nbad[0] == 0, ACAV_EINVAL, "%llu of %lld labels are outside [0, %d)", nbad[0], (long long)n, k);
-    ACAV_REQUIRE(nbad[1] == 0, ACAV_EINVAL, "%llu of the %lld x %d values are not finite (inf or NaN)", nbad[1], (long long)n, d);
-
-    // the positions by label, stably; per sorted position the start of its run; the label histogram for the tile list
-    std::vector<int> host((size_t)(2 * n));
-    int *perm = host.data(), *rstart = perm + n;
-    sort_by_label(lab, n, k, perm);
-    std::vector<int64_t> runs;  // the histogram without its empty labels: the same tiles
-    for (int64_t c = 0, first = 0; c < n; ++c) {
-        if (c == 0 || lab[(size_t)perm[c]] != lab[(size_t)perm[c - 1]]) first = c, runs.push_back(0);
-        rstart[c] = (int)first;
-        ++runs.back();
-    }
-    std::vector<NdTile> list;
-    const NdPlan plan = neardup_tiles(runs.data(), (int)runs.size(), d, cus, &list);
-
-    const bool best_dev = is_device_ptr(best), partner_dev = is_device_ptr(partner);
-    ACAV_TRY(upload(ints, host.data(), sizeof(int) * host.size(), st));
-    ACAV_TRY(upload(dtiles, list.data(), sizeof(NdTile) * list.size(), st));
-    ACAV_TRY(nrm.ensure(sizeof(double) * (size_t)n));
-    if (!best_dev) ACAV_TRY(obest.ensure(sizeof(double) * (size_t)n));
-    if (!partner_dev) ACAV_TRY(opartner.ensure(sizeof(int64_t) * (size_t)n));
-    double *dbest = best_dev ? best : obest.as<double>();
-    int64_t *dpartner = partner_dev ? partner : opartner.as<int64_t>();
-    const int *dperm = ints.as<int>(), *drstart = dperm + n;
-    const bool vec = d % 4 == 0 && (reinterpret_cast<uintptr_t>(xd) & 15) == 0;
-    hipLaunchKernelGGL(k_nd_norms, dim3((unsigned)n), dim3(64), 0, st, xd, d, dperm, nrm.as<double>());
-    ACAV_HIP_TRY(hipGetLastError());
-    if (plan.rt == 2)
-        ACAV_TRY(launch<2>(plan, vec, st, xd, d, (int)n, dperm, drstart, nrm.as<double>(), dtiles.as<NdTile>(), dbest, dpartner));
+    NdSetup S(st);
+    ACAV_TRY(S.prepare(x, n, d, labels, k, cus, best, partner, st));
+    if (S.plan.rt == 2)
+        ACAV_TRY(launch<2>(S.plan, S.vec, st, S.xd, d, (int)n, S.dperm, S.drstart, S.nrm.as<double>(), S.dtiles.as<NdTile>(), S.dbest,
+                           S.dpartner));
     else
-        ACAV_TRY(launch<1>(plan, vec, st, xd, d, (int)n, dperm, drstart, nrm.as<double>(), dtiles.as<NdTile>(), dbest, dpartner));
-    if (!best_dev) ACAV_HIP_TRY(hipMemcpyAsync(best, obest.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
-    if (!partner_dev) ACAV_HIP_TRY(hipMemcpyAsync(partner, opartner.p, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+        ACAV_TRY(launch<1>(S.plan, S.vec, st, S.xd, d, (int)n, S.dperm, S.drstart, S.nrm.as<double>(), S.dtiles.as<NdTile>(), S.dbest,
+                           S.dpartner));
+    ACAV_TRY(S.fetch(best, partner, n, st));
     ACAV_HIP_TRY(hipStreamSynchronize(st));
+    return ACAV_OK;
+}
+
+ACAV_EXPORT int acav_rows_neardup_pairs_plan(const int64_t *hist, int k, int d, int cus, const unsigned char *has_pairs, int64_t *out,
+                                             int64_t *tiles, int64_t cap)
+{
+    ACAV_REQUIRE(hist && out && has_pairs, ACAV_EINVAL, "NULL argument");
+    ACAV_REQUIRE(k >= 1 && d >= 1 && d <= ND_MAX_D && cus > 0, ACAV_EINVAL, "bad sizes");
+    int64_t n = 0;
+    ACAV_TRY(check_hist(hist, k, "hist", &n));
+    std::vector<NdTile> list, kept;
+    const NdPlan p = neardup_tiles(hist, k, d, cus, &list);
+    const int64_t blocks = pairs_tiles(list, p.rt, has_pairs, &kept);
+    const int64_t emit = (int64_t)kept.size();
+    ACAV_REQUIRE(!tiles || cap >= emit, ACAV_EINVAL, "room for %lld tiles, the emit sweep launches %lld", (long long)cap, (long long)emit);
+    out[0] = (int64_t)ND_QM * p.rt, out[1] = p.tiles, out[2] = p.blocks, out[3] = emit, out[4] = blocks, out[5] = (int64_t)p.lds;
+    // the count sweep's scratch, a degree per row and the offsets; the pairs themselves are the caller's
+    out[6] = (int64_t)(p.scratch + sizeof(int) * (size_t)n + sizeof(int64_t) * ((size_t)n + 1) + sizeof(NdTile) * (size_t)emit);
+    if (tiles)
+        for (int64_t t = 0; t < emit; ++t) {
+            const NdTile &e = kept[(size_t)t];
+            tiles[4 * t] = e.q0, tiles[4 * t + 1] = e.rows, tiles[4 * t + 2] = e.cb0, tiles[4 * t + 3] = e.blocks;
+        }
+    return ACAV_OK;
+}
+
+ACAV_EXPORT int acav_rows_neardup_pairs(int device, const float *x, int64_t n, int d, const int64_t *labels, int k, double threshold,
+                                        double *best, int64_t *partner, int64_t *offsets, int64_t cap, int64_t *pair_j,
+                                        double *pair_cos, void *stream)
+{
+    ACAV_REQUIRE(x && labels && best && partner && offsets, ACAV_EINVAL, "NULL argument");
+    ACAV_REQUIRE(n >= 1 && n <= ND_MAX_N, ACAV_EINVAL, "n=%lld must be in [1, 2^31): positions are 32-bit", (long long)n);
+    ACAV_REQUIRE(d >= 1 && d <= ND_MAX_D, ACAV_EINVAL, "d=%d must be in [1, %d]", d, ND_MAX_D);
+    ACAV_REQUIRE(k >= 1, ACAV_EINVAL, "k=%d must be at least 1", k);
+    ACAV_REQUIRE(threshold > 0.0 && threshold <= 1.0, ACAV_EINVAL, "threshold=%g must be in (0, 1]", threshold);  // a NaN fails too
+    ACAV_REQUIRE(cap >= 0, ACAV_EINVAL, "cap=%lld must not be negative", (long long)cap);
+    ACAV_REQUIRE(cap == 0 || pair_j, ACAV_EINVAL, "cap=%lld with a NULL pair_j: room for pairs needs a place for them", (long long)cap);
+    int cus = 0;
+    ACAV_TRY(use_device(device, &cus));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+
+    DevBuf ddeg, doff, dkept, opj, opc, dflag;
+    NdSetup S(st);  // after them: its drain idles the stream first
+    ACAV_TRY(S.prepare(x, n, d, labels, k, cus, best, partner, st));
+    const NdPlan &plan = S.plan;
+    const std::vector<NdTile> &list = S.list;
+    const int *perm = S.host.data();
+    const float *xd = S.xd;
+    const int *dperm = S.dperm, *drstart = S.drstart;
+    const bool vec = S.vec;
+    DevBuf &nrm = S.nrm, &dtiles = S.dtiles;
+    ACAV_TRY(ddeg.ensure(sizeof(int) * (size_t)n));
+    NdPairs pr = {threshold, ddeg.as<int>(), nullptr, nullptr, nullptr, nullptr};
+    if (plan.rt == 2)
+        ACAV_TRY((launch_pairs<2, ND_COUNT>(plan.tiles, vec, st, xd, d, (int)n, dperm, drstart, nrm.as<double>(), dtiles.as<NdTile>(),
+                                            S.dbest, S.dpartner, pr)));
+    else
+        ACAV_TRY((launch_pairs<1, ND_COUNT>(plan.tiles, vec, st, xd, d, (int)n, dperm, drstart, nrm.as<double>(), dtiles.as<NdTile>(),
+                                            S.dbest, S.dpartner, pr)));
+    std::vector<int> deg((size_t)n);
+    ACAV_HIP_TRY(hipMemcpyAsync(deg.data(), ddeg.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));
+    ACAV_TRY(S.fetch(best, partner, n, st));
+    ACAV_HIP_TRY(hipStreamSynchronize(st));
+
+    // the offsets: the exclusive prefix sum of the degrees over INPUT positions
+    std::vector<int64_t> off((size_t)n + 1);
+    off[0] = 0;
+    for (int64_t i = 0; i < n; ++i) off[(size_t)i + 1] = off[(size_t)i] + deg[(size_t)i];
+    const int64_t pairs = off[(size_t)n];
+    const bool off_dev = is_device_ptr(offsets);
+    if (off_dev)
+        ACAV_HIP_TRY(hipMemcpyAsync(offsets, off.data(), sizeof(int64_t) * off.size(), hipMemcpyHostToDevice, st));
+    else
+        std::copy(off.begin(), off.end(), offsets);
+    if (pairs == 0 || pairs > cap) {  // nothing to emit, or no room: the caller compares offsets[n] with cap
+        ACAV_HIP_TRY(hipStreamSynchronize(st));
+        return ACAV_OK;
+    }
+
+    // the emit sweep over the tiles that hold a row with pairs
+    const int qm = ND_QM * plan.rt;
+    std::vector<unsigned char> has_pairs((size_t)plan.tiles, 0);
+    for (int64_t c = 0; c < n; ++c)
+        if (deg[(size_t)perm[c]] > 0) has_pairs[(size_t)(c / qm)] = 1;
+    std::vector<NdTile> kept;
+    pairs_tiles(list, plan.rt, has_pairs.data(), &kept);
+    const int64_t *doffsets = offsets;
+    if (!off_dev) {
+        ACAV_TRY(upload(doff, off.data(), sizeof(int64_t) * off.size(), st));
+        doffsets = doff.as<int64_t>();
+    }
+    ACAV_TRY(upload(dkept, kept.data(), sizeof(NdTile) * kept.size(), st));
+    const bool pj_dev = is_device_ptr(pair_j), pc_dev = pair_cos && is_device_ptr(pair_cos);
+    if (!pj_dev) ACAV_TRY(opj.ensure(sizeof(int64_t) * (size_t)pairs));
+    if (pair_cos && !pc_dev) ACAV_TRY(opc.ensure(sizeof(double) * (size_t)pairs));
+    ACAV_TRY(dflag.ensure(sizeof(int)));
+    ACAV_HIP_TRY(hipMemsetAsync(dflag.p, 0, sizeof(int), st));
+    pr.deg = nullptr, pr.offsets = doffsets, pr.pair_j = pj_dev ? pair_j : opj.as<int64_t>();
+    pr.pair_cos = !pair_cos ? nullptr : pc_dev ? pair_cos : opc.as<double>(), pr.mismatch = dflag.as<int>();
+    if (plan.rt == 2)
+        ACAV_TRY((launch_pairs<2, ND_EMIT>((int64_t)kept.size(), vec, st, xd, d, (int)n, dperm, drstart, nrm.as<double>(),
+                                           dkept.as<NdTile>(), nullptr, nullptr, pr)));
+    else
+        ACAV_TRY((launch_pairs<1, ND_EMIT>((int64_t)kept.size(), vec, st, xd, d, (int)n, dperm, drstart, nrm.as<double>(),
+                                           dkept.as<NdTile>(), nullptr, nullptr, pr)));
+    int mismatch = 0;
+    ACAV_HIP_TRY(hipMemcpyAsync(&mismatch, dflag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    if (!pj_dev) ACAV_HIP_TRY(hipMemcpyAsync(pair_j, opj.p, sizeof(int64_t) * (size_t)pairs, hipMemcpyDeviceToHost, st));
+    if (pair_cos && !pc_dev) ACAV_HIP_TRY(hipMemcpyAsync(pair_cos, opc.p, sizeof(double) * (size_t)pairs, hipMemcpyDeviceToHost, st));
+    ACAV_HIP_TRY(hipStreamSynchronize(st));
+    ACAV_REQUIRE(mismatch == 0, ACAV_ESTATE, "the emit sweep counted other pairs than the count sweep: the rows changed during the call");
+    return ACAV_OK;
+}
+
+ACAV_EXPORT int acav_pairs_components(int64_t n, const int64_t *offsets, const int64_t *pair_j, int64_t *root)
+{
+    ACAV_REQUIRE(n >= 1 && offsets && root, ACAV_EINVAL, "n=%lld must be at least 1, offsets and root not NULL", (long long)n);
+    ACAV_REQUIRE(offsets[0] == 0, ACAV_EINVAL, "offsets[0] = %lld must be 0", (long long)offsets[0]);
+    for (int64_t i = 0; i < n; ++i)
+        ACAV_REQUIRE(offsets[i + 1] >= offsets[i], ACAV_EINVAL, "offsets decrease at row %lld", (long long)i);
+    const int64_t pairs = offsets[n];
+    ACAV_REQUIRE(pairs == 0 || pair_j, ACAV_EINVAL, "%lld pairs and a NULL pair_j", (long long)pairs);
+    for (int64_t e = 0; e < pairs; ++e)
+        ACAV_REQUIRE(pair_j[e] >= 0 && pair_j[e] < n, ACAV_EINVAL, "pair_j[%lld] = %lld is outside [0, %lld)", (long long)e,
+                     (long long)pair_j[e], (long long)n);
+    // union-find in a table of its own (root stays untouched until nothing can be refused): path halving, no recursion; the
+    // lower root becomes the parent, so a root is the lowest position of its set
+    std::vector<int64_t> up((size_t)n);
+    std::iota(up.begin(), up.end(), (int64_t)0);
+    auto find = [&](int64_t a) {
+        while (up[(size_t)a] != a) {
+            up[(size_t)a] = up[(size_t)up[(size_t)a]];
+            a = up[(size_t)a];
+        }
+        return a;
+    };
+    for (int64_t i = 0; i < n; ++i)
+        for (int64_t e = offsets[i]; e < offsets[i + 1]; ++e) {
+            const int64_t a = find(i), b = find(pair_j[e]);
+            if (a != b) up[(size_t)std::max(a, b)] = std::min(a, b);
+        }
+    for (int64_t i = 0; i < n; ++i) root[i] = find(i);
     return ACAV_OK;
 }
 
