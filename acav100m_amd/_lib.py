@@ -67,6 +67,8 @@ SIGNATURES = {
     "acav_rows_neardup_pairs": [i32, vp, i64, i32, vp, i32, f64, vp, vp, vp, i64, vp, vp, vp],
     "acav_rows_neardup_pairs_plan": [vp, i32, i32, i32, vp, C.POINTER(i64), vp, i64],
     "acav_pairs_components": [i64, vp, vp, vp],
+    "acav_pairs_cosine": [i32, vp, i64, i32, vp, vp, i64, vp, vp],
+    "acav_pairs_cosine_plan": [i64, i32, i32, C.POINTER(i64)],
     "acav_rows_crossdup": [i32, vp, i64, vp, i64, i32, vp, vp, i32, vp, vp, vp],
     "acav_rows_crossdup_plan": [vp, vp, i32, i32, i32, C.POINTER(i64), vp, i64],
     "acav_rows_probedup": [i32, vp, i64, vp, i64, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp],
@@ -158,7 +160,7 @@ _FIRST_DEVICE_CALLS = ("acav_device_count", "acav_device_info", "acav_kmeans_cre
                        "acav_rows_scatter", "acav_rows_project", "acav_pair_scores", "acav_rank_desc", "acav_rows_absmax",
                        "acav_lloyd_accumulate", "acav_lloyd_centers", "acav_kmeanspp_weights", "acav_kmeanspp_seed", "acav_rows_silhouette",
                        "acav_rows_silhouette_range", "acav_rows_normalize", "acav_rows_neardup", "acav_rows_neardup_pairs", "acav_rows_crossdup",
-                       "acav_rows_probedup")
+                       "acav_rows_probedup", "acav_pairs_cosine")
 _device_touched = False
 
 

@@ -83,7 +83,25 @@ dedup.groups_path lists every member of every group, kept ones included, by grou
 root),group_size,kept,shard_name,filename.  The json is summarise_groups' dictionary plus the keys above.  More than
 dedup.max_pairs pairs (default 2^27) are refused with the total and the five clusters that hold the most.  The three keys need
 dedup.groups; the mode is refused with dedup.against_path (a bipartite question: no groups among pool rows) and with
-dedup.probes > 1 (the pairs of probed clusters are a follow-up).  tests/_dupgroups_np.py restates the definition."""
+dedup.probes > 1 (the pairs of probed clusters are a follow-up).  tests/_dupgroups_np.py restates the definition.
+
+Confirmation in a second view (`--dedup.confirm_view=<model_key>/<layer> --dedup.confirm_threshold=<t2 in (0, 1]>`, pair_rows /
+pair_cosines / confirm_pairs, KMeans.duplicate_groups(confirm=), acav_pairs_cosine): one view is a weak witness -- every lecture
+over the same static slide is a video duplicate, every clip with the same licensed song an audio duplicate, a true re-upload
+matches in both.  With view A = dedup.view, t = dedup.threshold, view B = dedup.confirm_view and cosB the cosine of B's rows:
+  P_i'       = { j in P_i : cosB(i, j) >= t2 }
+  roots, groups, kept and similarity are the definitions above over P' in place of P; similarity stays a cosine of view A, the
+  largest among the row's CONFIRMED pairs; keep=central keeps using view A's a2; the blocking is view A's clustering alone.
+The pass of today yields P; a second pass over the row groups gathers only the R rows that occur in a pair from view B -- through
+the front-end the cache holds for B, so B is compared in the space it was clustered in -- into a [R, dB] device buffer (refused
+with the sizes when it does not fit; B is never held in one piece, a streamed run reads the shards a second time; no pair in A:
+no second pass), acav_pairs_cosine gives cosB of the listed pairs with acav_rows_neardup's arithmetic, chain for chain, and the
+filtered list goes on to the components.  The files keep their layouts.  The report gains confirm_view, confirm_threshold,
+pairs_before_confirm (pairs: the confirmed ones), groups_before_confirm and removed_before_confirm (the components of A alone)
+and confirm_similarity_counts (A's pairs with cosB >= g over the grid: one run is enough to pick t2); flagged,
+similarity_counts and the nearest-earlier rule of removed_beyond_nearest_rule stay those of view A alone.  The two keys go
+together, need dedup.groups=True (the confirmed relation is a pair list, and the groups mode is the one that has it) and are
+refused with dedup.against_path.  tests/_dupconfirm_np.py restates the definition."""
 import csv
 import json
 import numbers
@@ -226,6 +244,55 @@ def components(n, offsets, pair_j):
         _lib.check(_lib.load_library().acav_pairs_components(int(n), _lib.ptr(offsets), _lib.ptr(pair_j) if len(pair_j) else None,
                                                              _lib.ptr(root)))
     return root
+
+
+def pair_cosines(x, pair_i, pair_j, device="cuda"):
+    """float64 [P]: the cosine of every listed pair (pair_i[e], pair_j[e]) of x [n, d] (acav_pairs_cosine); -inf where a row is
+    all zero.  Any indices in [0, n), in any order, i == j allowed.  x and the lists: numpy or torch, host or device.  For a pair
+    that pairs_earlier lists for the same x these are the bytes of its pair_cos."""
+    keep, xp, n, on_gpu = _as_f32_2d(x)
+    d = int(keep.shape[1])
+    pairs = int(pair_i.shape[0]) if hasattr(pair_i, "shape") else len(pair_i)
+    pi, pj = _labels(pair_i, pairs), _labels(pair_j, pairs)
+    cos = np.empty(pairs, np.float64)
+    dev = keep.device.index if on_gpu else _device_index(device)
+    _lib.check(_lib.load_library().acav_pairs_cosine(dev, xp, n, d, _lib.ptr(pi) if pairs else None, _lib.ptr(pj) if pairs else None,
+                                                     pairs, _lib.ptr(cos), None))
+    return cos
+
+
+def pair_rows(offsets, pair_j):
+    """(later int64 [P], rows int64 [R], ci int64 [P], cj int64 [P]) of a pair list (pure numpy): the later row of every pair,
+    the ascending unique rows that occur in any pair, and the pairs re-indexed into rows: rows[ci[e]] = later[e], rows[cj[e]] =
+    pair_j[e] -- a second view needs only those R rows"""
+    offsets, pair_j = np.asarray(offsets, np.int64), np.asarray(pair_j, np.int64)
+    later = np.repeat(np.arange(len(offsets) - 1, dtype=np.int64), np.diff(offsets))
+    if later.shape != pair_j.shape:
+        raise ValueError("offsets state {} pairs, pair_j holds {}".format(later.shape[0], pair_j.shape))
+    rows = np.unique(np.concatenate([later, pair_j]))
+    return later, rows, np.searchsorted(rows, later).astype(np.int64), np.searchsorted(rows, pair_j).astype(np.int64)
+
+
+def confirm_pairs(offsets, pair_j, pair_cos, keep):
+    """(offsets int64 [n + 1], pair_j int64 [P'], pair_cos float64 [P']) of the pairs where keep bool [P] is True (pure numpy):
+    the same layout, the order inside a row preserved; a row all of whose pairs go has none"""
+    offsets, pair_j, pair_cos = np.asarray(offsets, np.int64), np.asarray(pair_j, np.int64), np.asarray(pair_cos, np.float64)
+    keep = np.asarray(keep, bool)
+    n = len(offsets) - 1
+    if not pair_j.shape == pair_cos.shape == keep.shape == (int(offsets[-1]),):
+        raise ValueError("pair_j {}, pair_cos {} and keep {} do not belong to {} pairs".format(pair_j.shape, pair_cos.shape,
+                                                                                              keep.shape, int(offsets[-1])))
+    later = np.repeat(np.arange(n, dtype=np.int64), np.diff(offsets))
+    out = np.zeros(n + 1, np.int64)
+    out[1:] = np.cumsum(np.bincount(later[keep], minlength=n))
+    return out, pair_j[keep], pair_cos[keep]
+
+
+def confirm_similarity_counts(cos_b):
+    """for every g of SIMILARITY_GRID how many of the first view's pairs have a cosine >= g in the second view: one run is
+    enough to pick dedup.confirm_threshold"""
+    cos_b = np.asarray(cos_b, np.float64)
+    return OrderedDict((repr(g), int((cos_b >= g).sum())) for g in SIMILARITY_GRID)
 
 
 def choose_kept(root, keep, a2=None):
@@ -470,6 +537,36 @@ def check_groups(opts):
     return True, keep, MAX_PAIRS if max_pairs is None else int(max_pairs), groups_path
 
 
+def check_confirm(opts, views=None, view=None):
+    """the keys of the confirmation in a second view -> (confirm_view, confirm_threshold); (None, None): the run of today.  The
+    two keys go together, need dedup.groups=True and are refused with dedup.against_path; confirm_view has the form "a/b" and
+    differs from dedup.view (view: the resolved one, once the cache is known) and, with views (the names the cache holds), is
+    one of them.  Pure: no device, no file"""
+    opts = opts or {}
+    cview, cthr = opts.get('confirm_view'), opts.get('confirm_threshold')
+    if cview is None and cthr is None:
+        return None, None
+    if cview is None or cthr is None:
+        raise ValueError("dedup.confirm_view and dedup.confirm_threshold go together: --dedup.confirm_view=<model_key>/<layer> "
+                         "--dedup.confirm_threshold=<t2 in (0, 1]>")
+    if opts.get('against_path') is not None:
+        raise ValueError("dedup.confirm_view is refused with dedup.against_path: the confirmation filters the pair list of the "
+                         "groups mode, a run against a held-out set has none")
+    if not opts.get('groups'):
+        raise ValueError("dedup.confirm_view needs --dedup.groups=True: the confirmed relation is a pair list, and the groups mode "
+                         "is the one that has it")
+    if isinstance(cthr, bool) or not isinstance(cthr, numbers.Real) or not 0.0 < float(cthr) <= 1.0:
+        raise ValueError("dedup.confirm_threshold must be a number in (0, 1], not {!r}".format(cthr))
+    if not isinstance(cview, str) or cview.count('/') != 1:
+        raise ValueError("dedup.confirm_view must be \"<model_key>/<layer>\", not {!r}".format(cview))
+    view = opts.get('view') if view is None else view
+    if cview == view:
+        raise ValueError("dedup.confirm_view={!r} is dedup.view: a second view confirms the pairs of the first".format(cview))
+    if views is not None and cview not in list(views):
+        raise ValueError("dedup.confirm_view={!r} is not a view of the cache (it has {})".format(cview, ', '.join(views)))
+    return cview, float(cthr)
+
+
 def check_options(opts, views=None, epoch=None, k=None):
     """the `dedup` options -> (threshold, view, out_path, report_path).  Pure: no device, no file.  views: the names
     "<model_key>/<layer>" the cache holds, once it is known (None: dedup.view is only checked for its form); epoch:
@@ -479,6 +576,7 @@ def check_options(opts, views=None, epoch=None, k=None):
     check_against_options(opts)
     check_probes(opts, k)
     check_groups(opts)
+    check_confirm(opts)
     thr = opts.get('threshold')
     if thr is None:
         raise ValueError("dedup needs --dedup.threshold=<t in (0, 1]>: the cosine from which a row counts as a duplicate of an "
@@ -498,6 +596,7 @@ def check_options(opts, views=None, epoch=None, k=None):
             view = views[0]
         elif view not in views:
             raise ValueError("dedup.view={!r} is not a view of the cache (it has {})".format(view, ', '.join(views)))
+        check_confirm(opts, views=views, view=view)
     if epoch is not None:
         if isinstance(epoch, (list, tuple)) and len(epoch) == 1:
             epoch = epoch[0]
@@ -535,6 +634,12 @@ def dedup(args):
     v = next((key for key in view_dims if '/'.join(key[1:]) == view), None)
     if v is None:
         raise ValueError("the shards hold no view {} (they have {})".format(view, ', '.join('/'.join(key[1:]) for key in view_dims)))
+    cview, cthr = check_confirm(opts, views=sorted(names), view=view)
+    vb = None
+    if cview is not None:
+        vb = next((key for key in view_dims if '/'.join(key[1:]) == cview), None)
+        if vb is None:
+            raise ValueError("the shards hold no view {} (they have {})".format(cview, ', '.join('/'.join(key[1:]) for key in view_dims)))
     dev = current_device(args)
     dt = cache.find(saved, v)
     front = FrontEnd.from_attrs(dt)
@@ -580,8 +685,38 @@ def dedup(args):
     labels, _ = km.calc_best(x, need_mean=False)  # a row's label is a pure function of the row and the state
     groups_mode, keep, max_pairs, groups_path = check_groups(opts)
     if groups_mode:
+        confirm = None
+        if vb is not None:
+            frontb = FrontEnd.from_attrs(cache.find(saved, vb))  # B is compared in the space it was clustered in
+            frontb.check_width(vb, view_dims[vb])
+            db = frontb.width_out(view_dims[vb])
+
+            def second_view(rows):
+                """the rows `rows` (ascending global row numbers) of view B after its front-end, gathered on the device one row
+                group at a time: view B is never held in one piece by this pass (a streamed run reads the shards again)"""
+                need_b = 4 * len(rows) * db
+                beside_b = groups.budget // 2 if groups.streamed else 4 * n_total * max(view_dims[vb], db)
+                free_b, _ = torch.cuda.mem_get_info()
+                if need_b + beside_b > free_b:  # refused before the second pass starts
+                    raise ValueError("dedup gathers the rows of view {} that occur in a pair: {} rows x {} columns need {} bytes on "
+                                     "the device ({} more for a row group), {} are free; raise dedup.threshold, or dedup a part of "
+                                     "the shards".format(cview, len(rows), db, need_b, beside_b, free_b))
+                groups.add_front_ends({vb: frontb})
+                buf = torch.empty((len(rows), db), dtype=torch.float32, device=x.device)
+                at = 0
+                for _gi, _table, rows_b in groups.iterate(views={vb}):
+                    part = rows_b[vb]
+                    lo, hi = (int(c) for c in np.searchsorted(rows, [at, at + part.shape[0]]))
+                    if hi > lo:
+                        buf[lo:hi] = part[torch.from_numpy(rows[lo:hi] - at).to(part.device)]
+                    at += part.shape[0]
+                if at != n_total:
+                    raise RuntimeError("the second pass delivered {} rows, the first {}".format(at, n_total))
+                return buf
+
+            confirm = (cview, cthr, second_view)
         return _dedup_groups(args, km, x, labels, K, threshold, keep, max_pairs, view, epoch, out_path, groups_path, report_path,
-                             (shard_name, filename))
+                             (shard_name, filename), confirm)
     lists = each = None
     if probes == 1:
         best, partner = nearest_earlier(x, labels, k=K)
@@ -602,14 +737,32 @@ def dedup(args):
     return report
 
 
-def _dedup_groups(args, km, x, labels, K, threshold, keep, max_pairs, view, epoch, out_path, groups_path, report_path, names):
-    """the groups mode of the verb: every pair over the threshold, their connected components, one kept row per group"""
+def _dedup_groups(args, km, x, labels, K, threshold, keep, max_pairs, view, epoch, out_path, groups_path, report_path, names,
+                  confirm=None):
+    """the groups mode of the verb: every pair over the threshold, their connected components, one kept row per group.
+    confirm (confirm_view, confirm_threshold, second_view: rows -> their rows of that view on the device): only the pairs that
+    also reach confirm_threshold in the second view count"""
     best, partner, offsets, pair_j, pair_cos = pairs_earlier(x, labels, threshold, k=K, max_pairs=max_pairs)
     n = len(best)
+    before = None
+    if confirm is not None:
+        cview, cthr, second_view = confirm
+        root_a = components(n, offsets, pair_j)  # what view A alone would join: on the host, no device
+        size_a = np.bincount(root_a, minlength=n)
+        before = [('confirm_view', cview), ('confirm_threshold', cthr), ('pairs_before_confirm', int(offsets[n])),
+                  ('groups_before_confirm', int((size_a >= 2).sum())), ('removed_before_confirm', int(n - (size_a >= 1).sum()))]
+        cos_b = np.empty(0, np.float64)
+        if offsets[n]:  # no pair in view A: nothing to confirm, the second pass is skipped
+            _later, rows, ci, cj = pair_rows(offsets, pair_j)
+            cos_b = pair_cosines(second_view(rows), ci, cj)
+        before.append(('confirm_similarity_counts', confirm_similarity_counts(cos_b)))
+        offsets, pair_j, pair_cos = confirm_pairs(offsets, pair_j, pair_cos, cos_b >= cthr)
     root = components(n, offsets, pair_j)
     a2 = km.quality(x, labels, rows=True)[1][:, 0] if keep == 'central' else None
     kept = choose_kept(root, keep, a2)
     report = summarise_groups(best, partner, _host(labels), K, threshold, offsets, root, kept, keep)
+    if before is not None:  # flagged, similarity_counts and the nearest-earlier rule stay those of view A alone
+        report.update(before)
     report.update(view=view, epoch=int(epoch), feature_path=str(args.data.path), clusters_path=str(args.data.output.path))
     out_path = _write_removed_csv(out_path, root, kept, pair_similarity(n, offsets, pair_j, pair_cos), names)
     if groups_path is not None:
@@ -618,6 +771,12 @@ def _dedup_groups(args, km, x, labels, K, threshold, keep, max_pairs, view, epoc
           "nearest-earlier rule; wrote {}".format(view, epoch, report['groups'], threshold, report['pairs'], report['removed'],
                                                   report['n'], keep, report['removed_beyond_nearest_rule'], out_path))
     print("groups of size " + "  ".join("{}: {}".format(b, c) for b, c in report['group_size_counts'].items()))
+    if before is not None:
+        print("confirmed in view {} at cosine >= {!r}: pairs {} -> {}, groups {} -> {}, removed rows {} -> {}; pairs with a cosine "
+              "there >= ".format(report['confirm_view'], report['confirm_threshold'], report['pairs_before_confirm'], report['pairs'],
+                                 report['groups_before_confirm'], report['groups'], report['removed_before_confirm'],
+                                 report['removed'])
+              + "  ".join("{}: {}".format(g, c) for g, c in report['confirm_similarity_counts'].items()))
     _write_report(report_path, report)
     return report
 

@@ -348,20 +348,34 @@ class KMeans:
         lists = self.probe_centers(batch, probes, labels) if probes != 1 else None
         return nearest_earlier(batch, labels, k=self._shape[0], device="cuda:{}".format(self._device), probes=lists)
 
-    def duplicate_groups(self, batch, threshold, labels=None, keep='first'):
+    def duplicate_groups(self, batch, threshold, labels=None, keep='first', confirm=None, confirm_threshold=None):
         """The groups of rows that cosines >= threshold inside a cluster connect (clustering/dedup.py: pairs_earlier,
         components, choose_kept) -> (root int64 [b]: the lowest row of every row's group, the row itself outside the groups;
         kept bool [b]: True outside the groups and for one row per group).  keep='first': the root; 'central': the member
         nearest to its centre (quality(rows=True)'s a2, ties to the lower row).  labels=None: calc_best(batch,
-        need_mean=False)'s.  Unlike near_duplicates' flags the groups do not depend on the order of the rows."""
-        from .dedup import choose_kept, components, pairs_earlier
+        need_mean=False)'s.  Unlike near_duplicates' flags the groups do not depend on the order of the rows.
+        confirm [b, d2] with confirm_threshold in (0, 1] (the two go together): the rows of a second view, in that view's own
+        space; only the pairs whose cosine there (dedup.pair_cosines) reaches confirm_threshold join rows."""
+        from .dedup import choose_kept, components, confirm_pairs, pair_cosines, pair_rows, pairs_earlier
         self._require_handle()
         if keep not in ('first', 'central'):
             raise ValueError("keep must be 'first' or 'central', not {!r}".format(keep))
+        if (confirm is None) != (confirm_threshold is None):
+            raise ValueError("confirm and confirm_threshold go together: the rows of a second view and the cosine a pair must reach there")
+        if confirm is not None:
+            if not 0.0 < float(confirm_threshold) <= 1.0:
+                raise ValueError("confirm_threshold must be in (0, 1], not {!r}".format(confirm_threshold))
+            if len(confirm.shape) != 2 or confirm.shape[0] != batch.shape[0]:
+                raise ValueError("confirm {} must hold a row of the second view for each of the {} rows".format(
+                    tuple(confirm.shape), batch.shape[0]))
         if labels is None:
             labels, _ = self.calc_best(batch, need_mean=False)
-        _best, _partner, offsets, pair_j, _cos = pairs_earlier(batch, labels, threshold, k=self._shape[0],
-                                                               device="cuda:{}".format(self._device))
+        _best, _partner, offsets, pair_j, cos = pairs_earlier(batch, labels, threshold, k=self._shape[0],
+                                                              device="cuda:{}".format(self._device))
+        if confirm is not None and len(pair_j):
+            later = pair_rows(offsets, pair_j)[0]
+            cos_b = pair_cosines(confirm, later, pair_j, device="cuda:{}".format(self._device))
+            offsets, pair_j, cos = confirm_pairs(offsets, pair_j, cos, cos_b >= float(confirm_threshold))
         root = components(len(offsets) - 1, offsets, pair_j)
         a2 = self.quality(batch, labels, rows=True)[1][:, 0] if keep == 'central' else None
         return root, choose_kept(root, keep, a2)

@@ -205,6 +205,10 @@ CLUSTERING_DEFAULTS = {
     #   dedup.keep         first (default: a group's first row in shard order) or central (the member nearest to its centre)
     #   dedup.max_pairs    the most pairs a run may hold (default 2^27, 16 bytes each on the device and on the host)
     #   dedup.groups_path  optional: every member of every group, group,group_size,kept,shard_name,filename
+    #   dedup.confirm_view       "<model_key>/<layer>", another view than dedup.view: a pair of dedup.view counts only if its
+    #                            cosine in this view reaches confirm_threshold too (a re-upload matches in both views, a shared
+    #                            slide or song in one).  Needs groups=True, refused with against_path.  Goes with:
+    #   dedup.confirm_threshold  a number in (0, 1]: the cosine a pair must reach in confirm_view
     'debug': False,
 }
 

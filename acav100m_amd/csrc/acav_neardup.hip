@@ -52,6 +52,11 @@
 // the count sweep's list, order kept): the walker stores those columns in ascending position from offsets[i] on, never at or
 // beyond offsets[i + 1]; a count that differs from the first raises a flag (ACAV_ESTATE).  No atomics, no sort; a pair's
 // cosine is the value the count sweep compared, the same chain.  acav_pairs_components: union-find on the host, no device.
+//
+// A list of pairs (acav_pairs_cosine; dedup.pair_cosines, `dedup --dedup.confirm_view=`): the cosines of given pairs (i, j) of
+// another array -- no labels, no runs, no walk.  k_paircos puts 16 pair_i rows and 16 pair_j rows of a wave through k_neardup's
+// stage loop and keeps the diagonal of the one accumulator: the kernel is bound by the gather, and the same instruction over
+// the same stages makes a pair's cosine the bytes the sweeps above give for it.
 #include <algorithm>
 #include <cmath>
 #include <numeric>
@@ -940,6 +945,120 @@ struct NdSetup {
     }
 };
 
+// ---- acav_pairs_cosine: the cosines of a LIST of pairs (i, j) of x [n] -- the confirmation of a pair list in a second view
+
+constexpr int PC_WAVE = 16;           // pairs of a wave per round: the diagonal of one 16 x 16 accumulator
+constexpr int PC_WG = 4 * PC_WAVE;    // pairs of a workgroup per round
+constexpr int PC_WG_PER_CU = 8;       // the grid stops growing there: 8 x 18 KB of LDS and 32 waves fill a compute unit
+constexpr size_t PC_LDS = sizeof(float) * 2 * PC_WG * ND_ST;  // the pair_i rows and the pair_j rows of one stage
+
+struct PcPlan {
+    int64_t wgs, rounds;
+    size_t scratch;
+};
+
+// workgroup b takes the rounds b, b + wgs, ...: round r holds the pairs [64 r, 64 r + 64), in the caller's order
+PcPlan paircos_plan(int64_t pairs, int cus)
+{
+    PcPlan p;
+    const int64_t rounds = (pairs + PC_WG - 1) / PC_WG;
+    p.wgs = std::min<int64_t>(rounds, (int64_t)cus * PC_WG_PER_CU);
+    p.rounds = p.wgs ? (rounds + p.wgs - 1) / p.wgs : 0;
+    // host lists staged on the device (16 per pair), a norm per pair end at the most (16), host cosines (8), the two counters
+    p.scratch = (size_t)pairs * 40 + 16;
+    return p;
+}
+
+// indices outside [0, n): counted before anything is indexed with one
+__global__ __launch_bounds__(256) void k_pc_indices(const int64_t *__restrict__ pi, const int64_t *__restrict__ pj, int64_t pairs,
+                                                    int64_t n, unsigned long long *__restrict__ bad)
+{
+    unsigned long long mine = 0;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < pairs; e += (int64_t)gridDim.x * 256)
+        mine += (pi[e] < 0 || pi[e] >= n ? 1ull : 0ull) + (pj[e] < 0 || pj[e] >= n ? 1ull : 0ull);
+    if (mine) atomicAdd(bad, mine);
+}
+
+// k_nd_norms' chain, one wave at a time over the entries c, c + waves, ...: nrm[c] = ||x[rows[c]]||^2 (rows NULL: row c itself)
+__global__ __launch_bounds__(64) void k_pc_norms(const float *__restrict__ x, int d, const int64_t *__restrict__ rows, int64_t count,
+                                                 double *__restrict__ nrm)
+{
+    for (int64_t c = blockIdx.x; c < count; c += gridDim.x) {
+        const size_t base = (size_t)(rows ? rows[c] : c) * d;
+        double p = 0.0;
+        for (int j = threadIdx.x; j < d; j += 64) {
+            const double v = (double)x[base + j];
+            p = fma(v, v, p);
+        }
+        for (int o = 32; o >= 1; o >>= 1) p = p + __shfl_xor(p, o);
+        if (threadIdx.x == 0) nrm[c] = p;
+    }
+}
+
+// one wave: 16 pairs per round, the pair_i rows as the A operand and the pair_j rows as the B operand of k_neardup's MFMA chain
+// (the same stages of ND_DK columns, zero-filled tails included); only the diagonal of the accumulator is a result: pair p of
+// the wave is register p / 4 of the lane with lane & 15 == p and lane >> 4 == p % 4.  na / nb: the norms of the two ends, by
+// ROW (by_row) or by pair.  Every index has been checked; the cosines leave by plain vector stores
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_paircos(const float *__restrict__ x, int d, const int64_t *__restrict__ pi,
+                                                 const int64_t *__restrict__ pj, int64_t pairs, const double *__restrict__ na,
+                                                 const double *__restrict__ nb, int by_row, int64_t rounds, double *__restrict__ cos)
+{
+    __shared__ float as[PC_WG * ND_ST];  // [PC_WG][ND_ST]: a stage of the pair_i rows
+    __shared__ float bs[PC_WG * ND_ST];  // of the pair_j rows
+
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int fr = lane & 15, fq = lane >> 4;  // fragment row (A) / column (B) and k index of this lane
+    const int lq = t & 7, lr = t >> 3;         // this thread stages columns 4 lq .. 4 lq + 3 of the pairs lr + 32 u
+    const double inf = __builtin_inf();
+
+    for (int64_t r = 0; r < rounds; ++r) {
+        const int64_t e0 = (r * gridDim.x + blockIdx.x) * PC_WG;
+        if (e0 >= pairs) break;  // the same for every thread of the workgroup
+        const float *arow[2], *brow[2];
+        bool ok[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int64_t e = e0 + lr + 32 * u;
+            ok[u] = e < pairs;
+            arow[u] = x + (size_t)pi[ok[u] ? e : e0] * d;
+            brow[u] = x + (size_t)pj[ok[u] ? e : e0] * d;
+        }
+        f64x4 acc = f64x4{0.0, 0.0, 0.0, 0.0};
+        float4 pa[2], pb[2];  // the next chunk, in flight while the current one is multiplied
+#pragma unroll
+        for (int u = 0; u < 2; ++u) pa[u] = nd_fetch<VEC>(arow[u], d, 4 * lq), pb[u] = nd_fetch<VEC>(brow[u], d, 4 * lq);
+        for (int j0 = 0; j0 < d; j0 += ND_DK) {
+            __syncthreads();  // the previous stage (of this round or the last) has been read
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                *reinterpret_cast<float4 *>(&as[(lr + 32 * u) * ND_ST + 4 * lq]) = nd_mask(pa[u], ok[u], d, j0 + 4 * lq);
+                *reinterpret_cast<float4 *>(&bs[(lr + 32 * u) * ND_ST + 4 * lq]) = nd_mask(pb[u], ok[u], d, j0 + 4 * lq);
+            }
+            __syncthreads();
+            if (j0 + ND_DK < d) {
+#pragma unroll
+                for (int u = 0; u < 2; ++u)
+                    pa[u] = nd_fetch<VEC>(arow[u], d, j0 + ND_DK + 4 * lq), pb[u] = nd_fetch<VEC>(brow[u], d, j0 + ND_DK + 4 * lq);
+            }
+#pragma unroll
+            for (int kk = 0; kk < ND_DK / 4; ++kk) {
+                const double a = (double)as[(wave * PC_WAVE + fr) * ND_ST + kk * 4 + fq];
+                const double b = (double)bs[(wave * PC_WAVE + fr) * ND_ST + kk * 4 + fq];
+                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
+            }
+        }
+        // C/D of the f64 MFMA: column = lane & 15, row = (lane >> 4) + 4 * register; the diagonal element of pair fr
+        const int64_t e = e0 + wave * PC_WAVE + fr;
+        if (fq == (fr & 3) && e < pairs) {
+            const int reg = fr >> 2;
+            const double dot = reg == 0 ? acc[0] : reg == 1 ? acc[1] : reg == 2 ? acc[2] : acc[3];
+            const double qn = na[by_row ? pi[e] : e], cn = nb[by_row ? pj[e] : e];
+            cos[e] = (qn > 0.0 && cn > 0.0) ? dot / sqrt(qn * cn) : -inf;
+        }
+    }
+}
+
 }  // namespace
 
 ACAV_EXPORT int acav_rows_neardup_plan(const int64_t *hist, int k, int d, int cus, int64_t *out, int64_t *tiles, int64_t cap)
@@ -1367,6 +1486,84 @@ ACAV_EXPORT int acav_rows_probedup(int device, const float *x, int64_t n, const 
     if (!best_dev) ACAV_HIP_TRY(hipMemcpyAsync(best, obest.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
     if (!partner_dev) ACAV_HIP_TRY(hipMemcpyAsync(partner, opartner.p, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, st));
     if (best_each && !each_dev) ACAV_HIP_TRY(hipMemcpyAsync(best_each, oeach.p, sizeof(double) * cells, hipMemcpyDeviceToHost, st));
+    ACAV_HIP_TRY(hipStreamSynchronize(st));
+    return ACAV_OK;
+}
+
+ACAV_EXPORT int acav_pairs_cosine_plan(int64_t pairs, int d, int cus, int64_t *out)
+{
+    ACAV_REQUIRE(out, ACAV_EINVAL, "NULL argument");
+    ACAV_REQUIRE(pairs >= 0 && d >= 1 && d <= ND_MAX_D && cus > 0, ACAV_EINVAL, "bad sizes");
+    const PcPlan p = paircos_plan(pairs, cus);
+    out[0] = PC_WAVE, out[1] = PC_WG, out[2] = p.wgs, out[3] = p.rounds, out[4] = (int64_t)PC_LDS, out[5] = (int64_t)p.scratch;
+    return ACAV_OK;
+}
+
+ACAV_EXPORT int acav_pairs_cosine(int device, const float *x, int64_t n, int d, const int64_t *pair_i, const int64_t *pair_j,
+                                  int64_t pairs, double *cos, void *stream)
+{
+    ACAV_REQUIRE(x && cos, ACAV_EINVAL, "NULL argument");
+    ACAV_REQUIRE(n >= 1 && n <= ND_MAX_N, ACAV_EINVAL, "n=%lld must be in [1, 2^31): positions are 32-bit", (long long)n);
+    ACAV_REQUIRE(d >= 1 && d <= ND_MAX_D, ACAV_EINVAL, "d=%d must be in [1, %d]", d, ND_MAX_D);
+    ACAV_REQUIRE(pairs >= 0, ACAV_EINVAL, "pairs=%lld must not be negative", (long long)pairs);
+    ACAV_REQUIRE(pairs == 0 || (pair_i && pair_j), ACAV_EINVAL, "%lld pairs with a NULL pair_i or pair_j", (long long)pairs);
+    if (pairs == 0) return ACAV_OK;
+    int cus = 0;
+    ACAV_TRY(use_device(device, &cus));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+
+    DevBuf stage_x, stage_i, stage_j, bad, nrm, ocos;
+    StreamDrain drain = {st};
+    const void *dx = nullptr, *di = nullptr, *dj = nullptr;
+    const size_t total = (size_t)n * d;
+    ACAV_TRY(to_device(x, sizeof(float) * total, stage_x, st, &dx));
+    ACAV_TRY(to_device(pair_i, sizeof(int64_t) * (size_t)pairs, stage_i, st, &di));
+    ACAV_TRY(to_device(pair_j, sizeof(int64_t) * (size_t)pairs, stage_j, st, &dj));
+    const float *xd = static_cast<const float *>(dx);
+    const int64_t *pi = static_cast<const int64_t *>(di), *pj = static_cast<const int64_t *>(dj);
+    ACAV_TRY(bad.ensure(sizeof(unsigned long long) * 2));  // [0] indices out of range, [1] values not finite
+    ACAV_HIP_TRY(hipMemsetAsync(bad.p, 0, sizeof(unsigned long long) * 2, st));
+    hipLaunchKernelGGL(k_pc_indices, dim3((unsigned)std::min<int64_t>((pairs + 255) / 256, 4096)), dim3(256), 0, st, pi, pj, pairs, n,
+                       bad.as<unsigned long long>());
+    ACAV_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_nd_finite, dim3((unsigned)std::min<size_t>((total + 255) / 256, (size_t)cus * 8)), dim3(256), 0, st, xd, total,
+                       bad.as<unsigned long long>() + 1);
+    ACAV_HIP_TRY(hipGetLastError());
+    unsigned long long nbad[2] = {0, 0};
+    ACAV_HIP_TRY(hipMemcpyAsync(nbad, bad.p, sizeof(nbad), hipMemcpyDeviceToHost, st));
+    ACAV_HIP_TRY(hipStreamSynchronize(st));
+    ACAV_REQUIRE(nbad[0] == 0, ACAV_EINVAL, "%llu of the 2 x %lld pair indices are outside [0, %lld)", nbad[0], (long long)pairs,
+                 (long long)n);
+    ACAV_REQUIRE(nbad[1] == 0, ACAV_EINVAL, "%llu of the %lld x %d values are not finite (inf or NaN)", nbad[1], (long long)n, d);
+
+    // the norms: one per row where that is no more than one per pair end (the rows are then read once, in order), else one per
+    // pair end -- the same chain on the same values either way
+    const bool by_row = n <= 2 * pairs;
+    const int64_t norms = by_row ? n : 2 * pairs;
+    ACAV_TRY(nrm.ensure(sizeof(double) * (size_t)norms));
+    double *na = nrm.as<double>(), *nb = by_row ? na : na + pairs;
+    const int64_t per = by_row ? n : pairs;
+    const unsigned waves = (unsigned)std::min<int64_t>(per, (int64_t)1 << 20);
+    hipLaunchKernelGGL(k_pc_norms, dim3(waves), dim3(64), 0, st, xd, d, by_row ? (const int64_t *)nullptr : pi, per, na);
+    ACAV_HIP_TRY(hipGetLastError());
+    if (!by_row) {
+        hipLaunchKernelGGL(k_pc_norms, dim3(waves), dim3(64), 0, st, xd, d, pj, per, nb);
+        ACAV_HIP_TRY(hipGetLastError());
+    }
+
+    const PcPlan plan = paircos_plan(pairs, cus);
+    const bool cos_dev = is_device_ptr(cos);
+    if (!cos_dev) ACAV_TRY(ocos.ensure(sizeof(double) * (size_t)pairs));
+    double *dcos = cos_dev ? cos : ocos.as<double>();
+    const bool vec = d % 4 == 0 && (reinterpret_cast<uintptr_t>(xd) & 15) == 0;
+    if (vec)
+        hipLaunchKernelGGL((k_paircos<true>), dim3((unsigned)plan.wgs), dim3(256), 0, st, xd, d, pi, pj, pairs, na, nb, by_row ? 1 : 0,
+                           plan.rounds, dcos);
+    else
+        hipLaunchKernelGGL((k_paircos<false>), dim3((unsigned)plan.wgs), dim3(256), 0, st, xd, d, pi, pj, pairs, na, nb, by_row ? 1 : 0,
+                           plan.rounds, dcos);
+    ACAV_HIP_TRY(hipGetLastError());
+    if (!cos_dev) ACAV_HIP_TRY(hipMemcpyAsync(cos, ocos.p, sizeof(double) * (size_t)pairs, hipMemcpyDeviceToHost, st));
     ACAV_HIP_TRY(hipStreamSynchronize(st));
     return ACAV_OK;
 }
